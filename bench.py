@@ -19,7 +19,12 @@ row + 16 B slot + 16 B output pair) over the probe phase's HIP-event time;
 16 B slot per probe tuple: north_star's "HBM read roofline").
 `roofline.kernel` is the same for the dominant kernel (the LDS join: the one
 hj_ctx_join_kernel names -- k_join_b / k_join_u / k_join_grp) alone.
-Launch:  python bench.py [--gpus 1 --steps K --warmup W --config C3]
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds what the headline figure does not need, each a run of its own outside the
+timed steps: the in-process copy floor (roofline.floor_ms, copy_floor), the
+host-memref leg (host_memref, C3 only) and the CPU baseline (cpu_baseline).
+--dump-outputs DIR writes the last timed step's result pairs (dump_outputs).
+Launch:  python bench.py [--gpus 1 --steps K --warmup W --config C3] [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 """
 import argparse
@@ -139,9 +144,14 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C3", choices=sorted(CONFIGS))
     ap.add_argument("--seed", type=lambda x: int(x, 0), default=0x5EED)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample-log2", type=int, default=22)
-    ap.add_argument("--no-host-leg", action="store_true", help="skip the host-memref (PCIe-inclusive) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the in-process copy floor "
+                         "(roofline.floor_ms), the host-memref leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--cpu-sample-log2", type=int, default=22, help="with --full: CPU baseline sample, 2^N rows")
+    ap.add_argument("--no-host-leg", action="store_true", help="with --full: skip the host-memref (PCIe-inclusive) leg")
     ap.add_argument("--verify", action="store_true", help="check the last step's output properties")
     ap.add_argument("--strategy", default="auto", choices=["auto", "global", "radix"])
     ap.add_argument("--radix-bits", type=int, default=0)
@@ -149,7 +159,7 @@ def parse():
                     help="use the multi-GPU code path (partition + all-to-all) even at N=1")
     ap.add_argument("--s-parts", type=int, default=0,
                     help="multi-GPU path: batches the shuffled probe side moves in (0: hashjoin.dist default)")
-    ap.add_argument("--no-floor", action="store_true", help="skip the in-process copy floor (roofline.floor_ms)")
+    ap.add_argument("--no-floor", action="store_true", help="with --full: skip the in-process copy floor (roofline.floor_ms)")
     ap.add_argument("--log2", type=int, default=0,
                     help="experiments: |R| = |S| = 2^LOG2 rows instead of the config's sizes (not a bench line)")
     return ap.parse_args()
@@ -350,6 +360,50 @@ def copy_floor(hashjoin, reps=5):
     return res
 
 
+# ---------------------------------------------------------------- output dump
+DUMP_SAMPLE_ROWS = 1 << 20   # 3 float64 columns of 2^20 rows: 24 MiB
+_MIX_R = 0x9E3779B97F4A7C15 - (1 << 64)   # odd 64-bit multipliers (as int64) of the pair fingerprint
+_MIX_S = 0xC2B2AE3D27D4EB4F - (1 << 64)
+
+
+def dump_outputs(outdir, o_r, o_s, seed, suffix=""):
+    """Write what the timed path returned in its last step -- the M result
+    pairs (out_r[i], out_s[i]) -- as float64 DIR/<name>.npy.  The join emits
+    its pairs in no fixed order, so they are put in the canonical order
+    (sorted by out_s, then out_r) first: two builds that compute the same
+    join then write the same files.
+      result_rows  [M]
+      out_r, out_s the canonical pairs; a seeded sample of DUMP_SAMPLE_ROWS of
+                   them when M is larger
+      sample_pos   the sample's positions in the canonical order
+      fingerprint  order-independent sums over ALL M pairs: each column's low
+                   24 bits and the rest, and a 20-bit hash of every pair
+    The values are row ids / payloads below 2^53, exact in float64."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    m = o_r.numel()
+    r, s = o_r.long(), o_s.long()
+    if m:
+        assert int(torch.maximum(r.abs().max(), s.abs().max())) < (1 << 53), "output values not exact in float64"
+    mix = ((r * _MIX_R + s * _MIX_S) >> 40) & 0xFFFFF
+    fp = [int(x.sum()) for x in (r & 0xFFFFFF, r >> 24, s & 0xFFFFFF, s >> 24, mix)]
+    del mix
+    r, i = torch.sort(r, stable=True)
+    s = s[i]
+    s, i = torch.sort(s, stable=True)
+    r = r[i]
+    del i
+    if m > DUMP_SAMPLE_ROWS:
+        g = torch.Generator().manual_seed(seed)
+        pos = torch.sort(torch.randint(0, m, (DUMP_SAMPLE_ROWS,), generator=g)).values
+        r, s = r[pos.to(r.device)], s[pos.to(s.device)]
+    else:
+        pos = torch.arange(m)
+    for name, v in (("result_rows", [m]), ("out_r", r.cpu().numpy()), ("out_s", s.cpu().numpy()),
+                    ("sample_pos", pos.numpy()), ("fingerprint", fp)):
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), np.asarray(v, dtype=np.float64))
+
+
 # ---------------------------------------------------------------- main
 def gen_inputs(hashjoin, a, NR, NS, distn, r0, nr, s0, ns):
     if distn == "pkfk":
@@ -494,12 +548,14 @@ def main():
                 phases["build"] += ev["routed"].elapsed_time(ev["built"])
                 phases["probe"] += ev["built"].elapsed_time(ev["probed"])
             last["m"] = o_r.numel()
+            if a.dump_outputs:
+                last["out"] = (o_r, o_s)
             last["rows"] = ev["rows"]
             last["mode"] = ev["mode"] + (", folded routing" if ev.get("folded") else "")
 
-    # the box's own copy rate (outside the timed steps): every line states how
-    # far its probe phase is from it (roofline.floor_ms / phase_over_floor)
-    floor = None if a.no_floor else copy_floor(hashjoin)
+    # --full: the box's own copy rate (outside the timed steps), so the line
+    # states how far its probe phase is from it (roofline.floor_ms / phase_over_floor)
+    floor = copy_floor(hashjoin) if a.full and not a.no_floor else None
     for _ in range(a.warmup):
         step(False)
     torch.cuda.synchronize()
@@ -540,6 +596,10 @@ def main():
         m_total = m_local
     if expect_m is not None and m_total != expect_m:
         raise SystemExit(f"join produced {m_total} rows, expected {expect_m}")
+
+    if a.dump_outputs:
+        o_r, o_s = last.pop("out") if use_dist else (out_r, out_s)
+        dump_outputs(a.dump_outputs, o_r[:m_local], o_s[:m_local], a.seed, f"_rank{rank}" if world > 1 else "")
 
     if a.verify and not use_dist:
         o_r, o_s = out_r[:m_local].long(), out_s[:m_local].long()
@@ -649,9 +709,9 @@ def main():
                                                "different GPU, not a like-for-like baseline"}
     if per_rank is not None:
         line["per_rank"] = per_rank
-    if rank == 0 and not use_dist and not a.no_host_leg and a.config == "C3":
+    if a.full and rank == 0 and not use_dist and not a.no_host_leg and a.config == "C3":
         line["host_memref"] = host_leg(hashjoin, a.seed)
-    if rank == 0 and not use_dist and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not use_dist and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(a.seed, a.cpu_sample_log2)
     elif rank == 0:
         line["cpu_baseline"] = None
