@@ -56,9 +56,6 @@ constexpr int kJoinSub = 8;        // sub-chunks per work item (one table build 
 constexpr int kPackedRow = 3;      // SrcForm of packed-row inputs
 constexpr int kBucketed = 4;       // SrcForm of a previous pass's bucket set
 constexpr unsigned kNoBucket = 0xFFFFFFFFu;
-// Join items of multi-chunk partitions first (k_item_desc): int64 rows only
-// (profiles/r03_heavy_first.txt).
-constexpr bool kHeavyFirst = true;
 
 __device__ __forceinline__ u64 rhash(u64 k) { return radix_hash(k); }
 
@@ -1250,7 +1247,7 @@ struct JoinArgs {
     // repeated}; modes: bit m = this launch runs when sample_mode() == m
     const u64 *sample = nullptr;
     unsigned modes = 7u;
-    // k_join_b (i32 rows): items past a workgroup's first two are handed out
+    // k_join_b (not DETECT): items past a workgroup's first two are handed out
     // by this counter (zeroed by k_item_desc) instead of w += grid, so
     // workgroups that drew heavy items (a hot key's chunks) take fewer
     unsigned *next_item = nullptr;
@@ -1376,6 +1373,44 @@ __global__ __launch_bounds__(256) void k_item_desc(const unsigned *work_start, c
     desc[at] = d;
 }
 
+// --------------------------------------------------------------- shared join steps
+// Run entries (row << 7 | count; 0 = none) of a wave's n row slots: slot i of
+// wave `wave` (of NW) is run lo + i * NW + wave, below hi.  The words are
+// wave-uniform: scalar loads (sload) into SGPRs.
+template <int NW>
+__device__ __forceinline__ void wave_ents(const u64 *list, u64 lo, u64 hi, unsigned wave, u64 *e, int n) {
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+        const u64 li = lo + (u64)i * NW + wave;
+        e[i] = li < hi ? sload(list + li) : 0ull;
+    }
+}
+
+// The rows of n run entries, lane `lane` row `lane` of each; bit i of the
+// result: v[i] is a row of run i.  Every lane loads (a lane past its run's
+// end re-reads the run's first row; no run: row 0), so the loads are
+// straight-line code and the build waits for the R rows only (vmcnt(SI)),
+// not for the S rows behind them.
+template <typename T>
+__device__ __forceinline__ unsigned wave_rows(const T *rows, const u64 *e, unsigned lane, T *v, int n) {
+    unsigned ok = 0;
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+        const bool in = lane < (unsigned)(e[i] & 127u);
+        v[i] = ld_s<kNtJoinLd>(rows + (e[i] >> 7) + (in ? lane : 0u));
+        ok |= (unsigned)in << i;
+    }
+    return ok;
+}
+
+// The context's "build keys repeat" flag.  A workgroup stores it once
+// (its dup_sent), from one thread: every table with a repeated key storing to
+// the one flag serialised those stores at the memory side (C1-ref at 2^28:
+// +3.5 ms, micro/join_micro.hip mode 1).
+__device__ __forceinline__ void set_dup_flag(const JoinArgs &a) {
+    __hip_atomic_store(a.dup_flag, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // A persistent workgroup of NT threads walks work items w = wg, wg + grid, ...
 // Work item = (partition, chunk of up to kJoinSub * NT * SI / 64 S runs):
 // build the partition's R runs into a 2^TSL-slot LDS table (rounds of
@@ -1384,19 +1419,17 @@ __global__ __launch_bounds__(256) void k_item_desc(const unsigned *work_start, c
 // ABL (diagnostics only, micro/join_micro.hip; the product uses 0) switches
 // phases off: 1 no cursor atomic, 2 no output writes, 4 no probe, 8 no build,
 // 16 probe reads the first slot only.
-// WPS: minimum waves per SIMD (4: <= 128 VGPRs, 2 workgroups of 512 per CU;
-// 2: <= 256 VGPRs).  RCAPX: build rows per round (0: 5/8 of the slots).
+// 4 waves per SIMD at least (<= 128 VGPRs, 2 workgroups of 512 per CU).
 // LIST: the items of a.list (what the fast kernels deferred) instead of all.
-template <bool WIDE, bool WRITE, int TSL, int NT, int ABL = 0, int SI_ = kJoinItems, int WPS = 4, int RCAPX = 0,
-          bool LIST = false>
-__global__ __launch_bounds__(NT, WPS) void k_join(JoinArgs a) {
+template <bool WIDE, bool WRITE, int TSL, int NT, int ABL = 0, bool LIST = false>
+__global__ __launch_bounds__(NT, 4) void k_join(JoinArgs a) {
     typedef Row<WIDE> R;
     typedef typename R::T T;
     typedef typename std::conditional<WIDE, u64, unsigned>::type PT;   // output element
     constexpr int TS = 1 << TSL;
     constexpr unsigned kMask = TS - 1;
-    constexpr int SI = SI_;                   // S rows per thread per sub-chunk
-    constexpr int RCAP = RCAPX ? RCAPX : TS * 5 / 8;   // build rows per round (load factor <= 0.625)
+    constexpr int SI = kJoinItems;            // S rows per thread per sub-chunk
+    constexpr int RCAP = TS * 5 / 8;          // build rows per round (load factor <= 0.625)
     constexpr int RI = RCAP / NT;             // build rows per thread per round
     constexpr int SUBR = NT * SI;             // rows per sub-chunk
     constexpr unsigned rb = (unsigned)RCAP >> kRunLog;       // runs per build round
@@ -1405,10 +1438,10 @@ __global__ __launch_bounds__(NT, WPS) void k_join(JoinArgs a) {
     static_assert((rb << kRunLog) == RCAP && (subb << kRunLog) == SUBR, "rounds must be whole runs");
     // A round loads RI rows per thread (runs lo + i * NW + wave) but steps
     // the run cursor by rb: rows past RI * NT in a round would never be
-    // built.  Round 5's dropped int64 shape (512 threads over 2048 slots:
-    // RCAP 1280, RI 2 -> 1024 rows loaded per 1280 stepped) lost one build
-    // row in five in every deferred partition -- 16,986 of 20,942 pairs on a
-    // 1-bit plan.
+    // built.  512 threads over 2048 slots is such a shape (RCAP 1280, RI 2
+    // -> 1024 rows loaded per 1280 stepped): it loses one build row in five
+    // in every deferred partition -- 16,986 of 20,942 pairs on a 1-bit plan
+    // (VERDICT r05 item 6).
     static_assert(RI * NT == RCAP, "a build round must load exactly RCAP rows");
     // wide: EMPTY key INT64_MIN (rows with that key take the null path);
     // narrow: the all-ones word (row ids < 2^31 never produce it)
@@ -1544,11 +1577,8 @@ __global__ __launch_bounds__(NT, WPS) void k_join(JoinArgs a) {
             if (dup) s_dup = 1u;
             __syncthreads();
             const bool unique = s_dup == 0u;
-            // once per workgroup: every table with a repeated key storing to
-            // the one flag serialised those stores at the memory side (C1-ref
-            // at 2^28: +3.5 ms, micro/join_micro.hip mode 1)
-            if (!unique && !dup_sent) {
-                if (threadIdx.x == 0) __hip_atomic_store(a.dup_flag, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!unique && !dup_sent) {   // once per workgroup (set_dup_flag)
+                if (threadIdx.x == 0) set_dup_flag(a);
                 dup_sent = true;
             }
 
@@ -1870,7 +1900,7 @@ __global__ __launch_bounds__(NT, WPS) void k_join(JoinArgs a) {
 // any of its pairs is written) and k_join joins the list afterwards.
 // Run entries, table, duplicate-free probe walk, ballot-compacted output
 // and the ONE cursor atomic per sub-chunk are as in k_join; a partition
-// with a repeated build key (GEN) takes a plain per-row walk to EMPTY.
+// with a repeated build key takes a plain per-row walk to EMPTY.
 __device__ __forceinline__ ItemDesc sload(const ItemDesc *p) {
     const u64 *q = (const u64 *)p;
     return ItemDesc{sload(q), sload(q + 1), sload(q + 2), sload(q + 3)};
@@ -1893,7 +1923,7 @@ struct JoinUSmem {
     u64 wsum[16];
 };
 
-template <bool WIDE, bool WRITE, int TSL, int NT, int RI, int SI, int WPS, bool GEN = true, int ABL = 0>
+template <bool WIDE, bool WRITE, int TSL, int NT, int RI, int SI, int WPS, int ABL = 0>
 __device__ __forceinline__ void join_u_body(JoinArgs a, JoinUSmem<WIDE, TSL, NT, SI> &sm) {
     typedef Row<WIDE> R;
     typedef typename R::T T;
@@ -1933,26 +1963,8 @@ __device__ __forceinline__ void join_u_body(JoinArgs a, JoinUSmem<WIDE, TSL, NT,
     const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
     const int lane = threadIdx.x & 63;
     const u64 lt = lane ? (~0ull >> (64 - lane)) : 0ull;
-    auto ents = [&](const u64 *list, u64 lo, u64 hi, u64 *e, int n) {
-#pragma unroll
-        for (int i = 0; i < n; ++i) {
-            const u64 li = lo + (u64)i * NW + wv0;
-            e[i] = li < hi ? sload(list + li) : 0ull;
-        }
-    };
-    // Every lane loads (a lane past its run's end re-reads the run's first
-    // row; no run: row 0), so the loads are straight-line code and the build
-    // waits for the R rows only (vmcnt(SI)), not for the S rows behind them.
-    auto rows_of = [&](const T *rows, const u64 *e, T *v, int n) {
-        unsigned ok = 0;
-#pragma unroll
-        for (int i = 0; i < n; ++i) {
-            const bool in = off < (unsigned)(e[i] & 127u);
-            v[i] = ld_s<kNtJoinLd>(rows + (e[i] >> 7) + (in ? off : 0u));
-            ok |= (unsigned)in << i;
-        }
-        return ok;
-    };
+    auto ents = [&](const u64 *list, u64 lo, u64 hi, u64 *e, int n) { wave_ents<NW>(list, lo, hi, wv0, e, n); };
+    auto rows_of = [&](const T *rows, const u64 *e, T *v, int n) { return wave_rows(rows, e, off, v, n); };
     T sv_[SI], rv_[RI];
     u64 er[RI], es[SI];
     ItemDesc it = sload(a.desc + w);
@@ -2030,7 +2042,7 @@ __device__ __forceinline__ void join_u_body(JoinArgs a, JoinUSmem<WIDE, TSL, NT,
             ents(a.r_runs, r0, it.r_hi, er, RI);
             rok = rows_of(rrows, er, rv_, RI);
             }
-            if (bad || (!GEN && ndup)) s_bad = 1u;
+            if (bad) s_bad = 1u;
             if (ndup) atomicAdd(&s_dup, ndup);
             __syncthreads();
             const unsigned nd = s_dup;
@@ -2040,8 +2052,8 @@ __device__ __forceinline__ void join_u_body(JoinArgs a, JoinUSmem<WIDE, TSL, NT,
             // k_join's wave-cooperative writes take them, before any probe
             const bool defer_it = s_bad ||
                                   (!WIDE && WRITE && (u64)nd * 4u > (it.r_hi - it.r_lo) << kRunLog);
-            if (!unique && !dup_sent) {   // once per workgroup (k_join)
-                if (threadIdx.x == 0) __hip_atomic_store(a.dup_flag, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!unique && !dup_sent) {   // once per workgroup (set_dup_flag)
+                if (threadIdx.x == 0) set_dup_flag(a);
                 dup_sent = true;
             }
             if (defer_it) {
@@ -2059,7 +2071,7 @@ __device__ __forceinline__ void join_u_body(JoinArgs a, JoinUSmem<WIDE, TSL, NT,
 #pragma unroll
                     for (int i = 0; i < SI; ++i)
                         if (((sok >> i) & 1u) && !(WIDE && R::key(sv_[i]) == kEmptyKey64) && !(ABL & 4)) pm |= 1u << i;
-                    if (GEN && !unique) {
+                    if (!unique) {
                         // a repeated build key: every row walks its chain to
                         // EMPTY, counting, then again writing at its prefix
                         unsigned cnt = 0, mb = 0u;   // mb bit i: row slot i has a match
@@ -2215,10 +2227,15 @@ __device__ __forceinline__ void join_u_body(JoinArgs a, JoinUSmem<WIDE, TSL, NT,
     }
 }
 
-template <bool WIDE, bool WRITE, int TSL, int NT, int RI, int SI, int WPS, bool GEN = true, int ABL = 0>
+// (The kernel is its LDS and a call.  Written into the kernel, the body's
+// statements compile to another instruction stream -- the stream shape's
+// count-only kernel at 46 instead of 48 VGPRs, in another order; so do they
+// with sm reached through a local pointer -- and that stream is unmeasured:
+// the split stays, for k_join_b likewise.)
+template <bool WIDE, bool WRITE, int TSL, int NT, int RI, int SI, int WPS, int ABL = 0>
 __global__ __launch_bounds__(NT, WPS) void k_join_u(JoinArgs a) {
     __shared__ JoinUSmem<WIDE, TSL, NT, SI> sm;
-    join_u_body<WIDE, WRITE, TSL, NT, RI, SI, WPS, GEN, ABL>(a, sm);
+    join_u_body<WIDE, WRITE, TSL, NT, RI, SI, WPS, ABL>(a, sm);
 }
 
 // k_join_b: k_join_u's item loop, loads, defer rules and output compaction
@@ -2255,12 +2272,6 @@ __global__ __launch_bounds__(NT, WPS) void k_join_u(JoinArgs a) {
 // i32 rows keep keys and row ids apart (a bucket's keys are one 16-B read);
 // an item whose probe rows would write many pairs per row (the reference's
 // keys in [1, 100k]) goes to k_join_grp before anything of it is written.
-// the int64 rows' fast join shape (see "join shapes" below)
-constexpr int kFastNTc = 768, kFastRIc = 3, kFastSIc = 3, kFastWPSc = 6;
-#ifndef HJ_WIDE_DYN
-#define HJ_WIDE_DYN 1   // int64 rows claim items from a counter (0: static w += grid, for A/B)
-#endif
-
 template <bool WIDE, int NT, int SI, bool DETECT, int TSL>
 struct JoinBSmem {
     static constexpr int TS = 1 << TSL, NB = TS / 4, NW = NT / 64;
@@ -2361,11 +2372,7 @@ __device__ __forceinline__ void join_b_body(JoinArgs a, JoinBSmem<WIDE, NT, SI, 
         if constexpr (WIDE) {
             // entries lo + i * NW + wv0 (the wide shape measured 1-3 % slower
             // with the narrow one's contiguous entries: profiles/r04_join_entries.txt)
-#pragma unroll
-            for (int i = 0; i < n; ++i) {
-                const u64 li = lo + (u64)i * NW + wv0;
-                e[i] = li < hi ? sload(list + li) : 0ull;
-            }
+            wave_ents<NW>(list, lo, hi, wv0, e, n);
             return (unsigned)n;
         }
         const u64 b0 = lo + (u64)wv0 * n;
@@ -2374,6 +2381,8 @@ __device__ __forceinline__ void join_b_body(JoinArgs a, JoinBSmem<WIDE, NT, SI, 
         for (int i = 0; i < n; ++i) e[i] = sload(list + bl + i);
         return b0 < hi ? (hi - b0 < (u64)n ? (unsigned)(hi - b0) : (unsigned)n) : 0u;
     };
+    // (wave_rows' loop, written out: with the call the i32 kernels compile to
+    // another instruction stream)
     auto rows_of = [&](const T *rows, const u64 *e0, unsigned nv, T *v, int n) {
         unsigned ok = 0;
         u64 e[RI > SI ? RI : SI];
@@ -2415,7 +2424,7 @@ __device__ __forceinline__ void join_b_body(JoinArgs a, JoinBSmem<WIDE, NT, SI, 
     unsigned nvr = ents(a.r_runs, it.r_lo, it.r_hi, er, RI), nvs = 0;
     // (DETECT reads no probe rows)
     if (!DETECT) nvs = ents(a.s_runs, it.s_lo, it.s_lo + subb < it.s_hi ? it.s_lo + subb : it.s_hi, es, SI);
-    constexpr bool dyn = !DETECT && (!WIDE || HJ_WIDE_DYN);
+    constexpr bool dyn = !DETECT;
     if (dyn) {
         if (threadIdx.x == 0) s_next = w + gridDim.x;
         __syncthreads();
@@ -2595,7 +2604,7 @@ __device__ __forceinline__ void join_b_body(JoinArgs a, JoinBSmem<WIDE, NT, SI, 
                 if (twin) s_ctl[1] = 1u;
                 __syncthreads();
                 if (threadIdx.x == 0 && s_ctl[1] && !dup_sent) {
-                    __hip_atomic_store(a.dup_flag, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    set_dup_flag(a);
                     dup_sent = true;
                 }
             } else {
@@ -2738,7 +2747,7 @@ __device__ __forceinline__ void join_b_body(JoinArgs a, JoinBSmem<WIDE, NT, SI, 
                             // a probe row met a repeated build key: the
                             // context's repeat flag, once per workgroup (k_join)
                             if (s_ctl[1] && !dup_sent) {
-                                __hip_atomic_store(a.dup_flag, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                set_dup_flag(a);
                                 dup_sent = true;
                             }
                         }
@@ -2792,7 +2801,6 @@ __global__ __launch_bounds__(NT, WPS) void k_join_b(JoinArgs a) {
     join_b_body<WIDE, WRITE, NT, RI, SI, WPS, DETECT, TSL>(a, sm);
 }
 
-
 // --------------------------------------------------------------- grouped join
 // k_join_grp: narrow rows (the reference's i32 keys / row ids) whose build
 // keys repeat many times -- join-performances.md:3-6's 10M x 10M keys in
@@ -2812,15 +2820,15 @@ __global__ __launch_bounds__(NT, WPS) void k_join_b(JoinArgs a) {
 // probing build walked every row past all earlier copies of its key (REF-A:
 // 0.65 ms of CAS walks) and the probe scanned the mixed cluster 64 slots per
 // step (profiles/r02_refa_join_ablation.txt).  Items of more than 63 runs
-// (> TS - 64 build rows) go to a.defer (k_join's rounds take them).  LIST: the items of a.list
-// (k_join_u's deferrals) instead of all.
+// (> TS - 64 build rows) go to a.defer (k_join's rounds take them).  Its items are
+// those of a.list (the fast kernel's deferrals), or all of them (join_uses_list).
 // WIDE (int64 key / int64 payload rows, round 5): the same grouping over
 // 2048 slots -- gkey holds the key (EMPTY = INT64_MIN: an item with that
 // build key goes to a.defer), gcnt the counts, grow the payloads -- at two
 // workgroups per CU (48 KiB of LDS each; at three the writing kernel spilled
 // at 80 VGPRs); REF-A's keys as int64 rows (REF-A64) took k_join's
 // linear-probing rounds 10.8 ms.
-template <bool WIDE, bool WRITE, int NT, int RI, int SI, bool LIST>
+template <bool WIDE, bool WRITE, int NT, int RI, int SI>
 __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
     typedef Row<WIDE> R;
     typedef typename R::T T;
@@ -2844,7 +2852,7 @@ __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
     __shared__ u64 wsum[16];
     __shared__ u64 s_base;
     __shared__ unsigned s_rep, s_bad;
-    const bool use_list = LIST && join_uses_list(a);
+    const bool use_list = join_uses_list(a);
     const unsigned total = use_list ? *a.list_n : a.work_start[a.P];
     if (!join_runs(a)) return;
     const T *rrows = (const T *)a.r;
@@ -2854,23 +2862,8 @@ __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
     const unsigned wv0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
     const unsigned lane = threadIdx.x & 63u;
     bool dup_sent = false;
-    auto ents = [&](const u64 *list, u64 lo, u64 hi, u64 *e, int n) {
-#pragma unroll
-        for (int i = 0; i < n; ++i) {
-            const u64 li = lo + (u64)i * NW + wv0;
-            e[i] = li < hi ? sload(list + li) : 0ull;
-        }
-    };
-    auto rows_of = [&](const T *rows, const u64 *e, T *v, int n) {
-        unsigned ok = 0;
-#pragma unroll
-        for (int i = 0; i < n; ++i) {
-            const bool in = lane < (unsigned)(e[i] & 127u);
-            v[i] = ld_s<kNtJoinLd>(rows + (e[i] >> 7) + (in ? lane : 0u));
-            ok |= (unsigned)in << i;
-        }
-        return ok;
-    };
+    auto ents = [&](const u64 *list, u64 lo, u64 hi, u64 *e, int n) { wave_ents<NW>(list, lo, hi, wv0, e, n); };
+    auto rows_of = [&](const T *rows, const u64 *e, T *v, int n) { return wave_rows(rows, e, lane, v, n); };
     // a slot's key / count
     auto key_is = [&](u64 e, u64 key) { return WIDE ? e == key : (e >> 32) == key; };
     auto count_at = [&](unsigned h, u64 e) -> unsigned { return WIDE ? gcnt[h] : (unsigned)e; };
@@ -2948,8 +2941,8 @@ __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
             if (rep) s_rep = 1u;
         }
         __syncthreads();
-        if (s_rep && !dup_sent) {   // once per workgroup (k_join)
-            if (threadIdx.x == 0) __hip_atomic_store(a.dup_flag, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (s_rep && !dup_sent) {   // once per workgroup (set_dup_flag)
+            if (threadIdx.x == 0) set_dup_flag(a);
             dup_sent = true;
         }
         // ---- placement: payloads (row ids) into their key's group
@@ -3067,7 +3060,7 @@ __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
 // Fast shape: 768 threads, 3 build + 3 probe rows per thread, 6 waves per
 // SIMD (profiles/r02_join_fast.txt: C3 k_join 3.50 -> 2.81 ms, C2 12.34 ->
 // 9.45 ms, C1-ref 1.31 -> 0.96 ms; k_join_b: C3 2.77 -> 2.55 ms).
-constexpr int kFastNT = kFastNTc, kFastRI = kFastRIc, kFastSI = kFastSIc, kFastWPS = kFastWPSc;
+constexpr int kFastNT = 768, kFastRI = 3, kFastSI = 3, kFastWPS = 6;
 // probe sides much larger than the build side (C2: 2^30 x 2^20, ~1000 S rows
 // per R row): many sub-chunks per item, so bigger sub-chunks and more waves
 // (1024 threads x 4 S rows, 8 waves per SIMD): C2 join 9.45 -> 8.77 ms, C3
@@ -3121,12 +3114,11 @@ inline unsigned blocks_for(u64 n, u64 per) { return (unsigned)((n + per - 1) / p
 
 // Workgroups of a partition pass over n rows: one per CU, fewer for small
 // inputs (each open bucket per workgroup and bin is potential slack).
-unsigned pass_grid(u64 n) {
-    const u64 tiles = (n + kTile - 1) / kTile;
+inline unsigned grid_of_tiles(u64 tiles, u64 most) {
     const u64 g = tiles / 8 > 0 ? tiles / 8 : 1;   // >= 8 tiles per workgroup
-    const u64 cus = (u64)cu_count();
-    return (unsigned)(g < cus ? g : cus);
+    return (unsigned)(g < most ? g : most);
 }
+unsigned pass_grid(u64 n) { return grid_of_tiles((n + kTile - 1) / kTile, (u64)cu_count()); }
 
 // The k_pass variant of a pass of fb bits: passes of <= 8 bits run the
 // half-size workgroups, two per CU (kSmallPassThreads).
@@ -3141,10 +3133,7 @@ inline unsigned pass_tile_rows(int fb, bool wide = true) {
 }
 unsigned pass_grid(u64 n, int fb, bool wide = true) {
     if (!small_pass(fb)) return pass_grid(n);
-    const u64 tiles = (n + pass_tile_rows(fb, wide) - 1) / pass_tile_rows(fb, wide);
-    const u64 g = tiles / 8 > 0 ? tiles / 8 : 1;
-    const u64 w = 2ull * (u64)cu_count();
-    return (unsigned)(g < w ? g : w);
+    return grid_of_tiles((n + pass_tile_rows(fb, wide) - 1) / pass_tile_rows(fb, wide), 2ull * (u64)cu_count());
 }
 
 // Exclusive scan of a u64 array of len elements in place (k_scan_*).
@@ -3571,6 +3560,45 @@ hipError_t radix_partition_routed(const void *tuples, long long n, const unsigne
     return radix_passes(src, (u64)(n > 0 ? n : 0), true, pl, 1, &in, nseg, ws, out, st);
 }
 
+// The JoinArgs every launch of a join shares: both sides' rows, runs and
+// starts, the work map and item descriptors, the LDS slot shift, the outputs,
+// the pair counter, the repeat flag and the build-time sample.  A stage
+// copies them and adds exactly the fields it reads (item source, deferral
+// list, modes, ...): the rest keep JoinArgs' defaults.
+JoinArgs join_args(bool wide, const RadixPlan &pl, const BucketSet &r, const BucketSet &s, int P,
+                   const unsigned *work_start, const void *desc, void *out_r, void *out_s, long long cap, u64 *counter,
+                   u64 *dup_flag, const u64 *sample) {
+    JoinArgs a{};
+    a.r = r.rows;
+    a.s = s.rows;
+    a.r_runs = r.runs;
+    a.s_runs = s.runs;
+    a.r_rstart = r.rstart;
+    a.s_rstart = s.rstart;
+    a.P = P;
+    a.work_start = work_start;
+    a.desc = (const ItemDesc *)desc;
+    // the hash bits right below the partition bits: LDS slot / bucket
+    a.tshift = 64 - pl.skip - pl.total_bits - (wide ? kTableLog : kTableLogNarrow);
+    a.out_r = out_r;
+    a.out_s = out_s;
+    a.cap = cap;
+    a.counter = counter;
+    a.dup_flag = dup_flag;
+    a.sample = sample;
+    return a;
+}
+// A deferred-item list in the work area is its count word n, then the items:
+// the stage that appends to it, and the stage that joins it.
+inline void defers_to(JoinArgs &a, unsigned *n) {
+    a.defer = n + 1;
+    a.defer_n = n;
+}
+inline void takes_list(JoinArgs &a, const unsigned *n) {
+    a.list = n + 1;
+    a.list_n = n;
+}
+
 hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
                       unsigned long long s_runs, unsigned *work_start, void *desc, void *out_r, void *out_s, long long cap,
                       unsigned long long *counter, unsigned long long *dup_flag, bool count_only, hipStream_t st,
@@ -3593,128 +3621,76 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
     u64 chb = (u64)kJoinSub * subb;
     const u64 want = (u64)s_runs / (16ull * (wide ? pg : pgn));
     if (want > chb) chb = (want + subb - 1) / subb * subb;
-    // heavy-first item order for int64 rows (longest items claimed first);
-    // i32 rows keep partition order (k_join_grp lost 0.2 ms on REF-A with it)
-    const bool heavy_first = kHeavyFirst && wide;
+    // heavy-first item order (k_item_desc: items of multi-chunk partitions
+    // first, so the longest items are claimed first) for int64 rows
+    // (profiles/r03_heavy_first.txt); i32 rows keep partition order
+    // (k_join_grp lost 0.2 ms on REF-A with it)
+    const bool heavy_first = wide;
     chunk_map_one(s.rstart, r.rstart, P, (unsigned)chb, work_start, work_owner, ws, st, heavy_first);
     const unsigned items = (unsigned)((u64)s_runs / chb + (u64)P + 1);
-    // the deferred-item lists live after the work map: the fast kernels'
-    // (for k_join, or for k_join_grp with i32 rows), then k_join_grp's
-    unsigned *defer_n = work_owner + radix_join_items(pl, s_runs);
-    unsigned *defer2_n = defer_n + 1 + radix_join_items(pl, s_runs);
-    unsigned *next_item = defer2_n + 1 + radix_join_items(pl, s_runs);
+    // the deferred-item lists live after the work map: list 1 is the fast
+    // kernel's, list 2 the grouped kernel's; then the fast kernel's item counter
+    unsigned *list1 = work_owner + radix_join_items(pl, s_runs);
+    unsigned *list2 = list1 + 1 + radix_join_items(pl, s_runs);
+    unsigned *next_item = list2 + 1 + radix_join_items(pl, s_runs);
     hipLaunchKernelGGL(k_item_desc, dim3(blocks_for(items, 256)), dim3(256), 0, st, (const unsigned *)work_start,
                        (const unsigned *)work_owner, (const u64 *)s.rstart, (const u64 *)r.rstart, P, (unsigned)chb,
-                       (ItemDesc *)desc, defer_n, defer2_n, next_item,
+                       (ItemDesc *)desc, list1, list2, next_item,
                        heavy_first ? (const u64 *)ws.pcur : nullptr, counter);
-    JoinArgs a;
-    a.r = r.rows;
-    a.s = s.rows;
-    a.r_runs = r.runs;
-    a.s_runs = s.runs;
-    a.r_rstart = r.rstart;
-    a.s_rstart = s.rstart;
-    a.P = P;
-    a.work_start = work_start;
-    a.desc = (const ItemDesc *)desc;
-    // the hash bits right below the partition bits: LDS slot / bucket
-    a.tshift = 64 - pl.skip - pl.total_bits - (wide ? kTableLog : kTableLogNarrow);
-    a.out_r = out_r;
-    a.out_s = out_s;
-    a.cap = cap;
-    a.counter = counter;
-    a.dup_flag = dup_flag;
-    a.sample = sample;
-    a.defer = defer_n + 1;
-    a.defer_n = defer_n;
+    const JoinArgs base = join_args(wide, pl, r, s, P, work_start, desc, out_r, out_s, cap, counter, dup_flag, sample);
     const unsigned grid = items < pg ? items : pg;
-#define HJ_LAUNCH(K, NT) hipLaunchKernelGGL(K, dim3(grid), dim3(NT), 0, st, a)
-#define HJ_WR(K_T, K_F, NT)      \
-    do {                         \
-        if (count_only) HJ_LAUNCH(K_F, NT); \
-        else HJ_LAUNCH(K_T, NT); \
+// kernel K<WIDE, WRITE, ...> over the items' persistent grid: the writing
+// instantiation, or the count-only one
+#define HJ_JOIN(K, GRID, NT, ARGS, WIDE, ...)                                                                   \
+    do {                                                                                                        \
+        if (count_only) hipLaunchKernelGGL((K<WIDE, false, __VA_ARGS__>), dim3(GRID), dim3(NT), 0, st, ARGS);   \
+        else hipLaunchKernelGGL((K<WIDE, true, __VA_ARGS__>), dim3(GRID), dim3(NT), 0, st, ARGS);               \
     } while (0)
-    if (wide) {
-        if (stream_shape) {
-            a.modes = kModesAll;
-            HJ_WR((k_join_u<true, true, kTableLog, kStreamNT, kStreamRI, kStreamSI, kStreamWPS>),
-                  (k_join_u<true, false, kTableLog, kStreamNT, kStreamRI, kStreamSI, kStreamWPS>), kStreamNT);
-        } else {
-            // k_join_b unless most build keys repeat; then k_join takes every
-            // item (below, the same launch that takes k_join_b's deferrals:
-            // no exit-only launch of a kernel the sample did not choose).
-            // (k_join_u served mode 2 before round 5 in a launch of its own;
-            // both bodies in one kernel spilled 20 B at the 80-VGPR cap.)
-            a.modes = kModeUnique | kModeSome;
-            if (HJ_WIDE_DYN) a.next_item = next_item;
-            HJ_WR((k_join_b<true, true, kFastNT, kFastRI, kFastSI, kFastWPS>),
-                  (k_join_b<true, false, kFastNT, kFastRI, kFastSI, kFastWPS>), kFastNT);
-            a.next_item = nullptr;
-            // k_join_grp (int64 rows, 2048 slots, two workgroups per CU):
-            // k_join_b's deferrals, or every item when most build keys
-            // repeat; what it defers (INT64_MIN build keys, > 31 runs) goes
-            // to k_join below
-            a.modes = kModesAll;
-            a.list = defer_n + 1;
-            a.list_n = defer_n;
-            a.all_if_mode2 = true;
-            a.defer = defer2_n + 1;
-            a.defer_n = defer2_n;
-            {
-                const unsigned g3 = items < (unsigned)(kGrpWidePerCU * cu_count()) ? items
-                                                                                   : (unsigned)(kGrpWidePerCU * cu_count());
-                if (count_only)
-                    hipLaunchKernelGGL((k_join_grp<true, false, kGrpNT, kGrpWideRI, kGrpWideSI, true>), dim3(g3),
-                                       dim3(kGrpNT), 0, st, a);
-                else
-                    hipLaunchKernelGGL((k_join_grp<true, true, kGrpNT, kGrpWideRI, kGrpWideSI, true>), dim3(g3),
-                                       dim3(kGrpNT), 0, st, a);
-            }
-            a.all_if_mode2 = false;
-        }
+
+    // ---- stage 1, the fast kernel: every item, deferring to list 1 what it
+    // cannot take.  The stream shape's k_join_u runs whatever the sample
+    // says.  k_join_b (int64 rows: the fast shape; i32 rows: keys and row ids
+    // apart in LDS, a bucket's 4 keys one 16-B read) runs unless most build
+    // keys repeat -- stage 2 takes every item then, in the launch that takes
+    // the deferrals otherwise (no exit-only launch of a kernel the sample did
+    // not choose; k_join_u and k_join_b as two bodies of one kernel spilled
+    // 20 B at the 80-VGPR cap) -- and claims its items from next_item.
+    JoinArgs fast = base;
+    defers_to(fast, list1);
+    if (stream_shape) {
+        fast.modes = kModesAll;
+        HJ_JOIN(k_join_u, grid, kStreamNT, fast, true, kTableLog, kStreamNT, kStreamRI, kStreamSI, kStreamWPS);
     } else {
-        // i32 rows: k_join_b (keys and row ids apart in LDS: a bucket's 4
-        // keys are one 16-B read) unless most build keys repeat; k_join_grp
-        // takes its deferrals (list mode) or, for mostly repeated keys, every
-        // item
-        a.modes = kModeUnique | kModeSome;
-        {
-            const unsigned gn = items < pgn ? items : pgn;
-            a.next_item = next_item;
-            if (count_only)
-                hipLaunchKernelGGL((k_join_b<false, false, kNarrowNT, kNarrowRI, kNarrowSI, kNarrowWPS, false,
-                                             kTableLogNarrow>),
-                                   dim3(gn), dim3(kNarrowNT), 0, st, a);
-            else
-                hipLaunchKernelGGL((k_join_b<false, true, kNarrowNT, kNarrowRI, kNarrowSI, kNarrowWPS, false,
-                                             kTableLogNarrow>),
-                                   dim3(gn), dim3(kNarrowNT), 0, st, a);
-            a.next_item = nullptr;
-        }
-        // k_join_grp: k_join_b's deferrals, or every item when most build
-        // keys repeat (one launch either way)
-        a.modes = kModesAll;
-        a.list = defer_n + 1;
-        a.list_n = defer_n;
-        a.all_if_mode2 = true;
-        a.defer = defer2_n + 1;
-        a.defer_n = defer2_n;
-        HJ_WR((k_join_grp<false, true, kGrpNT, kGrpRI, kGrpSI, true>), (k_join_grp<false, false, kGrpNT, kGrpRI, kGrpSI, true>), kGrpNT);
-        a.all_if_mode2 = false;
+        fast.modes = kModeUnique | kModeSome;
+        fast.next_item = next_item;
+        if (wide) HJ_JOIN(k_join_b, grid, kFastNT, fast, true, kFastNT, kFastRI, kFastSI, kFastWPS);
+        else
+            HJ_JOIN(k_join_b, items < pgn ? items : pgn, kNarrowNT, fast, false, kNarrowNT, kNarrowRI, kNarrowSI,
+                    kNarrowWPS, false, kTableLogNarrow);
     }
-    // what the kernels above deferred (INT64_MIN build keys, oversized
-    // partitions, full tables): k_join over that list, a persistent grid that
-    // exits at once when it is empty
-    a.modes = kModesAll;
-    a.list = wide && stream_shape ? defer_n + 1 : defer2_n + 1;
-    a.list_n = wide && stream_shape ? defer_n : defer2_n;
-    a.all_if_mode2 = false;
-    if (wide) HJ_WR((k_join<true, true, kTableLog, 512, 0, kJoinItems, 4, 0, true>),
-                    (k_join<true, false, kTableLog, 512, 0, kJoinItems, 4, 0, true>), 512);
-    else HJ_WR((k_join<false, true, kTableLog, 512, 0, kJoinItems, 4, 0, true>),
-               (k_join<false, false, kTableLog, 512, 0, kJoinItems, 4, 0, true>), 512);
-#undef HJ_WR
-#undef HJ_LAUNCH
+    // ---- stage 2, the grouped kernel (not after the stream kernel): list 1,
+    // or every item when most build keys repeat (one launch either way);
+    // what it defers (INT64_MIN build keys, more runs than its table takes)
+    // goes to list 2.  int64 rows: 2048 slots, kGrpWidePerCU workgroups per CU.
+    if (!stream_shape) {
+        JoinArgs grp = base;
+        grp.modes = kModesAll;
+        takes_list(grp, list1);
+        grp.all_if_mode2 = true;
+        defers_to(grp, list2);
+        const unsigned pgw = (unsigned)(kGrpWidePerCU * cu_count());
+        if (wide) HJ_JOIN(k_join_grp, items < pgw ? items : pgw, kGrpNT, grp, true, kGrpNT, kGrpWideRI, kGrpWideSI);
+        else HJ_JOIN(k_join_grp, grid, kGrpNT, grp, false, kGrpNT, kGrpRI, kGrpSI);
+    }
+    // ---- stage 3, k_join: what the stages above deferred (INT64_MIN build
+    // keys, oversized partitions, full tables) -- list 2, or list 1 after the
+    // stream kernel; a persistent grid that exits at once when the list is empty
+    JoinArgs rest = base;
+    rest.modes = kModesAll;
+    takes_list(rest, stream_shape ? list1 : list2);
+    if (wide) HJ_JOIN(k_join, grid, 512, rest, true, kTableLog, 512, 0, true);
+    else HJ_JOIN(k_join, grid, 512, rest, false, kTableLog, 512, 0, true);
+#undef HJ_JOIN
     return hipGetLastError();
 }
 
@@ -3751,50 +3727,43 @@ hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, con
     unsigned *work_owner = work_start + P + 1;
     const unsigned whole = 0x7FFFFFFFu;   // runs per item: a partition is one item
     chunk_map_one(r.rstart, r.rstart, P, whole, work_start, work_owner, ws, st);
-    unsigned *defer_n = work_owner + radix_join_items(pl, 0);
+    unsigned *list1 = work_owner + radix_join_items(pl, 0);
     hipLaunchKernelGGL(k_item_desc, dim3(blocks_for((u64)P + 1, 256)), dim3(256), 0, st, (const unsigned *)work_start,
                        (const unsigned *)work_owner, (const u64 *)r.rstart, (const u64 *)r.rstart, P, whole,
-                       (ItemDesc *)desc, defer_n, nullptr, nullptr, nullptr, nullptr);
-    JoinArgs a{};
-    a.r = r.rows;
-    a.s = r.rows;
-    a.r_runs = r.runs;
-    a.s_runs = r.runs;
-    a.r_rstart = r.rstart;
-    a.s_rstart = r.rstart;
-    a.P = P;
-    a.work_start = work_start;
-    a.desc = (const ItemDesc *)desc;
-    a.tshift = 64 - pl.skip - pl.total_bits - (wide ? kTableLog : kTableLogNarrow);
-    a.dup_flag = dup_flag;
-    a.sample = sample;
-    a.modes = kModesAll;
-    // partitions the bucketed table cannot take (oversized) are deferred to
-    // k_join's list-mode build below, which flags repeats inside each of its
-    // build rounds
-    a.defer = defer_n + 1;
-    a.defer_n = defer_n;
+                       (ItemDesc *)desc, list1, nullptr, nullptr, nullptr, nullptr);
+    // (the probe side is the build side; no outputs, and no counter yet)
+    const JoinArgs base = join_args(wide, pl, r, r, P, work_start, desc, nullptr, nullptr, 0, nullptr, dup_flag, sample);
+    const unsigned pg = (unsigned)(2 * cu_count());
+    // ---- k_join_b's DETECT build of every partition.  Partitions the
+    // bucketed table cannot take (oversized) are deferred to k_join's
+    // list-mode build below, which flags repeats inside each of its build rounds
+    JoinArgs det = base;
+    det.modes = kModesAll;
+    defers_to(det, list1);
     if (wide)
-        hipLaunchKernelGGL((k_join_b<true, false, kFastNT, kFastRI, kFastSI, kFastWPS, true>), dim3(2 * cu_count()),
-                           dim3(kFastNT), 0, st, a);
+        hipLaunchKernelGGL((k_join_b<true, false, kFastNT, kFastRI, kFastSI, kFastWPS, true>), dim3(pg), dim3(kFastNT), 0,
+                           st, det);
     else
         // (its signature words and suspect list on top of the table: one
         // workgroup per CU at 8192 slots: 3 waves per SIMD, register budget as for 4)
         hipLaunchKernelGGL((k_join_b<false, false, kNarrowNT, kNarrowRI, kNarrowSI, (kTableLogNarrow > 12 ? 3 : kNarrowWPS),
                                      true, kTableLogNarrow>),
-                           dim3(kNarrowPerCU * cu_count()), dim3(kNarrowNT), 0, st, a);
-    // the deferred partitions: k_join builds them (its probe sees an empty S
-    // chunk: an item's S runs are [s_lo, s_lo) below)
-    a.list = defer_n + 1;
-    a.list_n = defer_n;
-    a.empty_s = true;
-    a.counter = ws.pcur;   // (no probe rows: nothing is counted; a valid word all the same)
-    if (wide)
-        hipLaunchKernelGGL((k_join<true, false, kTableLog, 512, 0, kJoinItems, 4, 0, true>), dim3(2 * cu_count()),
-                           dim3(512), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_join<false, false, kTableLog, 512, 0, kJoinItems, 4, 0, true>), dim3(2 * cu_count()),
-                           dim3(512), 0, st, a);
+                           dim3(kNarrowPerCU * cu_count()), dim3(kNarrowNT), 0, st, det);
+    // count-only k_join over list 1, counting into ws.pcur
+    auto join_list1 = [&](bool empty_s, const u64 *skip_if_set) {
+        JoinArgs rest = base;
+        rest.modes = kModesAll;
+        takes_list(rest, list1);
+        rest.counter = ws.pcur;
+        rest.empty_s = empty_s;
+        rest.skip_if_set = skip_if_set;
+        if (wide) hipLaunchKernelGGL((k_join<true, false, kTableLog, 512, 0, true>), dim3(pg), dim3(512), 0, st, rest);
+        else hipLaunchKernelGGL((k_join<false, false, kTableLog, 512, 0, true>), dim3(pg), dim3(512), 0, st, rest);
+    };
+    // ---- the deferred partitions: k_join builds them (its probe sees an
+    // empty S chunk -- an item's S runs are [s_lo, s_lo) -- so nothing is
+    // counted; the counter is a valid word all the same)
+    join_list1(true, nullptr);
     // That build flags a key repeated inside one of its rounds only.  The
     // exact answer for a deferred (oversized) partition: the count-only
     // self-join of its rows across every round (S = the partition itself)
@@ -3803,21 +3772,13 @@ hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, con
     // pcur[2] = k_defer_rows's done count.
     hipError_t e = hipMemsetAsync(ws.pcur, 0, 3 * sizeof(u64), st);
     if (e != hipSuccess) return e;
-    a.empty_s = false;
-    a.counter = ws.pcur;
     // (skipped when the launches above already found a repeat: a key that
     // repeats m times inside one partition has >= 2 copies in some build
     // round once m exceeds the rounds, so the self-join only ever runs over
     // partitions whose keys repeat at most once per round)
-    a.skip_if_set = dup_flag;
-    if (wide)
-        hipLaunchKernelGGL((k_join<true, false, kTableLog, 512, 0, kJoinItems, 4, 0, true>), dim3(2 * cu_count()),
-                           dim3(512), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_join<false, false, kTableLog, 512, 0, kJoinItems, 4, 0, true>), dim3(2 * cu_count()),
-                           dim3(512), 0, st, a);
-    hipLaunchKernelGGL(k_defer_rows, dim3(2 * cu_count()), dim3(256), 0, st, (const unsigned *)(defer_n + 1),
-                       (const unsigned *)defer_n, (const ItemDesc *)desc, (const u64 *)r.runs, ws.pcur, dup_flag);
+    join_list1(false, dup_flag);
+    hipLaunchKernelGGL(k_defer_rows, dim3(pg), dim3(256), 0, st, (const unsigned *)(list1 + 1), (const unsigned *)list1,
+                       (const ItemDesc *)desc, (const u64 *)r.runs, ws.pcur, dup_flag);
     return hipGetLastError();
 }
 

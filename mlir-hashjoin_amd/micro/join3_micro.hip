@@ -142,7 +142,7 @@ int body(int lg) {
     U(768, 2, 2, 8, 2, "768 thr 2+2, 2/CU");
     U(512, 4, 4, 6, 3, "512 thr 4+4, 3/CU");
 #define UA(ABL, NAME) \
-    run(NAME, [&] { hipLaunchKernelGGL((k_join_u<W, true, 12, 768, 3, 3, 6, true, ABL>), dim3(2 * cus), dim3(768), 0, 0, a); })
+    run(NAME, [&] { hipLaunchKernelGGL((k_join_u<W, true, 12, 768, 3, 3, 6, ABL>), dim3(2 * cus), dim3(768), 0, 0, a); })
     if (!W) {   // i32 rows: an 8192-slot table is 64 KiB, still 2 workgroups per CU
         a.tshift = 64 - pl.total_bits - 13;
         run("768 thr 3+3, 8192 slots", [&] { hipLaunchKernelGGL((k_join_u<W, true, 13, 768, 3, 3, 6>), dim3(2 * cus), dim3(768), 0, 0, a); });

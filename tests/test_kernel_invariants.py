@@ -27,8 +27,8 @@ def test_join_round_must_load_every_row(tmp_path):
     rows per thread per round but steps its run cursor by RCAP / 64 runs, and
     RCAP = 1280 is no multiple of 512.  The kernel now refuses such a shape at
     compile time; the product shapes compile."""
-    bad = _instantiate(tmp_path, "template __global__ void k_join<true, true, 11, 512, 0, kJoinItems, 4, 0, true>(JoinArgs);")
+    bad = _instantiate(tmp_path, "template __global__ void k_join<true, true, 11, 512, 0, true>(JoinArgs);")
     assert bad.returncode != 0
     assert "a build round must load exactly RCAP rows" in bad.stderr
-    good = _instantiate(tmp_path, "template __global__ void k_join<true, true, kTableLog, 512, 0, kJoinItems, 4, 0, true>(JoinArgs);")
+    good = _instantiate(tmp_path, "template __global__ void k_join<true, true, kTableLog, 512, 0, true>(JoinArgs);")
     assert good.returncode == 0, good.stderr[-2000:]
