@@ -145,6 +145,8 @@ int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 #define HJ_JOIN_KERNEL_STREAM 3
 #define HJ_JOIN_KERNEL_GROUPED 4
 #define HJ_JOIN_KERNEL_GENERAL 5
+/* k_join_exists: the last probe was a radix semi- / anti-join (hj_dev_exists_*) */
+#define HJ_JOIN_KERNEL_EXISTS 6
 int hj_ctx_join_kernel(hj_ctx *ctx);
 
 /* ------------------------------------------------------------ device phases
@@ -174,6 +176,41 @@ int hj_dev_build_i32(hj_ctx *ctx, const int32_t *rkey, int64_t n, int64_t row_ba
 int hj_dev_count_i32(hj_ctx *ctx, const int32_t *skey, int64_t n, uint64_t *d_count, void *stream);
 int hj_dev_probe_i32(hj_ctx *ctx, const int32_t *skey, int64_t n, int64_t row_base,
                      int32_t *out_r, int32_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
+
+/* Semi- and anti-join probes (EXISTS / NOT EXISTS) over the table an ordinary
+ * hj_dev_build_* left: one build serves inner, semi and anti probes in any
+ * order.  For the built relation R and the probe relation S,
+ *   HJ_EXISTS_SEMI: the S rows j for which some i has R.key[i] == S.key[j];
+ *   HJ_EXISTS_ANTI: the S rows for which no such i exists.
+ * Every S row is in exactly one of the two results and at most once, however
+ * often its key repeats in R; two S rows with equal keys are two rows.
+ * INT64_MIN is a key like any other (it matches iff R holds an INT64_MIN
+ * key).  R empty: semi is empty, anti is S.  S empty: both are empty.  Row
+ * order is unspecified, as for the inner join.
+ * out_s receives the S payload (i32: the row id row_base + row); out_key is
+ * optional (NULL skips it), else it receives the S key at the same index, so
+ * a semi-join's survivors can feed the next build or probe without a gather.
+ * out_cap == 0 with both outputs NULL is the count-only form (spay may be
+ * NULL then).  d_count = M, the exact number of qualifying rows, even when
+ * M > out_cap: rows past out_cap are dropped and nothing is written at or
+ * past index out_cap; bit 63 as above.
+ * Errors as hj_dev_probe_*: HJ_ERR_ARG (null context, bad relation, bad
+ * output, a kind other than the two), HJ_ERR_STATE (no build of that layout).
+ * Asynchronous on the stream, kernels only once hj_ctx_reserve /
+ * hj_ctx_reserve_probe sized the workspace (graph-capturable); the strategy
+ * is chosen as for hj_dev_probe_* and hj_ctx_strategy_used, the probe timing
+ * and hj_ctx_join_kernel (HJ_JOIN_KERNEL_EXISTS after a radix one) report the
+ * call.  The built table, R's partition, the side list and the "build keys
+ * repeat" flag are left untouched: an inner probe afterwards returns what it
+ * returned before, and hj_ctx_build_has_duplicates keeps its answer. */
+#define HJ_EXISTS_SEMI 0
+#define HJ_EXISTS_ANTI 1
+int hj_dev_exists_i64(hj_ctx *ctx, int kind, const int64_t *skey, const int64_t *spay, int64_t n, int64_t *out_key,
+                      int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_exists_tuples_i64(hj_ctx *ctx, int kind, const int64_t *tuples, int64_t n, int64_t *out_key,
+                             int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_exists_i32(hj_ctx *ctx, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t *out_key,
+                      int32_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
 
 /* Radix partition of rows into nparts (1..8192) groups by a key hash independent of
  * the table's slot hash: out_tuples (2*n int64) receives packed {key, pay}

@@ -215,6 +215,7 @@ struct hj_ctx {
     // the last radix probe's shape, for hj_ctx_join_kernel (the kernel itself
     // follows from these and the build-time sample in meta[2..3])
     bool join_ran = false, join_wide = false, join_stream = false;
+    bool exists_ran = false;   // the last probe was a radix semi- / anti-join (HJ_JOIN_KERNEL_EXISTS)
     bool routed = false;   // the current build came from hj_dev_build_routed_i64 (plan.skip owner bits)
     bool dup_checked = false;   // hj_ctx_build_has_duplicates ran its DETECT build for this build
     bool host_building = false;  // host_join's build is running (do_build keeps the memo's input copies)
@@ -551,7 +552,7 @@ int do_build(hj_ctx *c, int layout, const hj::SrcDev &src, hipStream_t st) {
     c->n_build = src.n;
     c->used = choose_strategy(c, src.n);
     c->probe_used = -1;
-    c->join_ran = false;
+    c->join_ran = c->exists_ran = false;
     c->dup_checked = false;
     c->routed = false;
     // (hj_count_*'s kept table is gone; a host join's own build keeps the
@@ -606,7 +607,7 @@ int do_probe(hj_ctx *c, int layout, const hj::SrcDev &src, void *out_r, void *ou
     // (the radix join zeroes the counter in its work-map kernel: no memset launch)
     const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
     c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
-    c->join_ran = false;
+    c->join_ran = c->exists_ran = false;
     if (radix) {
         const bool wide = layout == kWide;
         const size_t esz = wide ? 16 : 8;
@@ -641,6 +642,56 @@ int do_probe(hj_ctx *c, int layout, const hj::SrcDev &src, void *out_r, void *ou
     size_t slow_cap = hj::probe_tiles(src.n);
     HJ_TRY(ensure_buf(c->slow, slow_cap * sizeof(unsigned)));
     HJ_HIP(hj::launch_probe(table_dev(c), layout, src, out, count_only, (unsigned *)c->slow.p, slow_cap, st));
+    record(c, kEvProbe1, st);
+    c->evs().rec[2] = c->timing;
+    c->evs().rec_mid = false;
+    return HJ_OK;
+}
+
+// Semi- / anti-join probe (hj_dev_exists_*): do_probe's checks, strategy
+// choice, events and workspace; the table, R's partition, the side list and
+// the repeat flag meta[1] are only read (meta[1] not even that).
+int do_exists(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, void *out_key, void *out_s, int64_t cap,
+              uint64_t *d_count, hipStream_t st) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (kind != HJ_EXISTS_SEMI && kind != HJ_EXISTS_ANTI)
+        HJ_FAIL(HJ_ERR_ARG, "kind must be HJ_EXISTS_SEMI or HJ_EXISTS_ANTI");
+    if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, "probe without a matching build");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
+    if (cap < 0 || (cap > 0 && !out_s) || (cap == 0 && !out_s && out_key)) HJ_FAIL(HJ_ERR_ARG, "bad output");
+    HJ_TRY(set_device(c));
+    const bool anti = kind == HJ_EXISTS_ANTI;
+    const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
+    c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
+    c->join_ran = c->exists_ran = false;
+    if (radix) {
+        const bool wide = layout == kWide;
+        const size_t esz = wide ? 16 : 8;
+        HJ_TRY(ensure_radix_scratch(c, c->sset, src.n, esz, c->plan));
+        record(c, kEvProbe0, st);
+        HJ_RADIX(c, st, hj::radix_partition(src, wide, c->plan, radix_work(c), bucket_set(c->sset), st));
+        trace("exists: S partitioned", st, src.n);
+        record(c, kEvProbeMid, st);
+        // (the counter is zeroed by the work-map kernel, as for the inner join)
+        HJ_RADIX(c, st, hj::radix_exists(wide, anti, c->plan, radix_work(c), bucket_set(c->rset), bucket_set(c->sset),
+                                         c->sset.max_runs, (unsigned *)c->work_start.p, c->work_desc.p, out_key, out_s,
+                                         cap, (unsigned long long *)d_count, st));
+        c->exists_ran = true;
+        trace("exists: joined", st, cap);
+        record(c, kEvProbe1, st);
+        c->evs().rec[2] = c->timing;
+        c->evs().rec_mid = c->timing;
+        return HJ_OK;
+    }
+    HJ_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
+    hj::OutDev out;
+    out.r = out_key;
+    out.s = out_s;
+    out.cap = cap;
+    out.counter = (unsigned long long *)d_count;
+    record(c, kEvProbe0, st);
+    HJ_HIP(hj::launch_probe_exists(table_dev(c), layout, src, out, anti, st));
     record(c, kEvProbe1, st);
     c->evs().rec[2] = c->timing;
     c->evs().rec_mid = false;
@@ -1466,6 +1517,7 @@ int hj_ctx_build_has_duplicates(hj_ctx *c) {
 
 int hj_ctx_join_kernel(hj_ctx *c) {
     if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (c->exists_ran && c->layout >= 0) return HJ_JOIN_KERNEL_EXISTS;
     if (!c->join_ran || c->layout < 0) return 0;
     HJ_TRY(set_device(c));
     unsigned long long v[2] = {0, 0};
@@ -1606,6 +1658,24 @@ int hj_dev_probe_i32(hj_ctx *c, const int32_t *skey, int64_t n, int64_t row_base
                     (hipStream_t)stream);
 }
 
+int hj_dev_exists_i64(hj_ctx *c, int kind, const int64_t *skey, const int64_t *spay, int64_t n, int64_t *out_key,
+                      int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream) {
+    // (the count-only form reads no payload: any readable column stands in)
+    if (n > 0 && !spay && (out_cap != 0 || out_s)) HJ_FAIL(HJ_ERR_ARG, "null probe payload");
+    return do_exists(c, kWide, kind, src_cols64(skey, spay ? spay : skey, n), out_key, out_s, out_cap, d_count,
+                     (hipStream_t)stream);
+}
+int hj_dev_exists_tuples_i64(hj_ctx *c, int kind, const int64_t *tuples, int64_t n, int64_t *out_key, int64_t *out_s,
+                             int64_t out_cap, uint64_t *d_count, void *stream) {
+    return do_exists(c, kWide, kind, src_packed(tuples, n), out_key, out_s, out_cap, d_count, (hipStream_t)stream);
+}
+int hj_dev_exists_i32(hj_ctx *c, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t *out_key,
+                      int32_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream) {
+    if (row_base < 0 || row_base + n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids out of range");
+    return do_exists(c, kNarrow, kind, src_col32(skey, n, row_base), out_key, out_s, out_cap, d_count,
+                     (hipStream_t)stream);
+}
+
 int hj_dev_partition_i64(hj_ctx *c, const int64_t *key, const int64_t *pay, int64_t n, int nparts,
                          int64_t *out_tuples, uint64_t *d_counts, void *stream) {
     if (n > 0 && !pay) HJ_FAIL(HJ_ERR_ARG, "null payload");
@@ -1682,7 +1752,7 @@ int hj_dev_build_routed_i64(hj_ctx *c, const int64_t *tuples, int64_t n, const u
     c->used = HJ_STRATEGY_RADIX;
     c->dual = false;
     c->probe_used = -1;
-    c->join_ran = false;
+    c->join_ran = c->exists_ran = false;
     c->memo.invalidate();
     c->plan = pl;
     c->routed = true;

@@ -113,6 +113,11 @@ size_t probe_tiles(long long n);
 // callers size it from probe_tiles so that cannot happen)
 hipError_t launch_probe(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
                         bool count_only, unsigned *slow, size_t slow_cap, hipStream_t st);
+// semi- (anti: anti-) join probe of the global table: out.r = S keys (may be
+// null), out.s = S payloads, out.cap == 0 counts only; one launch, no
+// general path, meta[1] untouched
+hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, bool anti,
+                               hipStream_t st);
 
 // ---------------------------------------------------------------- radix join
 // (hj_radix.hip) partitions both relations by the top bits of the key hash
@@ -200,6 +205,15 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
                       unsigned long long s_runs, unsigned *work_start, void *desc, void *out_r, void *out_s, long long cap,
                       unsigned long long *counter, unsigned long long *dup_flag, bool count_only, hipStream_t st,
                       const unsigned long long *sample, bool stream, int nparts = -1);
+// Semi- (anti: anti-) join of the partitioned relations: the S rows with /
+// without a partner in r.  out_key (may be null) and out_s receive the S keys
+// and payloads (int64, or int32 for narrow rows), cap == 0 counts only.  The
+// work map lives in work_start / desc as radix_join's (no deferred lists);
+// for anti every non-empty S partition is an item, build rows or not.
+// Reads r, writes neither it nor the repeat flag.
+hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
+                        const BucketSet &s, unsigned long long s_runs, unsigned *work_start, void *desc, void *out_key,
+                        void *out_s, long long cap, unsigned long long *counter, hipStream_t st);
 // Folded routing's send side: rows (int64 columns or packed tuples) grouped
 // by the top rbits (<= 9) of radix_hash into out_tuples, exact and contiguous
 // per bin, bins in order; counts[2^rbits] their sizes.  One EXACT partition

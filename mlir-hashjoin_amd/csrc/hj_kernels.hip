@@ -487,6 +487,108 @@ __global__ __launch_bounds__(kBlock) void k_probe_slow(TableDev t, SrcDev src, O
     }
 }
 
+// ------------------------------------------------------------------ exists probe
+// Semi- / anti-join probe (EXISTS / NOT EXISTS): the S rows that have / have
+// no partner in the built table.  k_probe's shape -- 2048-row tiles, every
+// row's first slot load issued before any is resolved, the LDS copy of small
+// tables, ballot compaction in row-slot-major order after ONE cursor add per
+// tile -- without its general path: a row yields at most one output element
+// whatever the build side repeats, so a chain walk ends at the first equal
+// key or at EMPTY, meta[1] is never read and no tile is handed on.  A wide
+// INT64_MIN probe key matches iff the side list holds a row (meta[0]).
+// out.r: the S keys (optional, may be null), out.s: the S payloads; anti
+// inverts `found` before the ballots.  out.cap == 0 is the count-only form
+// (nothing is written; kind, count-only and out.r are wave-uniform runtime
+// branches: one instantiation per layout, form and table placement).
+template <int L, int FORM, bool LDS>
+__global__ __launch_bounds__(kBlock) void k_probe_exists(TableDev t, SrcDev src, OutDev out, unsigned anti) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    constexpr int NW = kBlock / 64;
+    __shared__ unsigned long long st_base;
+    __shared__ unsigned s_cw[kProbeItems * NW];
+    extern __shared__ ulonglong2 s_tab[];
+
+    const slot_t *sl = (const slot_t *)t.slots;
+    if constexpr (LDS) {
+        const unsigned long long n16 = (t.mask + 1) * sizeof(slot_t) / 16;
+        const ulonglong2 *g16 = (const ulonglong2 *)t.slots;
+        for (unsigned long long j = threadIdx.x; j < n16; j += kBlock) s_tab[j] = g16[j];
+        __syncthreads();
+    }
+    auto slot_at = [&](unsigned long long h) -> slot_t {
+        if constexpr (LDS) return ((const slot_t *)s_tab)[h];
+        else return sl[h];
+    };
+    const bool side_rows = L == kWide && t.meta[0] != 0ull;   // the build side holds an INT64_MIN key
+    const unsigned flip = anti ? (1u << kProbeItems) - 1u : 0u;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long K[kProbeItems], P[kProbeItems], H[kProbeItems];
+        unsigned valid = 0, walk = 0, found = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            Tuple tp{0ull, 0ull};
+            if (probe_row<L, FORM>(src, q, i, tp)) {
+                valid |= 1u << i;
+                if (LY::null_key(tp.k)) found |= side_rows ? 1u << i : 0u;
+                else walk |= 1u << i;
+            }
+            K[i] = tp.k;
+            P[i] = tp.p;
+        }
+        slot_t S[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            H[i] = slot_of(K[i], t.shift);
+            if ((walk >> i) & 1u) S[i] = slot_at(H[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((walk >> i) & 1u)) continue;
+            slot_t sv = S[i];
+            unsigned long long hh = H[i];
+            while (!LY::empty(sv) && LY::key(sv) != K[i]) {
+                hh = (hh + 1) & t.mask;
+                sv = slot_at(hh);
+            }
+            if (!LY::empty(sv)) found |= 1u << i;
+        }
+        found = (found ^ flip) & valid;
+        const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+        unsigned lpre[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const unsigned long long bal = __ballot((found >> i) & 1u);
+            lpre[i] = (unsigned)__popcll(bal & lt);
+            if (lane == 0) s_cw[i * NW + wv] = (unsigned)__popcll(bal);
+        }
+        __syncthreads();
+        if (wv == 0) {   // exclusive scan of the kProbeItems * NW runs (<= 64)
+            static_assert(kProbeItems * NW <= 64, "one lane per run");
+            const unsigned v = lane < kProbeItems * NW ? s_cw[lane] : 0u;
+            const unsigned x = wave_incl_add(v);
+            if (lane < kProbeItems * NW) s_cw[lane] = x - v;
+            if (lane == 63) st_base = x ? atomicAdd(out.counter, (unsigned long long)x) : 0ull;
+        }
+        __syncthreads();
+        out_t *okk = (out_t *)out.r;
+        out_t *oss = (out_t *)out.s;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((found >> i) & 1u)) continue;
+            const unsigned long long gi = st_base + s_cw[i * NW + wv] + lpre[i];
+            if (gi < (unsigned long long)out.cap) {
+                oss[gi] = (out_t)P[i];
+                if (okk) okk[gi] = (out_t)K[i];
+            }
+        }
+        __syncthreads();   // s_cw / st_base reused by the next tile
+    }
+}
+
 // ------------------------------------------------------------------ partition
 // Radix partition by a hash independent of the slot hash (fmix64 top word,
 // multiply-shift onto [0, P)), so a partition's keys still spread over its
@@ -1007,6 +1109,39 @@ hipError_t launch_probe(const TableDev &t, int layout, const SrcDev &src, const 
         else return hipErrorInvalidValue;
     }
 #undef HJ_PROBE
+    return hipGetLastError();
+}
+
+hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, bool anti,
+                               hipStream_t st) {
+    if (src.n <= 0) return hipSuccess;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const unsigned tiles = grid_for(src.n, kProbeTile);
+    // the grid of launch_probe: LDS-resident tables stride the tiles from as
+    // many workgroups as LDS lets a CU hold, else one workgroup per tile
+    const size_t tbytes = (size_t)(t.mask + 1) * (layout == kWide ? 16 : 8);
+    const bool lds = tbytes <= (size_t)kLdsTableBytes && tbytes >= 16;
+    unsigned per_cu = lds ? (unsigned)(kLdsPerCu / tbytes) : 1u;
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const unsigned gl = tiles < (unsigned)cus * per_cu ? tiles : (unsigned)cus * per_cu;
+    const unsigned g = lds ? gl : tiles;
+    const unsigned a = anti ? 1u : 0u;
+#define HJ_EXISTS(L, F)                                                                                          \
+    do {                                                                                                         \
+        if (lds) hipLaunchKernelGGL((k_probe_exists<L, F, true>), dim3(g), dim3(kBlock), tbytes, st, t, src, out, a); \
+        else hipLaunchKernelGGL((k_probe_exists<L, F, false>), dim3(g), dim3(kBlock), 0, st, t, src, out, a);     \
+    } while (0)
+    if (layout == kWide) {
+        if (src.form == kCols64) HJ_EXISTS(kWide, kCols64);
+        else if (src.form == kPacked64) HJ_EXISTS(kWide, kPacked64);
+        else return hipErrorInvalidValue;
+    } else {
+        if (src.form == kCol32) HJ_EXISTS(kNarrow, kCol32);
+        else return hipErrorInvalidValue;
+    }
+#undef HJ_EXISTS
     return hipGetLastError();
 }
 

@@ -3043,6 +3043,186 @@ __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
     }
 }
 
+// --------------------------------------------------------------- exists join
+// Semi- / anti-join over the work items (EXISTS / NOT EXISTS): each S row of
+// the item's chunk is emitted at most once, so the LDS table holds KEYS only
+// and each key once -- one 8-B slot format for both widths (wide: the key,
+// EMPTY = INT64_MIN, a per-table LDS flag says "the rows built hold an
+// INT64_MIN key"; narrow: the zero-extended 32-bit key, EMPTY = all ones).
+// An insert ends at EMPTY or at its own key, so a hot build key takes one
+// slot.  2^13 slots = 64 KiB, two workgroups per CU; a build round takes
+// RCAP = 5120 rows (80 runs; load <= 0.625 however the keys repeat).
+//
+// Items whose build side is one round (every planner-sized partition) build
+// once and probe their sub-chunks against that table.  Larger build sides
+// (forced small radix_bits, a hot key's partition: rounds are cut by rows)
+// run the sub-chunks OUTERMOST: a sub-chunk's rows stay in registers with
+// their matched bits while every round is built and probed, and are emitted
+// after the last round -- exactly once, matched in some round (semi) or in
+// none (anti).  That re-reads R once per sub-chunk; such items are the
+// exception.  An item without build rows (anti's map keeps them) builds
+// nothing: no row of it matches.
+// Emit: ballot compaction per sub-chunk as k_probe_exists, ONE add on the
+// output cursor per sub-chunk, contiguous per-wave runs.  out_r = S keys
+// (optional), out_s = S payloads; cap == 0 counts only.  kind, count-only
+// and the key output are wave-uniform runtime branches.
+constexpr int kExistsTableLog = 13;
+// 1024 threads x 5 build keys + 3 probe rows, 8 waves per SIMD: both
+// workgroups a CU's LDS admits are resident (<= 64 VGPRs)
+constexpr int kExistsNT = 1024, kExistsSI = 3, kExistsWPS = 8;
+template <bool WIDE, int NT, int SI, int WPS>
+__global__ __launch_bounds__(NT, WPS) void k_join_exists(JoinArgs a, unsigned anti) {
+    typedef Row<WIDE> R;
+    typedef typename R::T T;
+    typedef typename std::conditional<WIDE, u64, unsigned>::type PT;   // output element
+    constexpr int TS = 1 << kExistsTableLog;
+    constexpr unsigned kMask = TS - 1;
+    constexpr int RCAP = TS * 5 / 8;          // build rows per round
+    constexpr int RI = RCAP / NT;             // build rows per thread per round
+    constexpr int NW = NT / 64;
+    constexpr unsigned rb = (unsigned)RCAP >> kRunLog;         // runs per build round
+    constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;  // runs per sub-chunk
+    static_assert(RI * NT == RCAP, "a build round must load exactly RCAP rows");
+    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
+    static_assert(SI * NW <= 64, "one lane per (row slot, wave) run");
+    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    __shared__ u64 tkey[TS];
+    __shared__ unsigned s_cw[SI * NW];
+    __shared__ u64 s_base;
+    __shared__ unsigned s_null;
+
+    const unsigned total = a.work_start[a.P];
+    if (blockIdx.x >= total) return;
+    const T *rrows = (const T *)a.r;
+    const T *srows = (const T *)a.s;
+    PT *okk = (PT *)a.out_r;
+    PT *oss = (PT *)a.out_s;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
+    const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
+    const u64 lt = off ? (~0ull >> (64 - off)) : 0ull;
+    const unsigned flip = anti ? (1u << SI) - 1u : 0u;
+
+    for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
+        const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
+        const bool rounds = it.r_hi - it.r_lo > (u64)rb;   // more than one build round
+        bool built = false;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += subb) {
+            const u64 shi = sb + subb < it.s_hi ? sb + subb : it.s_hi;
+            T sv[SI];
+            unsigned sok = 0, found = 0;
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                const u64 li = sb + (u64)i * NW + wave;
+                const u64 e = li < shi ? sload(a.s_runs + li) : 0ull;
+                if (off < (unsigned)(e & 127u)) {
+                    sv[i] = ld_s<kNtJoinLd>(srows + (e >> 7) + off);
+                    sok |= 1u << i;
+                } else {
+                    sv[i] = R::zero();
+                }
+            }
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += rb) {
+                if (rounds || !built) {
+                    // ---- build rows of runs [r0, rhi): keys only, each key once
+                    const u64 rhi = r0 + rb < it.r_hi ? r0 + rb : it.r_hi;
+                    u64 bk[RI];
+                    unsigned rok = 0;
+#pragma unroll
+                    for (int i = 0; i < RI; ++i) {
+                        const u64 li = r0 + (u64)i * NW + wave;
+                        const u64 e = li < rhi ? sload(a.r_runs + li) : 0ull;
+                        bk[i] = 0ull;
+                        if (off < (unsigned)(e & 127u)) {
+                            const T *p = rrows + (e >> 7) + off;
+                            if constexpr (WIDE) bk[i] = *(const u64 *)p;   // (the key word of the 16-B row)
+                            else bk[i] = *p >> 32;
+                            rok |= 1u << i;
+                        }
+                    }
+                    __syncthreads();   // the previous table's probes are done
+                    for (int j = threadIdx.x; j < TS / 2; j += NT)
+                        ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+                    if (threadIdx.x == 0) s_null = 0u;
+                    __syncthreads();
+                    bool nul = false;
+#pragma unroll
+                    for (int i = 0; i < RI; ++i) {
+                        if (!((rok >> i) & 1u)) continue;
+                        const u64 key = bk[i];
+                        if (WIDE && key == kEmptyKey64) {
+                            nul = true;
+                            continue;
+                        }
+                        unsigned h = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                        while (true) {   // ends at EMPTY (claimed) or at the key itself
+                            const u64 old = atomicCAS(&tkey[h], kEmpty, key);
+                            if (old == kEmpty || old == key) break;
+                            h = (h + 1) & kMask;
+                        }
+                    }
+                    if (nul) s_null = 1u;
+                    __syncthreads();
+                    built = true;
+                }
+                // ---- probe the rows still unmatched: first slots read before any is resolved
+                unsigned hp[SI];
+                u64 e0[SI];
+                unsigned open = sok & ~found;
+                const bool nullr = s_null != 0u;
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    const u64 key = R::key(sv[i]);
+                    if (WIDE && key == kEmptyKey64) {
+                        if (((open >> i) & 1u) && nullr) found |= 1u << i;
+                        open &= ~(1u << i);
+                    }
+                    hp[i] = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                    e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
+                }
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    if (!((open >> i) & 1u)) continue;
+                    const u64 key = R::key(sv[i]);
+                    unsigned h = hp[i];
+                    u64 e = e0[i];
+                    while (e != kEmpty && e != key) {
+                        h = (h + 1) & kMask;
+                        e = tkey[h];
+                    }
+                    if (e == key) found |= 1u << i;
+                }
+            }
+            // ---- emit this sub-chunk's rows
+            found = (found ^ flip) & sok;
+            unsigned lpre[SI];
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                const u64 bal = __ballot((found >> i) & 1u);
+                lpre[i] = (unsigned)__popcll(bal & lt);
+                if (off == 0) s_cw[i * NW + wave] = (unsigned)__popcll(bal);
+            }
+            __syncthreads();
+            if (wave == 0) {   // exclusive scan of the SI * NW runs
+                const unsigned v = off < (unsigned)(SI * NW) ? s_cw[off] : 0u;
+                const unsigned x = wave_incl_add(v);
+                if (off < (unsigned)(SI * NW)) s_cw[off] = x - v;
+                if (off == 63) s_base = x ? atomicAdd(a.counter, (u64)x) : 0ull;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                if (!((found >> i) & 1u)) continue;
+                const u64 gi = s_base + s_cw[i * NW + wave] + lpre[i];
+                if (gi < (u64)a.cap) {
+                    st_s<kNtJoinSt>(oss + gi, (PT)R::pay(sv[i]));
+                    if (okk) st_s<kNtJoinSt>(okk + gi, (PT)R::key(sv[i]));
+                }
+            }
+            __syncthreads();   // s_cw / s_base reused by the next sub-chunk
+        }
+    }
+}
+
 // --------------------------------------------------------------- join shapes
 // One product kernel per (row width, shape), chosen from facts known when
 // the join is launched -- never from an earlier join's statistics:
@@ -3691,6 +3871,43 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
     if (wide) HJ_JOIN(k_join, grid, 512, rest, true, kTableLog, 512, 0, true);
     else HJ_JOIN(k_join, grid, 512, rest, false, kTableLog, 512, 0, true);
 #undef HJ_JOIN
+    return hipGetLastError();
+}
+
+hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
+                        const BucketSet &s, unsigned long long s_runs, unsigned *work_start, void *desc, void *out_key,
+                        void *out_s, long long cap, unsigned long long *counter, hipStream_t st) {
+    const int P = 1 << pl.total_bits;
+    unsigned *work_owner = work_start + P + 1;
+    if (pl.pbl[pl.passes - 1] != kFinalPbl) return hipErrorInvalidValue;
+    const unsigned pg = (unsigned)(2 * cu_count());   // two 64-KiB tables per CU
+    // S runs per work item as radix_join sizes them; never below the item
+    // radix_join_items counts with, so the map fits the same buffers
+    constexpr unsigned subb = (unsigned)((kExistsNT * kExistsSI) >> kRunLog);
+    static_assert(kExistsNT * kExistsSI >= kFastNT * kFastSI || kExistsNT * kExistsSI >= kNarrowNT * kNarrowSI,
+                  "an exists item must be at least radix_join_items' item");
+    u64 chb = (u64)kJoinSub * subb;
+    const u64 want = (u64)s_runs / (16ull * pg);
+    if (want > chb) chb = (want + subb - 1) / subb * subb;
+    // semi: partitions without build rows have nothing to emit (zero chunks);
+    // anti: those S rows are exactly the ones to emit, so every non-empty S
+    // partition is live.  Either way items <= s_runs / chb + P: one partial
+    // chunk per partition at most, which is what radix_join_items bounds.
+    chunk_map_one(s.rstart, anti ? nullptr : r.rstart, P, (unsigned)chb, work_start, work_owner, ws, st, false);
+    const unsigned items = (unsigned)((u64)s_runs / chb + (u64)P + 1);
+    hipLaunchKernelGGL(k_item_desc, dim3(blocks_for(items, 256)), dim3(256), 0, st, (const unsigned *)work_start,
+                       (const unsigned *)work_owner, (const u64 *)s.rstart, (const u64 *)r.rstart, P, (unsigned)chb,
+                       (ItemDesc *)desc, nullptr, nullptr, nullptr, nullptr, counter);
+    JoinArgs a = join_args(wide, pl, r, s, P, work_start, desc, out_key, out_s, cap, counter, nullptr, nullptr);
+    a.tshift = 64 - pl.skip - pl.total_bits - kExistsTableLog;
+    const unsigned grid = items < pg ? items : pg;
+    const unsigned kind = anti ? 1u : 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_join_exists<true, kExistsNT, kExistsSI, kExistsWPS>), dim3(grid), dim3(kExistsNT), 0, st,
+                           a, kind);
+    else
+        hipLaunchKernelGGL((k_join_exists<false, kExistsNT, kExistsSI, kExistsWPS>), dim3(grid), dim3(kExistsNT), 0, st,
+                           a, kind);
     return hipGetLastError();
 }
 

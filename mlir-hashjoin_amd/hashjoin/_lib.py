@@ -24,6 +24,10 @@ HJ_STRATEGY_AUTO = 0
 HJ_STRATEGY_GLOBAL = 1
 HJ_STRATEGY_RADIX = 2
 
+HJ_EXISTS_SEMI = 0
+HJ_EXISTS_ANTI = 1
+HJ_JOIN_KERNEL_EXISTS = 6
+
 _vp = C.c_void_p
 _i64 = C.c_int64
 _u64 = C.c_uint64
@@ -76,6 +80,9 @@ def _load():
         "hj_dev_build_i32": (_int, [_vp, _vp, _i64, _i64, _vp]),
         "hj_dev_count_i32": (_int, [_vp, _vp, _i64, _vp, _vp]),
         "hj_dev_probe_i32": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_exists_i64": (_int, [_vp, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_exists_tuples_i64": (_int, [_vp, _int, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_exists_i32": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_partition_i64": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_dev_partition_tuples_i64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_partition_of": (_int, [_i64, _int]),

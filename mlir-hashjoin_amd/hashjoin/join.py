@@ -21,9 +21,11 @@ import os
 
 import torch
 
-from ._lib import HJ_STRATEGY_AUTO, HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, check, lib
+from ._lib import (HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_STRATEGY_AUTO, HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, check,
+                   lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
+EXISTS_KINDS = {"semi": HJ_EXISTS_SEMI, "anti": HJ_EXISTS_ANTI}
 
 
 def _ptr(t):
@@ -114,12 +116,14 @@ class HashJoin:
             check(r, "hj_ctx_build_has_duplicates")
         return bool(r)
 
-    JOIN_KERNELS = {1: "k_join_b", 2: "k_join_u", 3: "k_join_u_stream", 4: "k_join_grp", 5: "k_join"}
+    JOIN_KERNELS = {1: "k_join_b", 2: "k_join_u", 3: "k_join_u_stream", 4: "k_join_grp", 5: "k_join",
+                    6: "k_join_exists"}
 
     @property
     def join_kernel(self):
         """Kernel of the last radix join (hj_ctx_join_kernel): 'k_join_b',
-        'k_join_u_stream', 'k_join_grp', 'k_join', or None (no radix join)."""
+        'k_join_u_stream', 'k_join_grp', 'k_join', 'k_join_exists' (a radix
+        semi- / anti-join), or None (no radix join)."""
         r = lib.hj_ctx_join_kernel(self._ctx)
         if r < 0:
             check(r, "hj_ctx_join_kernel")
@@ -214,6 +218,89 @@ class HashJoin:
                                           out_r.numel(), _ptr(count), _stream(self.device, stream)),
               "hj_dev_probe_tuples_i64")
         return count
+
+    # ---- semi- / anti-join probes (hj.h "Semi- and anti-join probes")
+    def probe_exists(self, skey, spay=None, kind="semi", out_s=None, out_key=None, count=None, row_base=0,
+                     stream=None):
+        """EXISTS ('semi') / NOT EXISTS ('anti') probe of the built table: the S
+        rows with / without a partner, each at most once.  Writes min(M, cap)
+        S payloads (i32: row ids row_base + row) into out_s and, if given,
+        their keys into out_key; `count` (int64 device tensor) receives M.
+        out_s None is the count-only form.  Returns count."""
+        _need_cuda(skey, spay, out_s, out_key)
+        st = _stream(self.device, stream)
+        count = self._count if count is None else count
+        k = EXISTS_KINDS[kind]
+        cap = 0 if out_s is None else out_s.numel()
+        if out_key is not None and (out_s is None or out_key.numel() != cap):
+            raise ValueError("out_key needs an out_s of the same length")
+        for o in (out_s, out_key):
+            if o is not None and o.dtype != skey.dtype:
+                raise ValueError("exists outputs carry the probe key's dtype")
+        if skey.dtype == torch.int64:
+            if spay is None and out_s is not None:
+                raise ValueError("int64 probe needs an int64 payload column")
+            if spay is not None and (spay.dtype != torch.int64 or spay.numel() != skey.numel()):
+                raise ValueError("int64 probe needs an int64 payload column of the same length")
+            check(lib.hj_dev_exists_i64(self._ctx, k, _ptr(skey), _ptr(spay), skey.numel(), _ptr(out_key), _ptr(out_s),
+                                        cap, _ptr(count), st), "hj_dev_exists_i64")
+        elif skey.dtype == torch.int32:
+            if spay is not None:
+                raise ValueError("i32 joins carry row ids, not payloads (reference types)")
+            check(lib.hj_dev_exists_i32(self._ctx, k, _ptr(skey), skey.numel(), int(row_base), _ptr(out_key),
+                                        _ptr(out_s), cap, _ptr(count), st), "hj_dev_exists_i32")
+        else:
+            raise TypeError("keys must be int32 or int64")
+        return count
+
+    def probe_exists_tuples(self, tuples, kind, out_s, out_key=None, count=None, stream=None):
+        """probe_exists over packed (n, 2) int64 {key, payload} rows."""
+        _need_cuda(tuples, out_s, out_key)
+        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
+            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        count = self._count if count is None else count
+        cap = 0 if out_s is None else out_s.numel()
+        if out_key is not None and (out_s is None or out_key.numel() != cap):
+            raise ValueError("out_key needs an out_s of the same length")
+        check(lib.hj_dev_exists_tuples_i64(self._ctx, EXISTS_KINDS[kind], _ptr(tuples), tuples.shape[0], _ptr(out_key),
+                                           _ptr(out_s), cap, _ptr(count), _stream(self.device, stream)),
+              "hj_dev_exists_tuples_i64")
+        return count
+
+    def count_exists(self, skey, kind="semi", stream=None, sync=True):
+        """How many S rows have ('semi') / have no ('anti') partner."""
+        cnt = self.probe_exists(skey, kind=kind, stream=stream)
+        return int(cnt.item()) if sync else cnt
+
+    def _exists_join(self, kind, rkey, skey, spay, rpay, with_keys, capacity, stream):
+        self.probe_hint(skey.numel())
+        try:
+            if rkey.dtype == torch.int64 and rpay is None:
+                rpay = torch.zeros_like(rkey)   # (the build ABI wants a column; exists probes never read it)
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+        cap = max(1, skey.numel() if capacity is None else int(capacity))
+        for _ in range(2):
+            out_s = torch.empty(cap, dtype=skey.dtype, device=self.device)
+            out_key = torch.empty(cap, dtype=skey.dtype, device=self.device) if with_keys else None
+            m = int(self.probe_exists(skey, spay, kind, out_s, out_key, stream=stream).item())
+            if m < 0:   # bit 63 (hj.h)
+                raise RuntimeError("hash join: internal work list overflow (count flagged)")
+            if m <= cap:
+                return (out_key[:m], out_s[:m]) if with_keys else out_s[:m]
+            cap = m
+        raise RuntimeError("exists output did not fit after resizing")
+
+    def semi_join(self, rkey, skey, spay=None, rpay=None, with_keys=False, capacity=None, stream=None):
+        """Build R, then the S payloads (row ids for int32 keys) of the rows
+        whose key R holds -- (keys, payloads) if with_keys.  The output is
+        sized |S| rows, or `capacity` with one re-probe at the exact M."""
+        return self._exists_join("semi", rkey, skey, spay, rpay, with_keys, capacity, stream)
+
+    def anti_join(self, rkey, skey, spay=None, rpay=None, with_keys=False, capacity=None, stream=None):
+        """As semi_join, for the S rows whose key R does not hold."""
+        return self._exists_join("anti", rkey, skey, spay, rpay, with_keys, capacity, stream)
 
     # ---- folded routing (hj.h "Folded routing"): the owner and the
     # receiver's first radix-pass bin from one hash, so receivers skip a pass
