@@ -240,10 +240,18 @@ int hj_route_plan(int64_t n_build_global, int nranks, int *sub_bits);
  * a key histogram. */
 int hj_dev_route_i64(hj_ctx *ctx, const int64_t *key, const int64_t *pay, int64_t n, int nranks, int sub_bits,
                      int64_t *out_tuples, uint64_t *d_counts, void *stream);
-/* Build from routed tuples: nsrc sources' rows one after another, each
- * source's grouped by bin 0 .. 2^sub_bits - 1; d_counts (device, nsrc x
+/* Build from routed tuples: nsrc (1..64) sources' rows one after another,
+ * each source's grouped by bin 0 .. 2^sub_bits - 1; d_counts (device, nsrc x
  * 2^sub_bits uint64, row s = source s's bin sizes).  nranks, sub_bits as
- * routed. */
+ * routed (nranks << sub_bits <= 512, else HJ_ERR_ARG).  Any counts are
+ * joined exactly, empty sources and (source, bin) pairs of a few rows
+ * included: the workspace is sized for rows / 64 + nsrc * 2^sub_bits listed
+ * runs.
+ * The build is an ordinary radix build of this owner's rows: besides
+ * hj_dev_probe_routed_i64, hj_dev_probe_i64 / _tuples_i64, hj_dev_count_i64
+ * and hj_dev_exists_i64 / _tuples_i64 over unrouted rows are valid after it
+ * and return the join with the built rows (they run both local passes on
+ * their probe side). */
 int hj_dev_build_routed_i64(hj_ctx *ctx, const int64_t *tuples, int64_t n, const uint64_t *d_counts, int nsrc,
                             int nranks, int sub_bits, void *stream);
 /* Probe routed tuples of bins [bin0, bin0 + nbins) only (the part of the probe

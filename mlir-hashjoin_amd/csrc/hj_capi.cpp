@@ -488,11 +488,12 @@ hj::BucketSet bucket_set(SetBufs &sb) {
 }
 
 // Partition scratch for n rows under plan pl (shared by R and S), plus the
-// relation's own final set.
-int ensure_radix_scratch(hj_ctx *c, SetBufs &fin, int64_t n, size_t esz, const hj::RadixPlan &pl) {
+// relation's own final set.  routed_src > 0: the rows come routed from that
+// many sources (the run lists then hold an entry per (source, bin) at least).
+int ensure_radix_scratch(hj_ctx *c, SetBufs &fin, int64_t n, size_t esz, const hj::RadixPlan &pl, int routed_src = 0) {
     const size_t P = size_t(1) << pl.total_bits;
-    HJ_TRY(ensure_set(fin, hj::radix_need(n, pl, true), esz, P, hj::kFinalPbl));
-    if (pl.passes > 1) HJ_TRY(ensure_set(c->tset, hj::radix_need(n, pl, false), esz, P, hj::kPassPbl));
+    HJ_TRY(ensure_set(fin, hj::radix_need(n, pl, true, routed_src), esz, P, hj::kFinalPbl));
+    if (pl.passes > 1) HJ_TRY(ensure_set(c->tset, hj::radix_need(n, pl, false, routed_src), esz, P, hj::kPassPbl));
     HJ_TRY(ensure_buf(c->nb, 16));
     HJ_TRY(ensure_buf(c->pcur, (P + 1) * 8));
     HJ_TRY(ensure_buf(c->rcur, (P + 1) * 8));
@@ -1728,6 +1729,8 @@ int hj_dev_build_routed_i64(hj_ctx *c, const int64_t *tuples, int64_t n, const u
     if (nsrc < 1 || nsrc > hj::kMaxRouteSources || nranks < 1 || (nranks & (nranks - 1)) || sub_bits < 1 ||
         sub_bits > 9)
         HJ_FAIL(HJ_ERR_ARG, "bad routed layout");
+    // (what hj_dev_route_i64 can have produced: owner and bin bits from 9 hash bits)
+    if (ceil_log2((unsigned long long)nranks) + sub_bits > 9) HJ_FAIL(HJ_ERR_ARG, "nranks << sub_bits must be <= 512");
     hipStream_t st = (hipStream_t)stream;
     HJ_TRY(set_device(c));
     HJ_TRY(ensure_meta(c, 64));
@@ -1757,7 +1760,7 @@ int hj_dev_build_routed_i64(hj_ctx *c, const int64_t *tuples, int64_t n, const u
     c->plan = pl;
     c->routed = true;
     c->dup_checked = false;
-    HJ_TRY(ensure_radix_scratch(c, c->rset, n, 16, pl));
+    HJ_TRY(ensure_radix_scratch(c, c->rset, n, 16, pl, nsrc));
     record(c, kEvInit0, st);
     HJ_HIP(hipMemsetAsync(c->meta, 0, 4 * sizeof(unsigned long long), st));
     record(c, kEvInit1, st);
@@ -1784,7 +1787,7 @@ int hj_dev_probe_routed_i64(hj_ctx *c, const int64_t *tuples, int64_t n, const u
     hipStream_t st = (hipStream_t)stream;
     HJ_TRY(set_device(c));
     c->probe_used = HJ_STRATEGY_RADIX;   // (radix_join zeroes d_count)
-    HJ_TRY(ensure_radix_scratch(c, c->sset, n, 16, c->plan));
+    HJ_TRY(ensure_radix_scratch(c, c->sset, n, 16, c->plan, nsrc));
     record(c, kEvProbe0, st);
     HJ_RADIX(c, st, hj::radix_partition_routed(tuples, n, (const unsigned long long *)d_counts, nsrc, nbins, c->plan,
                                       radix_work(c), bucket_set(c->sset), st));

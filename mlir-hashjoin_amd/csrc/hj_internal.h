@@ -184,7 +184,9 @@ struct RadixNeed {                 // sizes of one bucket set
 // force_bits > 0: fixed 2^bits partitions; wide: int64 rows (else i32 rows, twice the rows per partition)
 RadixPlan radix_plan(long long n_build, int force_bits = 0, bool wide = true);
 // Bucket capacity of the final set (`final_set`) or the ping set of plan pl for n rows.
-RadixNeed radix_need(long long n, const RadixPlan &pl, bool final_set);
+// routed_src > 0: the rows arrive routed from that many sources
+// (radix_partition_routed), one run list entry per (source, bin) at least.
+RadixNeed radix_need(long long n, const RadixPlan &pl, bool final_set, int routed_src = 0);
 unsigned long long radix_tiles(long long n, int max_nseg);
 unsigned long long radix_join_items(const RadixPlan &pl, unsigned long long s_runs);
 // words of radix_join's work_start buffer: work map (P + 1 + items), then two

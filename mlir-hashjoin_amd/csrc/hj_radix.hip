@@ -3383,7 +3383,13 @@ RadixPlan radix_plan(long long n_build, int force_bits, bool wide) {
 // set.  It allocates at most n / PB full buckets plus one open bucket per
 // (workgroup segment run, bin): runs <= G + nseg_in; and a bucket is only
 // allocated to take rows.
-RadixNeed radix_need(long long n, const RadixPlan &pl, bool final_set) {
+// routed_src > 0: the first pass ran on routed_src other GPUs (folded
+// routing) and k_routed_list lists its output in the ping set's run arrays:
+// every (source, bin) pair is a "bucket" of its own there, ceil(c / 64) runs
+// each, so the listing and the second pass's tiles are sized for rows / 64 +
+// routed_src * F runs (the ping set's row buffer is not used and keeps the
+// plain pass's size).
+RadixNeed radix_need(long long n, const RadixPlan &pl, bool final_set, int routed_src) {
     RadixNeed need{1, 1};
     const u64 rows = n > 0 ? (u64)n : 1;
     u64 nseg = 1, prev_b = 0;
@@ -3397,9 +3403,11 @@ RadixNeed radix_need(long long n, const RadixPlan &pl, bool final_set) {
         const u64 tr = pass_tile_rows(pl.bits[i]), rpt = tr >> kRunLog;
         const u64 tiles = i == 0 ? (rows + tr - 1) / tr : (rows / 64 + prev_b) / rpt + nseg + 1;
         const u64 b = (tiles * tr >> pl.pbl[i]) + G + (nseg + G) * F + G + 1;
-        prev_b = b;
+        // what the next pass reads as buckets_in, and the entries the set's run list is sized by
+        const u64 listed = i == 0 && routed_src > 0 && (u64)routed_src * F > b ? (u64)routed_src * F : b;
+        prev_b = listed;
         if (to_final == final_set) {
-            if (b > need.buckets) need.buckets = b;
+            if (listed > need.buckets) need.buckets = listed;
             if ((b << pl.pbl[i]) > need.rows) need.rows = b << pl.pbl[i];
         }
         nseg *= F;
@@ -3726,7 +3734,10 @@ hipError_t radix_partition_routed(const void *tuples, long long n, const unsigne
                                   const RadixPlan &pl, const RadixWork &ws, const BucketSet &out, hipStream_t st) {
     if (pl.passes != 2 || nsrc < 1 || nsrc > kMaxRouteSources || nseg < 1) return hipErrorInvalidValue;
     // the routed listing borrows the ping set's run arrays (a 2-pass plan's
-    // second pass writes `out`, not ws.tmp)
+    // second pass writes `out`, not ws.tmp): ceil(c / 64) runs per (source,
+    // segment), which radix_need(.., routed_src = nsrc) sized them for -- a
+    // list too short is an error here, never runs dropped by the kernel's clamp
+    if (ws.tmp.max_runs < ((u64)(n > 0 ? n : 0) >> kRunLog) + (u64)nsrc * (u64)nseg) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_routed_list, dim3(nseg), dim3(256), 0, st, (const u64 *)cnt, nsrc, nseg, ws.tmp.runs,
                        ws.tmp.rstart, (u64)ws.tmp.max_runs);
     BucketSet in = ws.tmp;

@@ -69,10 +69,14 @@ def _owner_join(hj, rk, rp, sk, sp, P):
     return outs
 
 
-def _owner_join_folded(hj, rk, rp, sk, sp, P, sub, s_parts=1):
+def _owner_join_folded(hj, rk, rp, sk, sp, P, sub, s_parts=1, check=False):
     """The folded routing (hj_dev_route_i64): owner and first-pass bin from
     the radix hash; each owner's slices joined with the routed build / probe
-    (one local pass), its S in s_parts bin ranges: lists of (o_r, o_s)."""
+    (one local pass), its S in s_parts bin ranges: lists of (o_r, o_s).
+    check: every slice handed to the join holds only its owner's keys, bin by
+    bin as the counts say (routed_layout.check_layout, the numpy restatement
+    of the routing hash)."""
+    from routed_layout import check_layout
     F = 1 << sub
     tr, cr = hj.route(rk, rp, P, sub)
     ts, cs = hj.route(sk, sp, P, sub)
@@ -81,11 +85,16 @@ def _owner_join_folded(hj, rk, rp, sk, sp, P, sub, s_parts=1):
     offs = np.concatenate([[0], np.cumsum(csh)])
     outs = []
     for q in range(P):
+        if check:
+            check_layout(tr[offr[q * F]:offr[(q + 1) * F]].cpu().numpy(), crh[q * F:(q + 1) * F].reshape(1, F), 0, P,
+                         sub, q)
         hj.build_routed(tr[offr[q * F]:offr[(q + 1) * F]], cr[q * F:(q + 1) * F].view(1, F), P, sub)
         rs, ss = [], []
         for k in range(s_parts):
             b0, b1 = q * F + F * k // s_parts, q * F + F * (k + 1) // s_parts
             sq = ts[offs[b0]:offs[b1]]
+            if check:
+                check_layout(sq.cpu().numpy(), csh[b0:b1].reshape(1, b1 - b0), b0 - q * F, P, sub, q)
             cap = max(1, sq.shape[0])
             for _ in range(2):
                 o_r = torch.empty(cap, dtype=torch.int64, device="cuda"); o_s = torch.empty_like(o_r)
@@ -109,7 +118,7 @@ def test_owner_slices_folded_vs_oracle(hj, oracle, P, sub, s_parts, kind):
         rk, rp = oracle.gen_uniform_i64(80 + P + sub, 1, 1, 900, 20000)
         sk, sp = oracle.gen_uniform_i64(80 + P + sub, 2, 1, 900, 25000)
     d = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
-    outs = _owner_join_folded(hj, d(rk), d(rp), d(sk), d(sp), P, sub, s_parts)
+    outs = _owner_join_folded(hj, d(rk), d(rp), d(sk), d(sp), P, sub, s_parts, check=True)
     got_r = np.concatenate([o[0].cpu().numpy() for o in outs])
     got_s = np.concatenate([o[1].cpu().numpy() for o in outs])
     assert oracle.same_multiset(got_r, got_s, *oracle.nested_loop_i64(rk, rp, sk, sp))
