@@ -130,7 +130,9 @@ int hj_ctx_last_timing_ex(hj_ctx *ctx, float ms[8]);
  * starts the totals again; HJ_ERR_STATE unless accumulating. */
 int hj_ctx_timing_accumulate(hj_ctx *ctx, int enable);
 int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
-/* RADIX: the join kernel of the last probe.  A pure function of the row
+/* RADIX: the join kernel of the last probe, whichever entry point ran it
+ * (hj_dev_probe_*, hj_dev_count_*, hj_dev_exists_*, and after a routed build
+ * hj_dev_probe_routed_i64 too).  A pure function of the row
  * width, the probe / build size ratio (>= 8: the probe-heavy shape) and the
  * build side's repeated keys, sampled at build time over up to 64 partitions
  * -- never of an earlier join's statistics: HJ_JOIN_KERNEL_BUCKETED

@@ -490,8 +490,8 @@ hj::BucketSet bucket_set(SetBufs &sb) {
 // Partition scratch for n rows under plan pl (shared by R and S), plus the
 // relation's own final set.  routed_src > 0: the rows come routed from that
 // many sources (the run lists then hold an entry per (source, bin) at least).
-int ensure_radix_scratch(hj_ctx *c, SetBufs &fin, int64_t n, size_t esz, const hj::RadixPlan &pl, int routed_src = 0) {
-    const size_t P = size_t(1) << pl.total_bits;
+int ensure_radix_scratch(hj_ctx *c, SetBufs &fin, int64_t n, bool wide, const hj::RadixPlan &pl, int routed_src = 0) {
+    const size_t P = size_t(1) << pl.total_bits, esz = wide ? 16 : 8;   // (packed partitioned rows)
     HJ_TRY(ensure_set(fin, hj::radix_need(n, pl, true, routed_src), esz, P, hj::kFinalPbl));
     if (pl.passes > 1) HJ_TRY(ensure_set(c->tset, hj::radix_need(n, pl, false, routed_src), esz, P, hj::kPassPbl));
     HJ_TRY(ensure_buf(c->nb, 16));
@@ -531,6 +531,8 @@ hj::RadixWork radix_work(hj_ctx *c) {
     w.scan_sums = (unsigned long long *)c->scan_sums.p;
     w.scan_state = (unsigned long long *)c->scan_state.p;
     w.raw_cnt = (unsigned long long *)c->raw_cnt.p;
+    w.work_start = (unsigned *)c->work_start.p;
+    w.work_desc = c->work_desc.p;
     return w;
 }
 
@@ -541,59 +543,157 @@ int choose_strategy(const hj_ctx *c, int64_t n_build) {
     return HJ_STRATEGY_GLOBAL;
 }
 
+// One relation as the radix passes take it: plain, or (counts set) packed
+// tuples that arrive routed, split by source and first-pass bin.
+struct RadixSrc {
+    hj::SrcDev src;
+    const uint64_t *counts = nullptr;   // routed: [nsrc][nbins] rows
+    int nsrc = 0, nbins = 0;
+};
+
+int radix_partition_src(hj_ctx *c, const RadixSrc &in, SetBufs &fin, hipStream_t st) {
+    if (in.counts)
+        HJ_RADIX(c, st, hj::radix_partition_routed(in.src.key, in.src.n, (const unsigned long long *)in.counts, in.nsrc,
+                                                   in.nbins, c->plan, radix_work(c), bucket_set(fin), st));
+    else
+        HJ_RADIX(c, st, hj::radix_partition(in.src, c->layout == kWide, c->plan, radix_work(c), bucket_set(fin), st));
+    return HJ_OK;
+}
+
+// A build starts on the context: a new timing step, and what the last build and its probes left is reset.
+int begin_build(hj_ctx *c, int layout, int64_t n, int used, bool dual, bool routed, const hj::RadixPlan &plan) {
+    HJ_TRY(set_device(c));
+    HJ_TRY(ensure_meta(c, 64));
+    HJ_TRY(timing_advance(c));
+    c->layout = layout;
+    c->n_build = n;
+    c->used = used;
+    c->dual = dual;
+    c->routed = routed;
+    c->plan = plan;
+    c->probe_used = -1;
+    c->join_ran = c->exists_ran = c->dup_checked = false;
+    // (hj_count_*'s kept table is gone; a host join's own build keeps the
+    // EXACT copies it has just taken of its inputs)
+    if (c->host_building) c->memo.valid = false;
+    else c->memo.invalidate();
+    return HJ_OK;
+}
+
+// The radix build under c->plan: R partitioned by the top key-hash bits
+// (tables are built per partition in LDS at probe time) and sampled.  The
+// build phase ends here unless a global table follows (dual).
+int radix_build(hj_ctx *c, const RadixSrc &in, hipStream_t st) {
+    const bool wide = c->layout == kWide;
+    HJ_TRY(ensure_radix_scratch(c, c->rset, in.src.n, wide, c->plan, in.nsrc));
+    record(c, kEvInit0, st);
+    // meta[0] side count, [1] dup flag, [2..3] the build-side sample
+    HJ_HIP(hipMemsetAsync(c->meta, 0, 4 * sizeof(unsigned long long), st));
+    record(c, kEvInit1, st);
+    trace("build: workspace", st, in.src.n);
+    HJ_TRY(radix_partition_src(c, in, c->rset, st));
+    // repeated build keys, sampled: decides the join kernel (radix_join)
+    HJ_HIP(hj::radix_sample(wide, c->plan, bucket_set(c->rset), c->meta + 2, st));
+    trace("build: R partitioned", st, (long long)c->plan.total_bits);
+    if (!c->dual) {
+        record(c, kEvBuild1, st);
+        c->evs().rec[0] = c->evs().rec[1] = c->timing;
+    }
+    return HJ_OK;
+}
+
 int do_build(hj_ctx *c, int layout, const hj::SrcDev &src, hipStream_t st) {
     if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
     if (src.n < 0 || (src.n > 0 && !src.key) || (src.form == hj::kCols64 && src.n > 0 && !src.pay))
         HJ_FAIL(HJ_ERR_ARG, "bad build relation");
     if (layout == kNarrow && src.n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids: build side must have < 2^31 rows");
-    HJ_TRY(set_device(c));
-    HJ_TRY(ensure_meta(c, 64));
-    HJ_TRY(timing_advance(c));
-    c->layout = layout;
-    c->n_build = src.n;
-    c->used = choose_strategy(c, src.n);
-    c->probe_used = -1;
-    c->join_ran = c->exists_ran = false;
-    c->dup_checked = false;
-    c->routed = false;
-    // (hj_count_*'s kept table is gone; a host join's own build keeps the
-    // EXACT copies it has just taken of its inputs)
-    if (c->host_building) c->memo.valid = false;
-    else c->memo.invalidate();
+    const int used = choose_strategy(c, src.n);
     // (a known probe side settled the strategy in choose_strategy: no dual)
-    c->dual = c->used == HJ_STRATEGY_GLOBAL && c->strategy == HJ_STRATEGY_AUTO && src.n >= kDualMinBuildRows &&
-              c->probe_hint < 0;
-    if (c->used == HJ_STRATEGY_RADIX || c->dual) {
-        // build = radix-partition R by the top key-hash bits (tables are built
-        // per partition in LDS at probe time)
-        const bool wide = layout == kWide;
-        const size_t esz = wide ? 16 : 8;   // packed partitioned rows
-        c->plan = hj::radix_plan(src.n, c->radix_bits, wide);
-        HJ_TRY(ensure_radix_scratch(c, c->rset, src.n, esz, c->plan));
-        record(c, kEvInit0, st);
-        // meta[0] side count, [1] dup flag, [2..3] the build-side sample
-        HJ_HIP(hipMemsetAsync(c->meta, 0, 4 * sizeof(unsigned long long), st));
-        record(c, kEvInit1, st);
-        trace("build: workspace", st, src.n);
-        HJ_RADIX(c, st, hj::radix_partition(src, wide, c->plan, radix_work(c), bucket_set(c->rset), st));
-        // repeated build keys, sampled: decides the join kernel (radix_join)
-        HJ_HIP(hj::radix_sample(wide, c->plan, bucket_set(c->rset), c->meta + 2, st));
-        trace("build: R partitioned", st, (long long)c->plan.total_bits);
-        if (!c->dual) {
-            record(c, kEvBuild1, st);
-            c->evs().rec[0] = c->evs().rec[1] = c->timing;
-            return HJ_OK;
-        }
+    const bool dual = used == HJ_STRATEGY_GLOBAL && c->strategy == HJ_STRATEGY_AUTO && src.n >= kDualMinBuildRows &&
+                      c->probe_hint < 0;
+    const bool radix = used == HJ_STRATEGY_RADIX || dual;
+    HJ_TRY(begin_build(c, layout, src.n, used, dual, false,
+                       radix ? hj::radix_plan(src.n, c->radix_bits, layout == kWide) : c->plan));
+    if (radix) {
+        HJ_TRY(radix_build(c, RadixSrc{src}, st));
+        if (!dual) return HJ_OK;
     }
     HJ_TRY(ensure_table(c, src.n, layout));
     c->bits = table_bits(src.n);
     const hj::TableDev t = table_dev(c);
-    if (!c->dual) record(c, kEvInit0, st);   // (dual: the build phase starts at R's partition)
+    if (!dual) record(c, kEvInit0, st);   // (dual: the build phase starts at R's partition)
     HJ_HIP(hj::launch_init(t, layout, 1ull << c->bits, st));
-    if (!c->dual) record(c, kEvInit1, st);
+    if (!dual) record(c, kEvInit1, st);
     HJ_HIP(hj::launch_build(t, layout, src, st));
     record(c, kEvBuild1, st);
     c->evs().rec[0] = c->evs().rec[1] = c->timing;
+    return HJ_OK;
+}
+
+// One probe of the current build, after the entry point's argument checks.
+enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti };
+struct ProbeReq {
+    RadixSrc in;       // S; routed: bins [bin0, bin0 + in.nbins) of the build's first pass
+    int bin0 = 0;
+    hj::OutDev out;    // inner: R and S payloads; semi / anti: S keys (may be null) and S payloads
+    ProbeKind kind = kProbeInner;
+};
+
+int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
+    HJ_TRY(set_device(c));
+    const hj::SrcDev &src = q.in.src;
+    const bool exists = q.kind == kProbeSemi || q.kind == kProbeAnti;
+    const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
+    c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
+    c->join_ran = c->exists_ran = false;
+    if (!radix) {
+        HJ_HIP(hipMemsetAsync(q.out.counter, 0, sizeof(uint64_t), st));
+        record(c, kEvProbe0, st);
+        if (exists) {
+            HJ_HIP(hj::launch_probe_exists(table_dev(c), c->layout, src, q.out, q.kind == kProbeAnti, st));
+        } else {
+            const size_t slow_cap = hj::probe_tiles(src.n);
+            HJ_TRY(ensure_buf(c->slow, slow_cap * sizeof(unsigned)));
+            HJ_HIP(hj::launch_probe(table_dev(c), c->layout, src, q.out, q.kind == kProbeCount, (unsigned *)c->slow.p,
+                                    slow_cap, st));
+        }
+    } else {
+        // (the work-map kernel zeroes the counter: no memset launch)
+        const bool wide = c->layout == kWide;
+        trace("probe: enter", st, src.n);
+        HJ_TRY(ensure_radix_scratch(c, c->sset, src.n, wide, c->plan, q.in.nsrc));
+        trace("probe: workspace", st, (long long)c->sset.max_buckets);
+        record(c, kEvProbe0, st);
+        HJ_TRY(radix_partition_src(c, q.in, c->sset, st));
+        trace("probe: S partitioned", st, src.n);
+        record(c, kEvProbeMid, st);
+        hj::BucketSet r = bucket_set(c->rset);
+        hj::JoinOpts o;
+        if (q.in.counts) {
+            // bins [bin0, bin0 + nbins): partitions [bin0, bin0 + nbins) << bits[1] of R
+            r.rstart += (size_t)q.bin0 << c->plan.bits[1];
+            o.nparts = q.in.nbins << c->plan.bits[1];
+        }
+        if (exists) {
+            HJ_RADIX(c, st, hj::radix_exists(wide, q.kind == kProbeAnti, c->plan, radix_work(c), r, bucket_set(c->sset),
+                                             q.out, st));
+            c->exists_ran = true;
+        } else {
+            // the kernel: a function of (row width, size ratio, build-time sample)
+            o.dup_flag = c->meta + 1;
+            o.sample = c->meta + 2;
+            o.count_only = q.kind == kProbeCount;
+            o.stream = src.n >= 8 * c->n_build;
+            HJ_RADIX(c, st, hj::radix_join(wide, c->plan, radix_work(c), r, bucket_set(c->sset), q.out, o, st));
+            c->join_ran = true;
+            c->join_wide = wide;
+            c->join_stream = o.stream;
+        }
+        trace("probe: joined", st, q.out.cap);
+    }
+    record(c, kEvProbe1, st);
+    c->evs().rec[2] = c->timing;
+    c->evs().rec_mid = radix && c->timing;   // kEvProbeMid split the phase (partition | join)
     return HJ_OK;
 }
 
@@ -604,54 +704,15 @@ int do_probe(hj_ctx *c, int layout, const hj::SrcDev &src, void *out_r, void *ou
     if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
     if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
     if (!count_only && (cap < 0 || (cap > 0 && (!out_r || !out_s)))) HJ_FAIL(HJ_ERR_ARG, "bad output");
-    HJ_TRY(set_device(c));
-    // (the radix join zeroes the counter in its work-map kernel: no memset launch)
-    const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
-    c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
-    c->join_ran = c->exists_ran = false;
-    if (radix) {
-        const bool wide = layout == kWide;
-        const size_t esz = wide ? 16 : 8;
-        trace("probe: enter", st, src.n);
-        HJ_TRY(ensure_radix_scratch(c, c->sset, src.n, esz, c->plan));
-        trace("probe: workspace", st, (long long)c->sset.max_buckets);
-        record(c, kEvProbe0, st);
-        HJ_RADIX(c, st, hj::radix_partition(src, wide, c->plan, radix_work(c), bucket_set(c->sset), st));
-        trace("probe: S partitioned", st, src.n);
-        record(c, kEvProbeMid, st);
-        // the kernel: a function of (row width, size ratio, build-time sample)
-        const bool stream = src.n >= 8 * c->n_build;
-        HJ_RADIX(c, st, hj::radix_join(wide, c->plan, radix_work(c), bucket_set(c->rset), bucket_set(c->sset), c->sset.max_runs,
-                              (unsigned *)c->work_start.p, c->work_desc.p, out_r, out_s, count_only ? 0 : cap,
-                              (unsigned long long *)d_count, c->meta + 1, count_only, st, c->meta + 2, stream));
-        c->join_ran = true;
-        c->join_wide = wide;
-        c->join_stream = stream;
-        trace("probe: joined", st, cap);
-        record(c, kEvProbe1, st);
-        c->evs().rec[2] = c->timing;
-        c->evs().rec_mid = c->timing;
-        return HJ_OK;
-    }
-    HJ_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
-    hj::OutDev out;
-    out.r = out_r;
-    out.s = out_s;
-    out.cap = count_only ? 0 : cap;
-    out.counter = (unsigned long long *)d_count;
-    record(c, kEvProbe0, st);
-    size_t slow_cap = hj::probe_tiles(src.n);
-    HJ_TRY(ensure_buf(c->slow, slow_cap * sizeof(unsigned)));
-    HJ_HIP(hj::launch_probe(table_dev(c), layout, src, out, count_only, (unsigned *)c->slow.p, slow_cap, st));
-    record(c, kEvProbe1, st);
-    c->evs().rec[2] = c->timing;
-    c->evs().rec_mid = false;
-    return HJ_OK;
+    ProbeReq q;
+    q.in.src = src;
+    q.out = hj::OutDev{out_r, out_s, count_only ? 0 : cap, (unsigned long long *)d_count};
+    q.kind = count_only ? kProbeCount : kProbeInner;
+    return run_probe(c, q, st);
 }
 
-// Semi- / anti-join probe (hj_dev_exists_*): do_probe's checks, strategy
-// choice, events and workspace; the table, R's partition, the side list and
-// the repeat flag meta[1] are only read (meta[1] not even that).
+// Semi- / anti-join probe (hj_dev_exists_*): the table, R's partition, the
+// side list and the repeat flag meta[1] are only read (meta[1] not even that).
 int do_exists(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, void *out_key, void *out_s, int64_t cap,
               uint64_t *d_count, hipStream_t st) {
     if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
@@ -661,42 +722,11 @@ int do_exists(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, void *out_
     if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
     if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
     if (cap < 0 || (cap > 0 && !out_s) || (cap == 0 && !out_s && out_key)) HJ_FAIL(HJ_ERR_ARG, "bad output");
-    HJ_TRY(set_device(c));
-    const bool anti = kind == HJ_EXISTS_ANTI;
-    const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
-    c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
-    c->join_ran = c->exists_ran = false;
-    if (radix) {
-        const bool wide = layout == kWide;
-        const size_t esz = wide ? 16 : 8;
-        HJ_TRY(ensure_radix_scratch(c, c->sset, src.n, esz, c->plan));
-        record(c, kEvProbe0, st);
-        HJ_RADIX(c, st, hj::radix_partition(src, wide, c->plan, radix_work(c), bucket_set(c->sset), st));
-        trace("exists: S partitioned", st, src.n);
-        record(c, kEvProbeMid, st);
-        // (the counter is zeroed by the work-map kernel, as for the inner join)
-        HJ_RADIX(c, st, hj::radix_exists(wide, anti, c->plan, radix_work(c), bucket_set(c->rset), bucket_set(c->sset),
-                                         c->sset.max_runs, (unsigned *)c->work_start.p, c->work_desc.p, out_key, out_s,
-                                         cap, (unsigned long long *)d_count, st));
-        c->exists_ran = true;
-        trace("exists: joined", st, cap);
-        record(c, kEvProbe1, st);
-        c->evs().rec[2] = c->timing;
-        c->evs().rec_mid = c->timing;
-        return HJ_OK;
-    }
-    HJ_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
-    hj::OutDev out;
-    out.r = out_key;
-    out.s = out_s;
-    out.cap = cap;
-    out.counter = (unsigned long long *)d_count;
-    record(c, kEvProbe0, st);
-    HJ_HIP(hj::launch_probe_exists(table_dev(c), layout, src, out, anti, st));
-    record(c, kEvProbe1, st);
-    c->evs().rec[2] = c->timing;
-    c->evs().rec_mid = false;
-    return HJ_OK;
+    ProbeReq q;
+    q.in.src = src;
+    q.out = hj::OutDev{out_key, out_s, cap, (unsigned long long *)d_count};
+    q.kind = kind == HJ_EXISTS_ANTI ? kProbeAnti : kProbeSemi;
+    return run_probe(c, q, st);
 }
 
 int do_partition(hj_ctx *c, const hj::SrcDev &src, int nparts, int64_t *out, uint64_t *d_counts, hipStream_t st) {
@@ -1472,13 +1502,12 @@ int hj_ctx_reserve(hj_ctx *c, int64_t max_build_rows, int key_bits) {
     if (max_build_rows < 0 || (key_bits != 32 && key_bits != 64)) HJ_FAIL(HJ_ERR_ARG, "bad reserve arguments");
     HJ_TRY(set_device(c));
     HJ_TRY(ensure_meta(c, 64));
-    const size_t esz = key_bits == 64 ? 16 : 8;
     if (choose_strategy(c, max_build_rows) == HJ_STRATEGY_GLOBAL) {
         HJ_TRY(ensure_table(c, max_build_rows, key_bits == 64 ? kWide : kNarrow));
         if (c->strategy != HJ_STRATEGY_AUTO || max_build_rows < kDualMinBuildRows) return HJ_OK;
     }
     const hj::RadixPlan pl = hj::radix_plan(max_build_rows, c->radix_bits, key_bits == 64);
-    return ensure_radix_scratch(c, c->rset, max_build_rows, esz, pl);
+    return ensure_radix_scratch(c, c->rset, max_build_rows, key_bits == 64, pl);
 }
 
 int64_t hj_ctx_table_capacity(const hj_ctx *c) {
@@ -1506,9 +1535,9 @@ int hj_ctx_build_has_duplicates(hj_ctx *c) {
         // only those a probe row met): the exact answer, once per build, is a
         // DETECT build over every partition of R (the work map is rebuilt from
         // R alone; the last join's map is not needed again)
-        HJ_RADIX(c, nullptr, hj::radix_detect(c->layout == kWide, c->plan, radix_work(c), bucket_set(c->rset),
-                                               (unsigned *)c->work_start.p, c->work_desc.p, c->meta + 1,
-                                               c->meta + 2, nullptr));
+        hipStream_t st = nullptr;   // the default stream
+        HJ_RADIX(c, st, hj::radix_detect(c->layout == kWide, c->plan, radix_work(c), bucket_set(c->rset),
+                                         /*dup_flag*/ c->meta + 1, /*sample*/ c->meta + 2, st));
         HJ_HIP(hipDeviceSynchronize());
         HJ_HIP(hipMemcpy(&v, c->meta + 1, 8, hipMemcpyDeviceToHost));
         c->dup_checked = true;
@@ -1620,8 +1649,7 @@ int hj_ctx_reserve_probe(hj_ctx *c, int64_t max_probe_rows, int key_bits) {
     if (max_probe_rows < 0 || (key_bits != 32 && key_bits != 64)) HJ_FAIL(HJ_ERR_ARG, "bad reserve arguments");
     if (c->layout < 0 || (c->used != HJ_STRATEGY_RADIX && !c->dual)) return HJ_OK;   // the global table needs none
     HJ_TRY(set_device(c));
-    const size_t esz = key_bits == 64 ? 16 : 8;
-    return ensure_radix_scratch(c, c->sset, max_probe_rows, esz, c->plan);
+    return ensure_radix_scratch(c, c->sset, max_probe_rows, key_bits == 64, c->plan);
 }
 
 // ------------------------------------------------------------ device phases
@@ -1731,10 +1759,6 @@ int hj_dev_build_routed_i64(hj_ctx *c, const int64_t *tuples, int64_t n, const u
         HJ_FAIL(HJ_ERR_ARG, "bad routed layout");
     // (what hj_dev_route_i64 can have produced: owner and bin bits from 9 hash bits)
     if (ceil_log2((unsigned long long)nranks) + sub_bits > 9) HJ_FAIL(HJ_ERR_ARG, "nranks << sub_bits must be <= 512");
-    hipStream_t st = (hipStream_t)stream;
-    HJ_TRY(set_device(c));
-    HJ_TRY(ensure_meta(c, 64));
-    HJ_TRY(timing_advance(c));
     // this rank's plan: the routing's bins are its first pass (skip = the
     // owner bits above them), one local pass of <= 9 bits below them
     hj::RadixPlan pl = hj::radix_plan(n, 0, true);
@@ -1750,26 +1774,8 @@ int hj_dev_build_routed_i64(hj_ctx *c, const int64_t *tuples, int64_t n, const u
     pl.pbl[2] = 0;
     pl.total_bits = t;
     pl.skip = ceil_log2((unsigned long long)nranks);
-    c->layout = kWide;
-    c->n_build = n;
-    c->used = HJ_STRATEGY_RADIX;
-    c->dual = false;
-    c->probe_used = -1;
-    c->join_ran = c->exists_ran = false;
-    c->memo.invalidate();
-    c->plan = pl;
-    c->routed = true;
-    c->dup_checked = false;
-    HJ_TRY(ensure_radix_scratch(c, c->rset, n, 16, pl, nsrc));
-    record(c, kEvInit0, st);
-    HJ_HIP(hipMemsetAsync(c->meta, 0, 4 * sizeof(unsigned long long), st));
-    record(c, kEvInit1, st);
-    HJ_RADIX(c, st, hj::radix_partition_routed(tuples, n, (const unsigned long long *)d_counts, nsrc, 1 << sub_bits, pl,
-                                      radix_work(c), bucket_set(c->rset), st));
-    HJ_HIP(hj::radix_sample(true, pl, bucket_set(c->rset), c->meta + 2, st));
-    record(c, kEvBuild1, st);
-    c->evs().rec[0] = c->evs().rec[1] = c->timing;
-    return HJ_OK;
+    HJ_TRY(begin_build(c, kWide, n, HJ_STRATEGY_RADIX, false, true, pl));
+    return radix_build(c, RadixSrc{src_packed(tuples, n), d_counts, nsrc, 1 << sub_bits}, (hipStream_t)stream);
 }
 
 int hj_dev_probe_routed_i64(hj_ctx *c, const int64_t *tuples, int64_t n, const uint64_t *d_counts, int nsrc,
@@ -1784,29 +1790,11 @@ int hj_dev_probe_routed_i64(hj_ctx *c, const int64_t *tuples, int64_t n, const u
     const int F = 1 << c->plan.bits[0];
     if (nsrc < 1 || nsrc > hj::kMaxRouteSources || bin0 < 0 || nbins < 1 || bin0 + nbins > F)
         HJ_FAIL(HJ_ERR_ARG, "bad routed layout");
-    hipStream_t st = (hipStream_t)stream;
-    HJ_TRY(set_device(c));
-    c->probe_used = HJ_STRATEGY_RADIX;   // (radix_join zeroes d_count)
-    HJ_TRY(ensure_radix_scratch(c, c->sset, n, 16, c->plan, nsrc));
-    record(c, kEvProbe0, st);
-    HJ_RADIX(c, st, hj::radix_partition_routed(tuples, n, (const unsigned long long *)d_counts, nsrc, nbins, c->plan,
-                                      radix_work(c), bucket_set(c->sset), st));
-    record(c, kEvProbeMid, st);
-    // bins [bin0, bin0 + nbins): partitions [bin0, bin0 + nbins) << bits[1] of R
-    hj::BucketSet r = bucket_set(c->rset);
-    r.rstart += (size_t)bin0 << c->plan.bits[1];
-    const bool stream_shape = n >= 8 * c->n_build;
-    HJ_RADIX(c, st, hj::radix_join(true, c->plan, radix_work(c), r, bucket_set(c->sset), c->sset.max_runs,
-                          (unsigned *)c->work_start.p, c->work_desc.p, out_r, out_s, out_cap,
-                          (unsigned long long *)d_count, c->meta + 1, false, st, c->meta + 2, stream_shape,
-                          nbins << c->plan.bits[1]));
-    c->join_ran = true;
-    c->join_wide = true;
-    c->join_stream = stream_shape;
-    record(c, kEvProbe1, st);
-    c->evs().rec[2] = c->timing;
-    c->evs().rec_mid = c->timing;
-    return HJ_OK;
+    ProbeReq q;
+    q.in = RadixSrc{src_packed(tuples, n), d_counts, nsrc, nbins};
+    q.bin0 = bin0;
+    q.out = hj::OutDev{out_r, out_s, out_cap, (unsigned long long *)d_count};
+    return run_probe(c, q, (hipStream_t)stream);
 }
 
 int hj_partition_of(int64_t key, int nparts) {

@@ -174,6 +174,8 @@ struct RadixWork {                 // scratch shared by the partition passes
     // 2 x (kRawCntWords): a small pass's raw run counts by pass parity, when
     // the next pass's plan launch scans them itself (null: a scan launch)
     unsigned long long *raw_cnt = nullptr;
+    unsigned *work_start = nullptr;   // >= radix_work_words: the joins' work map and deferred-item lists
+    void *work_desc = nullptr;        // >= radix_join_items * radix_item_desc_bytes(): their item descriptors
 };
 constexpr unsigned long long kRawCntWords = 4097;   // kPlanSegs + 1 (hj_radix.hip)
 
@@ -189,33 +191,33 @@ RadixPlan radix_plan(long long n_build, int force_bits = 0, bool wide = true);
 RadixNeed radix_need(long long n, const RadixPlan &pl, bool final_set, int routed_src = 0);
 unsigned long long radix_tiles(long long n, int max_nseg);
 unsigned long long radix_join_items(const RadixPlan &pl, unsigned long long s_runs);
-// words of radix_join's work_start buffer: work map (P + 1 + items), then two
+// words of RadixWork::work_start: work map (P + 1 + items), then two
 // deferred-item lists (count + items each: the fast join's, the grouped join's)
 unsigned long long radix_work_words(const RadixPlan &pl, unsigned long long s_runs);
 // Partitioned rows are packed: 16 B {key, pay} (wide) or 8 B key << 32 | row id (narrow).
 hipError_t radix_partition(const SrcDev &src, bool wide, const RadixPlan &pl, const RadixWork &ws,
                            const BucketSet &out, hipStream_t st);
 size_t radix_item_desc_bytes();
-// work_start: >= radix_work_words words; desc: >= radix_join_items * radix_item_desc_bytes()
-// sample: the build side's {rows, repeats} from radix_sample (device memory,
-// may be null = "unique"); stream = the probe side is many times the build
-// side (C2): int64 rows take the larger-sub-chunk shape.  The kernel that
-// joins follows from (wide, stream, sample) alone: join_kernel_choice.
-// nparts >= 0: join that many partitions (r.rstart / s.rstart views of a
-// sub-range) instead of the plan's 2^total_bits.
+struct JoinOpts {                                 // radix_join's modes
+    unsigned long long *dup_flag = nullptr;       // set when the build keys of a built partition repeat
+    const unsigned long long *sample = nullptr;   // the build side's {rows, repeats} from radix_sample (device memory; null = "unique")
+    bool count_only = false;                      // out.r / out.s are not written
+    bool stream = false;                          // the probe side is many times the build side (C2): int64 rows take the larger-sub-chunk shape
+    int nparts = -1;                              // >= 0: join that many partitions (r.rstart / s.rstart views of a sub-range), not the plan's 2^total_bits
+};
+// The kernel that joins follows from (wide, opt.stream, opt.sample) alone:
+// join_kernel_choice.  ws.work_start / ws.work_desc are sized for s.max_runs;
+// the work-map launch zeroes out.counter.
 hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
-                      unsigned long long s_runs, unsigned *work_start, void *desc, void *out_r, void *out_s, long long cap,
-                      unsigned long long *counter, unsigned long long *dup_flag, bool count_only, hipStream_t st,
-                      const unsigned long long *sample, bool stream, int nparts = -1);
+                      const OutDev &out, const JoinOpts &opt, hipStream_t st);
 // Semi- (anti: anti-) join of the partitioned relations: the S rows with /
-// without a partner in r.  out_key (may be null) and out_s receive the S keys
-// and payloads (int64, or int32 for narrow rows), cap == 0 counts only.  The
-// work map lives in work_start / desc as radix_join's (no deferred lists);
-// for anti every non-empty S partition is an item, build rows or not.
-// Reads r, writes neither it nor the repeat flag.
+// without a partner in r.  out.r (may be null) and out.s receive the S keys
+// and payloads (int64, or int32 for narrow rows), out.cap == 0 counts only.
+// The work map is radix_join's (no deferred lists); for anti every non-empty
+// S partition is an item, build rows or not.  Reads r, writes neither it nor
+// the repeat flag.
 hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
-                        const BucketSet &s, unsigned long long s_runs, unsigned *work_start, void *desc, void *out_key,
-                        void *out_s, long long cap, unsigned long long *counter, hipStream_t st);
+                        const BucketSet &s, const OutDev &out, hipStream_t st);
 // Folded routing's send side: rows (int64 columns or packed tuples) grouped
 // by the top rbits (<= 9) of radix_hash into out_tuples, exact and contiguous
 // per bin, bins in order; counts[2^rbits] their sizes.  One EXACT partition
@@ -239,12 +241,12 @@ hipError_t radix_sample(bool wide, const RadixPlan &pl, const BucketSet &r, unsi
                         hipStream_t st);
 // The exact "build keys repeat" answer for the whole build side r (the
 // plan's 2^total_bits partitions): k_join_b's DETECT build over one item per
-// non-empty partition (a work map rebuilt from r.rstart alone, in work_start /
-// desc), the partitions it cannot take by k_join's list-mode build (repeats
-// inside each of its build rounds); sets *dup_flag.  The joins themselves only
-// flag repeats of partitions they built (k_join_b: that a probe row met).
-hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, unsigned *work_start,
-                        void *desc, unsigned long long *dup_flag, const unsigned long long *sample, hipStream_t st);
+// non-empty partition (a work map rebuilt from r.rstart alone), the
+// partitions it cannot take by k_join's list-mode build (repeats inside each
+// of its build rounds); sets *dup_flag.  The joins themselves only flag
+// repeats of partitions they built (k_join_b: that a probe row met).
+hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
+                        unsigned long long *dup_flag, const unsigned long long *sample, hipStream_t st);
 // HJ_JOIN_KERNEL_* of the radix join for this shape and sample (host mirror
 // of the device-side choice)
 int join_kernel_choice(bool wide, bool stream, unsigned long long rows, unsigned long long repeats);

@@ -3438,9 +3438,10 @@ hipError_t exclusive_scan_u64(unsigned long long *v, unsigned long long len, uns
 size_t exclusive_scan_sums(unsigned long long len) { return (size_t)(len / kScanBlock + 2); }
 
 unsigned long long radix_join_items(const RadixPlan &pl, unsigned long long s_runs) {
-    // the smallest item of any shape (radix_join sizes items by its kernel's sub-chunk)
-    const u64 sub = (u64)kFastNT * kFastSI < (u64)kNarrowNT * kNarrowSI ? (u64)kFastNT * kFastSI
-                                                                         : (u64)kNarrowNT * kNarrowSI;
+    // the smallest item of any shape (work_map sizes items by its kernel's sub-chunk)
+    constexpr u64 sub = (u64)kFastNT * kFastSI;
+    static_assert(sub <= (u64)kNarrowNT * kNarrowSI && sub <= (u64)kStreamNT * kStreamSI &&
+                      sub <= (u64)kExistsNT * kExistsSI, "no kernel's sub-chunk is below the one the items are counted with");
     const u64 chr = (u64)kJoinSub * (sub >> kRunLog);
     return s_runs / chr + (1ull << pl.total_bits) + 2;
 }
@@ -3756,9 +3757,8 @@ hipError_t radix_partition_routed(const void *tuples, long long n, const unsigne
 // the pair counter, the repeat flag and the build-time sample.  A stage
 // copies them and adds exactly the fields it reads (item source, deferral
 // list, modes, ...): the rest keep JoinArgs' defaults.
-JoinArgs join_args(bool wide, const RadixPlan &pl, const BucketSet &r, const BucketSet &s, int P,
-                   const unsigned *work_start, const void *desc, void *out_r, void *out_s, long long cap, u64 *counter,
-                   u64 *dup_flag, const u64 *sample) {
+JoinArgs join_args(bool wide, const RadixPlan &pl, const BucketSet &r, const BucketSet &s, int P, const RadixWork &ws,
+                   const OutDev &out, u64 *dup_flag, const u64 *sample) {
     JoinArgs a{};
     a.r = r.rows;
     a.s = s.rows;
@@ -3767,14 +3767,14 @@ JoinArgs join_args(bool wide, const RadixPlan &pl, const BucketSet &r, const Buc
     a.r_rstart = r.rstart;
     a.s_rstart = s.rstart;
     a.P = P;
-    a.work_start = work_start;
-    a.desc = (const ItemDesc *)desc;
+    a.work_start = ws.work_start;
+    a.desc = (const ItemDesc *)ws.work_desc;
     // the hash bits right below the partition bits: LDS slot / bucket
     a.tshift = 64 - pl.skip - pl.total_bits - (wide ? kTableLog : kTableLogNarrow);
-    a.out_r = out_r;
-    a.out_s = out_s;
-    a.cap = cap;
-    a.counter = counter;
+    a.out_r = out.r;
+    a.out_s = out.s;
+    a.cap = out.cap;
+    a.counter = out.counter;
     a.dup_flag = dup_flag;
     a.sample = sample;
     return a;
@@ -3790,51 +3790,74 @@ inline void takes_list(JoinArgs &a, const unsigned *n) {
     a.list_n = n;
 }
 
-hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
-                      unsigned long long s_runs, unsigned *work_start, void *desc, void *out_r, void *out_s, long long cap,
-                      unsigned long long *counter, unsigned long long *dup_flag, bool count_only, hipStream_t st,
-                      const unsigned long long *sample, bool stream, int nparts) {
-    const int P = nparts >= 0 ? nparts : 1 << pl.total_bits;
-    unsigned *work_owner = work_start + P + 1;
-    if (pl.pbl[pl.passes - 1] != kFinalPbl) return hipErrorInvalidValue;
-    // persistent grids: two workgroups per CU (LDS-limited); i32 rows' fast
-    // kernel kNarrowPerCU
-    const unsigned pg = (unsigned)(2 * cu_count());
-    const unsigned pgn = (unsigned)(kNarrowPerCU * cu_count());
-    // the probe-heavy stream shape: int64 rows only (i32 rows keep the fast shape)
-    const bool stream_shape = stream && wide;
+// The work map every join starts from, in ws.work_start: the P partitions'
+// chunk starts, the item -> partition owner list, then deferred-item list 1
+// (the fast kernel's), list 2 (the grouped kernel's) and the fast kernel's
+// item counter; the items' descriptors in ws.work_desc.
+struct WorkMapSpec {
+    unsigned subb = 0;          // S runs per sub-chunk of the kernel that joins
+    unsigned grid = 1;          // that kernel's persistent grid
+    bool r_gates = true;        // a partition without build rows has no items
+    bool heavy_first = false;   // items of multi-chunk partitions first (k_item_desc): the longest are claimed first
+    int lists = 0;              // deferred-item lists in use: 0, 1, or 2 and the item counter
+    u64 *counter = nullptr;     // zeroed by k_item_desc
+};
+struct WorkMap {
+    unsigned items;             // their upper bound (one partial chunk per partition at most); 0: a plan the joins cannot take
+    unsigned *list1, *list2, *next_item;
+};
+// s: the side whose runs are cut into items; null: one item per non-empty partition of r (radix_detect)
+WorkMap work_map(const RadixPlan &pl, int P, const RadixWork &ws, const BucketSet &r, const BucketSet *s,
+                 const WorkMapSpec &m, hipStream_t st) {
+    WorkMap w{};
+    if (pl.pbl[pl.passes - 1] != kFinalPbl) return w;
+    unsigned *work_owner = ws.work_start + P + 1;
+    const u64 *s_rstart = s ? s->rstart : r.rstart, s_runs = s ? s->max_runs : 0;
     // S runs per work item: at least kJoinSub sub-chunks, more when S is
     // large against the partition count (each item rebuilds its R table), as
     // long as ~16 items per workgroup remain for balance
-    const unsigned subb = stream_shape ? (unsigned)((kStreamNT * kStreamSI) >> kRunLog)
-                                       : (wide ? (unsigned)((kFastNT * kFastSI) >> kRunLog)
-                                               : (unsigned)((kNarrowNT * kNarrowSI) >> kRunLog));
-    u64 chb = (u64)kJoinSub * subb;
-    const u64 want = (u64)s_runs / (16ull * (wide ? pg : pgn));
-    if (want > chb) chb = (want + subb - 1) / subb * subb;
-    // heavy-first item order (k_item_desc: items of multi-chunk partitions
-    // first, so the longest items are claimed first) for int64 rows
-    // (profiles/r03_heavy_first.txt); i32 rows keep partition order
-    // (k_join_grp lost 0.2 ms on REF-A with it)
-    const bool heavy_first = wide;
-    chunk_map_one(s.rstart, r.rstart, P, (unsigned)chb, work_start, work_owner, ws, st, heavy_first);
-    const unsigned items = (unsigned)((u64)s_runs / chb + (u64)P + 1);
-    // the deferred-item lists live after the work map: list 1 is the fast
-    // kernel's, list 2 the grouped kernel's; then the fast kernel's item counter
-    unsigned *list1 = work_owner + radix_join_items(pl, s_runs);
-    unsigned *list2 = list1 + 1 + radix_join_items(pl, s_runs);
-    unsigned *next_item = list2 + 1 + radix_join_items(pl, s_runs);
-    hipLaunchKernelGGL(k_item_desc, dim3(blocks_for(items, 256)), dim3(256), 0, st, (const unsigned *)work_start,
-                       (const unsigned *)work_owner, (const u64 *)s.rstart, (const u64 *)r.rstart, P, (unsigned)chb,
-                       (ItemDesc *)desc, list1, list2, next_item,
-                       heavy_first ? (const u64 *)ws.pcur : nullptr, counter);
-    const JoinArgs base = join_args(wide, pl, r, s, P, work_start, desc, out_r, out_s, cap, counter, dup_flag, sample);
-    const unsigned grid = items < pg ? items : pg;
+    u64 chb = s ? (u64)kJoinSub * m.subb : 0x7FFFFFFFu;
+    const u64 want = s_runs / (16ull * m.grid);
+    if (want > chb) chb = (want + m.subb - 1) / m.subb * m.subb;
+    chunk_map_one(s_rstart, m.r_gates ? r.rstart : nullptr, P, (unsigned)chb, ws.work_start, work_owner, ws, st,
+                  m.heavy_first);
+    w.items = (unsigned)(s_runs / chb + (u64)P + 1);
+    const u64 room = radix_join_items(pl, s_runs);
+    if (m.lists >= 1) w.list1 = work_owner + room;
+    if (m.lists >= 2) w.list2 = w.list1 + 1 + room, w.next_item = w.list2 + 1 + room;
+    hipLaunchKernelGGL(k_item_desc, dim3(blocks_for(w.items, 256)), dim3(256), 0, st, (const unsigned *)ws.work_start,
+                       (const unsigned *)work_owner, s_rstart, (const u64 *)r.rstart, P, (unsigned)chb,
+                       (ItemDesc *)ws.work_desc, w.list1, w.list2, w.next_item,
+                       m.heavy_first ? (const u64 *)ws.pcur : nullptr, m.counter);
+    return w;
+}
+
+hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
+                      const OutDev &out, const JoinOpts &opt, hipStream_t st) {
+    const int P = opt.nparts >= 0 ? opt.nparts : 1 << pl.total_bits;
+    // persistent grids: two workgroups per CU (LDS-limited); i32 rows' fast kernel kNarrowPerCU
+    const unsigned pg = (unsigned)(2 * cu_count()), pgn = (unsigned)(kNarrowPerCU * cu_count());
+    // the probe-heavy stream shape: int64 rows only (i32 rows keep the fast shape)
+    const bool stream_shape = opt.stream && wide;
+    WorkMapSpec m;
+    m.subb = stream_shape ? (unsigned)((kStreamNT * kStreamSI) >> kRunLog)
+                          : (wide ? (unsigned)((kFastNT * kFastSI) >> kRunLog)
+                                  : (unsigned)((kNarrowNT * kNarrowSI) >> kRunLog));
+    m.grid = wide ? pg : pgn;
+    // heavy-first for int64 rows (profiles/r03_heavy_first.txt); i32 rows keep
+    // partition order (k_join_grp lost 0.2 ms on REF-A with it)
+    m.heavy_first = wide;
+    m.lists = 2;
+    m.counter = out.counter;
+    const WorkMap w = work_map(pl, P, ws, r, &s, m, st);
+    if (!w.items) return hipErrorInvalidValue;
+    const JoinArgs base = join_args(wide, pl, r, s, P, ws, out, opt.dup_flag, opt.sample);
+    const unsigned grid = w.items < pg ? w.items : pg;
 // kernel K<WIDE, WRITE, ...> over the items' persistent grid: the writing
 // instantiation, or the count-only one
 #define HJ_JOIN(K, GRID, NT, ARGS, WIDE, ...)                                                                   \
     do {                                                                                                        \
-        if (count_only) hipLaunchKernelGGL((K<WIDE, false, __VA_ARGS__>), dim3(GRID), dim3(NT), 0, st, ARGS);   \
+        if (opt.count_only) hipLaunchKernelGGL((K<WIDE, false, __VA_ARGS__>), dim3(GRID), dim3(NT), 0, st, ARGS); \
         else hipLaunchKernelGGL((K<WIDE, true, __VA_ARGS__>), dim3(GRID), dim3(NT), 0, st, ARGS);               \
     } while (0)
 
@@ -3845,18 +3868,18 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
     // keys repeat -- stage 2 takes every item then, in the launch that takes
     // the deferrals otherwise (no exit-only launch of a kernel the sample did
     // not choose; k_join_u and k_join_b as two bodies of one kernel spilled
-    // 20 B at the 80-VGPR cap) -- and claims its items from next_item.
+    // 20 B at the 80-VGPR cap) -- and claims its w.items from next_item.
     JoinArgs fast = base;
-    defers_to(fast, list1);
+    defers_to(fast, w.list1);
     if (stream_shape) {
         fast.modes = kModesAll;
         HJ_JOIN(k_join_u, grid, kStreamNT, fast, true, kTableLog, kStreamNT, kStreamRI, kStreamSI, kStreamWPS);
     } else {
         fast.modes = kModeUnique | kModeSome;
-        fast.next_item = next_item;
+        fast.next_item = w.next_item;
         if (wide) HJ_JOIN(k_join_b, grid, kFastNT, fast, true, kFastNT, kFastRI, kFastSI, kFastWPS);
         else
-            HJ_JOIN(k_join_b, items < pgn ? items : pgn, kNarrowNT, fast, false, kNarrowNT, kNarrowRI, kNarrowSI,
+            HJ_JOIN(k_join_b, w.items < pgn ? w.items : pgn, kNarrowNT, fast, false, kNarrowNT, kNarrowRI, kNarrowSI,
                     kNarrowWPS, false, kTableLogNarrow);
     }
     // ---- stage 2, the grouped kernel (not after the stream kernel): list 1,
@@ -3866,11 +3889,11 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
     if (!stream_shape) {
         JoinArgs grp = base;
         grp.modes = kModesAll;
-        takes_list(grp, list1);
+        takes_list(grp, w.list1);
         grp.all_if_mode2 = true;
-        defers_to(grp, list2);
+        defers_to(grp, w.list2);
         const unsigned pgw = (unsigned)(kGrpWidePerCU * cu_count());
-        if (wide) HJ_JOIN(k_join_grp, items < pgw ? items : pgw, kGrpNT, grp, true, kGrpNT, kGrpWideRI, kGrpWideSI);
+        if (wide) HJ_JOIN(k_join_grp, w.items < pgw ? w.items : pgw, kGrpNT, grp, true, kGrpNT, kGrpWideRI, kGrpWideSI);
         else HJ_JOIN(k_join_grp, grid, kGrpNT, grp, false, kGrpNT, kGrpRI, kGrpSI);
     }
     // ---- stage 3, k_join: what the stages above deferred (INT64_MIN build
@@ -3878,7 +3901,7 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
     // stream kernel; a persistent grid that exits at once when the list is empty
     JoinArgs rest = base;
     rest.modes = kModesAll;
-    takes_list(rest, stream_shape ? list1 : list2);
+    takes_list(rest, stream_shape ? w.list1 : w.list2);
     if (wide) HJ_JOIN(k_join, grid, 512, rest, true, kTableLog, 512, 0, true);
     else HJ_JOIN(k_join, grid, 512, rest, false, kTableLog, 512, 0, true);
 #undef HJ_JOIN
@@ -3886,32 +3909,21 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
 }
 
 hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
-                        const BucketSet &s, unsigned long long s_runs, unsigned *work_start, void *desc, void *out_key,
-                        void *out_s, long long cap, unsigned long long *counter, hipStream_t st) {
+                        const BucketSet &s, const OutDev &out, hipStream_t st) {
     const int P = 1 << pl.total_bits;
-    unsigned *work_owner = work_start + P + 1;
-    if (pl.pbl[pl.passes - 1] != kFinalPbl) return hipErrorInvalidValue;
     const unsigned pg = (unsigned)(2 * cu_count());   // two 64-KiB tables per CU
-    // S runs per work item as radix_join sizes them; never below the item
-    // radix_join_items counts with, so the map fits the same buffers
-    constexpr unsigned subb = (unsigned)((kExistsNT * kExistsSI) >> kRunLog);
-    static_assert(kExistsNT * kExistsSI >= kFastNT * kFastSI || kExistsNT * kExistsSI >= kNarrowNT * kNarrowSI,
-                  "an exists item must be at least radix_join_items' item");
-    u64 chb = (u64)kJoinSub * subb;
-    const u64 want = (u64)s_runs / (16ull * pg);
-    if (want > chb) chb = (want + subb - 1) / subb * subb;
-    // semi: partitions without build rows have nothing to emit (zero chunks);
-    // anti: those S rows are exactly the ones to emit, so every non-empty S
-    // partition is live.  Either way items <= s_runs / chb + P: one partial
-    // chunk per partition at most, which is what radix_join_items bounds.
-    chunk_map_one(s.rstart, anti ? nullptr : r.rstart, P, (unsigned)chb, work_start, work_owner, ws, st, false);
-    const unsigned items = (unsigned)((u64)s_runs / chb + (u64)P + 1);
-    hipLaunchKernelGGL(k_item_desc, dim3(blocks_for(items, 256)), dim3(256), 0, st, (const unsigned *)work_start,
-                       (const unsigned *)work_owner, (const u64 *)s.rstart, (const u64 *)r.rstart, P, (unsigned)chb,
-                       (ItemDesc *)desc, nullptr, nullptr, nullptr, nullptr, counter);
-    JoinArgs a = join_args(wide, pl, r, s, P, work_start, desc, out_key, out_s, cap, counter, nullptr, nullptr);
+    WorkMapSpec m;
+    m.subb = (unsigned)((kExistsNT * kExistsSI) >> kRunLog);
+    m.grid = pg;
+    // semi: partitions without build rows have nothing to emit; anti: those S
+    // rows are exactly the ones to emit, so every non-empty S partition is live
+    m.r_gates = !anti;
+    m.counter = out.counter;
+    const WorkMap w = work_map(pl, P, ws, r, &s, m, st);
+    if (!w.items) return hipErrorInvalidValue;
+    JoinArgs a = join_args(wide, pl, r, s, P, ws, out, nullptr, nullptr);
     a.tshift = 64 - pl.skip - pl.total_bits - kExistsTableLog;
-    const unsigned grid = items < pg ? items : pg;
+    const unsigned grid = w.items < pg ? w.items : pg;
     const unsigned kind = anti ? 1u : 0u;
     if (wide)
         hipLaunchKernelGGL((k_join_exists<true, kExistsNT, kExistsSI, kExistsWPS>), dim3(grid), dim3(kExistsNT), 0, st,
@@ -3947,27 +3959,24 @@ __global__ __launch_bounds__(256) void k_defer_rows(const unsigned *list, const 
     }
 }
 
-hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, unsigned *work_start,
-                        void *desc, unsigned long long *dup_flag, const unsigned long long *sample, hipStream_t st) {
+hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
+                        unsigned long long *dup_flag, const unsigned long long *sample, hipStream_t st) {
     // one item per non-empty partition of the WHOLE build side (a work map
     // from r.rstart alone: partitions no probe row reached are checked too)
     const int P = 1 << pl.total_bits;
-    unsigned *work_owner = work_start + P + 1;
-    const unsigned whole = 0x7FFFFFFFu;   // runs per item: a partition is one item
-    chunk_map_one(r.rstart, r.rstart, P, whole, work_start, work_owner, ws, st);
-    unsigned *list1 = work_owner + radix_join_items(pl, 0);
-    hipLaunchKernelGGL(k_item_desc, dim3(blocks_for((u64)P + 1, 256)), dim3(256), 0, st, (const unsigned *)work_start,
-                       (const unsigned *)work_owner, (const u64 *)r.rstart, (const u64 *)r.rstart, P, whole,
-                       (ItemDesc *)desc, list1, nullptr, nullptr, nullptr, nullptr);
+    WorkMapSpec m;
+    m.lists = 1;
+    const WorkMap w = work_map(pl, P, ws, r, nullptr, m, st);
+    if (!w.items) return hipErrorInvalidValue;
     // (the probe side is the build side; no outputs, and no counter yet)
-    const JoinArgs base = join_args(wide, pl, r, r, P, work_start, desc, nullptr, nullptr, 0, nullptr, dup_flag, sample);
+    const JoinArgs base = join_args(wide, pl, r, r, P, ws, OutDev{}, dup_flag, sample);
     const unsigned pg = (unsigned)(2 * cu_count());
     // ---- k_join_b's DETECT build of every partition.  Partitions the
     // bucketed table cannot take (oversized) are deferred to k_join's
     // list-mode build below, which flags repeats inside each of its build rounds
     JoinArgs det = base;
     det.modes = kModesAll;
-    defers_to(det, list1);
+    defers_to(det, w.list1);
     if (wide)
         hipLaunchKernelGGL((k_join_b<true, false, kFastNT, kFastRI, kFastSI, kFastWPS, true>), dim3(pg), dim3(kFastNT), 0,
                            st, det);
@@ -3981,7 +3990,7 @@ hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, con
     auto join_list1 = [&](bool empty_s, const u64 *skip_if_set) {
         JoinArgs rest = base;
         rest.modes = kModesAll;
-        takes_list(rest, list1);
+        takes_list(rest, w.list1);
         rest.counter = ws.pcur;
         rest.empty_s = empty_s;
         rest.skip_if_set = skip_if_set;
@@ -4005,8 +4014,8 @@ hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, con
     // round once m exceeds the rounds, so the self-join only ever runs over
     // partitions whose keys repeat at most once per round)
     join_list1(false, dup_flag);
-    hipLaunchKernelGGL(k_defer_rows, dim3(pg), dim3(256), 0, st, (const unsigned *)(list1 + 1), (const unsigned *)list1,
-                       (const ItemDesc *)desc, (const u64 *)r.runs, ws.pcur, dup_flag);
+    hipLaunchKernelGGL(k_defer_rows, dim3(pg), dim3(256), 0, st, (const unsigned *)(w.list1 + 1), (const unsigned *)w.list1,
+                       (const ItemDesc *)ws.work_desc, (const u64 *)r.runs, ws.pcur, dup_flag);
     return hipGetLastError();
 }
 

@@ -93,8 +93,12 @@ int body(int lg) {
     CK(hipDeviceSynchronize());
     unsigned *work = dalloc<unsigned>(radix_work_words(pl, ss.max_runs));
     void *desc = dalloc<char>(radix_join_items(pl, ss.max_runs) * radix_item_desc_bytes());
+    ws.work_start = work;
+    ws.work_desc = desc;
     u64 *out_r = dalloc<u64>(n + (1 << 20)), *out_s = dalloc<u64>(n + (1 << 20));
     u64 *cnt = dalloc<u64>(8), *dup = dalloc<u64>(8);
+    JoinOpts jo;
+    jo.dup_flag = dup;
     unsigned *defer = dalloc<unsigned>(radix_join_items(pl, ss.max_runs) + 8), *defer_n = dalloc<unsigned>(4);
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
@@ -124,7 +128,7 @@ int body(int lg) {
         printf("%-40s %7.3f ms  %7.1f GB/s  M=%llu deferred=%u\n", name, ms, (3.0 * n * (W ? 16 : 8)) / ms / 1e6, m, dn);
     };
     run("radix_join (product)", [&] {
-        CK(radix_join(W, pl, ws, rs, ss, ss.max_runs, work, desc, out_r, out_s, (long long)n, cnt, dup, false, 0, nullptr, false));
+        CK(radix_join(W, pl, ws, rs, ss, OutDev{out_r, out_s, (long long)n, cnt}, jo, 0));
     });
     JoinArgs a;
     a.r = rs.rows; a.s = ss.rows; a.r_runs = rs.runs; a.s_runs = ss.runs; a.r_rstart = rs.rstart;

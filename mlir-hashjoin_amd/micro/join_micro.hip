@@ -111,8 +111,12 @@ int main(int argc, char **argv) {
     }
     unsigned *work = dalloc<unsigned>(radix_work_words(pl, ss.max_runs));
     void *desc = dalloc<char>(radix_join_items(pl, ss.max_runs) * radix_item_desc_bytes());
+    ws.work_start = work;
+    ws.work_desc = desc;
     u64 *out_r = dalloc<u64>(n + (1 << 20)), *out_s = dalloc<u64>(n + (1 << 20)), *cnt = dalloc<u64>(8),
         *dup = dalloc<u64>(8);
+    JoinOpts jo;
+    jo.dup_flag = dup;
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
@@ -136,7 +140,7 @@ int main(int argc, char **argv) {
         printf("%-34s %7.3f ms  %7.1f GB/s  M=%llu\n", name, ms, (3.0 * n * 16) / ms / 1e6, m);
     };
     run("radix_join (product)", [&] {
-        CK(radix_join(true, pl, ws, rs, ss, ss.max_runs, work, desc, out_r, out_s, (long long)n, cnt, dup, false, 0, nullptr, false));
+        CK(radix_join(true, pl, ws, rs, ss, OutDev{out_r, out_s, (long long)n, cnt}, jo, 0));
     });
     // work map of the product call stays in `work`
     JoinArgs a;

@@ -75,6 +75,8 @@ int main(int argc, char **argv) {
     const u64 cap = 1200000000ull;
     unsigned *work = dalloc<unsigned>(radix_work_words(pl, ss.max_runs));
     void *desc = dalloc<char>(radix_join_items(pl, ss.max_runs) * radix_item_desc_bytes());
+    ws.work_start = work;
+    ws.work_desc = desc;
     unsigned *out_r = dalloc<unsigned>(cap), *out_s = dalloc<unsigned>(cap);
     u64 *cnt = dalloc<u64>(8), *dup = dalloc<u64>(8);
     // a build-side sample that says "most keys repeat": the grouped join over every item
@@ -106,15 +108,18 @@ int main(int argc, char **argv) {
     };
     // the general kernel over every item (what the product runs once the
     // fast path has deferred most items)
-    CK(radix_join(false, pl, ws, rs, ss, ss.max_runs, work, desc, out_r, out_s, (long long)cap, cnt, dup, false, 0,
-                  stats, false));
+    JoinOpts jo;
+    jo.dup_flag = dup;
+    jo.sample = stats;
+    JoinOpts jo_count = jo;
+    jo_count.count_only = true;
+    CK(radix_join(false, pl, ws, rs, ss, OutDev{out_r, out_s, (long long)cap, cnt}, jo, 0));
     CK(hipDeviceSynchronize());
     run("product general path (k_join_grp)", [&] {
-        CK(radix_join(false, pl, ws, rs, ss, ss.max_runs, work, desc, out_r, out_s, (long long)cap, cnt, dup, false, 0,
-                      stats, false));
+        CK(radix_join(false, pl, ws, rs, ss, OutDev{out_r, out_s, (long long)cap, cnt}, jo, 0));
     });
     run("product general, count only", [&] {
-        CK(radix_join(false, pl, ws, rs, ss, ss.max_runs, work, desc, out_r, out_s, 0, cnt, dup, true, 0, stats, false));
+        CK(radix_join(false, pl, ws, rs, ss, OutDev{out_r, out_s, 0, cnt}, jo_count, 0));
     });
     JoinArgs a;
     a.r = rs.rows; a.s = ss.rows; a.r_runs = rs.runs; a.s_runs = ss.runs; a.r_rstart = rs.rstart;

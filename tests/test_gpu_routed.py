@@ -19,7 +19,7 @@ import torch
 
 import routed_layout as RL
 from hashjoin import HashJoin
-from hashjoin._lib import HJ_ERR_ARG, lib
+from hashjoin._lib import HJ_ERR_ARG, HJ_JOIN_KERNEL_EXISTS, lib
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +28,7 @@ SENTINEL = 0x5A5A5A5A5A5A5A5A
 # (senders = owners, bin bits per owner, S bin ranges); (8, 6, 2) is the N = 8 product plan
 SHAPES = [(2, 4, 1), (4, 3, 3), (8, 1, 1), (16, 5, 4), (64, 3, 2), (8, 6, 2)]
 RUN_UNITS = [0, 1, 63, 64, 65, 129]   # rows of one (sender, part): around the 64-row run unit
+EXISTS = HashJoin.JOIN_KERNELS[HJ_JOIN_KERNEL_EXISTS]
 
 
 def _dev(a):
@@ -269,10 +270,29 @@ def test_capacity_below_m(hj, oracle):
     assert len(np.unique(both, axis=0)) == M
 
 
+def _reported(h):
+    """What the context says of its last probe: (join kernel, strategy)."""
+    return h.join_kernel, h.strategy_used
+
+
+def _alone(build, probe):
+    """_reported of a fresh context after build(h) followed directly by probe(h)."""
+    h = HashJoin(0)
+    try:
+        build(h)
+        probe(h)
+        return _reported(h)
+    finally:
+        h.close()
+
+
 def test_unrouted_probes_after_routed_build(hj, oracle):
     """After a routed build the ordinary probes are valid too (hj.h): this
     owner's S rows, unrouted, through hj_dev_probe_tuples_i64 and the semi-
-    and anti-join hj_dev_exists_tuples_i64 give the oracle's join / np.isin."""
+    and anti-join hj_dev_exists_tuples_i64 give the oracle's join / np.isin.
+    hj_ctx_join_kernel names the last probe's kernel throughout: the exists
+    kernel after each exists probe, and after the closing routed probe what a
+    fresh context reports for that build and probe alone."""
     N, sub, q = 4, 3, 1
     rk, rp, sk, sp = oracle.gen_pkfk_i64(360, 40000, 60000, 0.6)
     rk = rk.copy(); sk = sk.copy()
@@ -295,6 +315,7 @@ def test_unrouted_probes_after_routed_build(hj, oracle):
         out_k = torch.empty_like(out_s)
         m = int(hj.probe_exists_tuples(t, kind, out_s, out_k).item())
         assert m == len(want)
+        assert hj.join_kernel == EXISTS
         got = oracle.sorted_pairs(out_k[:m].cpu().numpy(), out_s[:m].cpu().numpy())
         assert np.array_equal(got, oracle.sorted_pairs(want[:, 0], want[:, 1]))
     # and the routed probe still joins after them
@@ -302,6 +323,62 @@ def test_unrouted_probes_after_routed_build(hj, oracle):
     ts, cs = S.received(q)
     o = RL.probe_exact(lambda a, b: hj.probe_routed(ts, cs, 0, a, b), ts.shape[0], ts.device)
     assert oracle.same_multiset(o[0].cpu().numpy(), o[1].cpu().numpy(), *exp)
+    last = _reported(hj)
+    assert last[0] != EXISTS
+    tr, cr = RL.Routed(hj, _dev(rk), _dev(rp), N, sub).received(q)
+    fresh = _alone(lambda h: h.build_routed(tr, cr, N, sub),
+                   lambda h: RL.probe_exact(lambda a, b: h.probe_routed(ts, cs, 0, a, b), ts.shape[0], ts.device))
+    assert fresh[0] is not None
+    assert last == fresh
+
+
+def test_last_probe_is_reported_through_mixed_probes(hj, oracle, relations):
+    """One routed build, then routed inner, semi, tuple, anti, count and routed
+    inner probes in that order, then a semi probe with a routed inner probe
+    directly behind it (the one order in which no other entry point runs
+    between an exists probe and a routed one): every call returns the oracle's
+    count (np.isin for semi / anti), and join_kernel / strategy_used name that
+    call's kernel: the exists kernel for semi / anti, for an inner probe what
+    a fresh context reports after the same build followed by that probe alone."""
+    N, sub, q = 4, 3, 1
+    (rk, rp, sk, sp), dev, _ = relations["pkfk"]
+    tr, cr = RL.Routed(hj, dev[0], dev[1], N, sub).received(q)
+    ts, cs = RL.Routed(hj, dev[2], dev[3], N, sub).received(q)
+    g = N.bit_length() - 1
+    own_r, own_s = RL.rparts(rk, g) == q, RL.rparts(sk, g) == q
+    mine = np.stack([sk[own_s], sp[own_s]], axis=1)
+    t, col = _dev(mine), _dev(mine[:, 0])
+    M = len(oracle.chained_join_i64(rk[own_r], rp[own_r], mine[:, 0], mine[:, 1])[0])
+    hit = int(np.isin(mine[:, 0], rk[own_r]).sum())
+    assert 0 < hit < len(mine) and ts.shape[0] == len(mine)
+
+    def build(h):
+        h.build_routed(tr, cr, N, sub)
+
+    def routed(h):
+        return RL.probe_exact(lambda a, b: h.probe_routed(ts, cs, 0, a, b), len(mine), t.device)[0].shape[0]
+
+    def tuples(h):
+        return RL.probe_exact(lambda a, b: h.probe_tuples(t, a, b), len(mine), t.device)[0].shape[0]
+
+    def count(h):
+        return h.count_rows(col)
+
+    def exists(kind):
+        return lambda h: int(h.probe_exists_tuples(t, kind, torch.empty(len(mine), dtype=torch.int64, device="cuda")).item())
+
+    alone = {f: _alone(build, f) for f in (routed, tuples, count)}
+    for f in alone:
+        assert alone[f] == (alone[f][0], "radix") and alone[f][0] not in (None, EXISTS)
+    steps = [(routed, M, alone[routed]), (exists("semi"), hit, (EXISTS, "radix")), (tuples, M, alone[tuples]),
+             (exists("anti"), len(mine) - hit, (EXISTS, "radix")), (count, M, alone[count]),
+             (routed, M, alone[routed]), (exists("semi"), hit, (EXISTS, "radix")), (routed, M, alone[routed])]
+    build(hj)
+    for i, (probe, want, reported) in enumerate(steps):
+        got = probe(hj)
+        print(f"step {i}: count {got} (want {want}), reports {_reported(hj)} (want {reported})")
+        assert got == want
+        assert _reported(hj) == reported
 
 
 def test_routed_build_rejects_more_than_nine_routing_bits(hj):
