@@ -381,9 +381,7 @@ int ensure_rows(Buf &b, size_t bytes, size_t bucket_bytes) {
     if (b.bytes >= bytes) return HJ_OK;
     if (bytes < kPlaceMinBytes || bucket_bytes < kPlaceMinBucket || !placement_probe_on()) return ensure_buf(b, bytes);
     free_buf(b);
-    int dev = 0, cus = 0;
-    HJ_HIP(hipGetDevice(&dev));
-    HJ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const int cus = hj::cu_count();
     const float good = g_place_good.load();
     std::vector<Buf> held;   // rejected draws still held (oldest first)
     Buf best;
@@ -2106,9 +2104,7 @@ int hj_dev_stream_copy(const void *in, void *out, int64_t rows, int shape, void 
     if (rows < 0) HJ_FAIL(HJ_ERR_ARG, "negative row count");
     if (rows > 0 && (!in || !out || (((uintptr_t)in | (uintptr_t)out) & 15)))
         HJ_FAIL(HJ_ERR_ARG, "copy buffers must be non-null and 16-B aligned");
-    int dev = 0, cus = 0;
-    HJ_HIP(hipGetDevice(&dev));
-    HJ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const int cus = hj::cu_count();
     HJ_HIP(hj::launch_stream_copy(in, out, rows, shape, cus, (hipStream_t)stream));
     return HJ_OK;
 }
@@ -2170,9 +2166,7 @@ double hj_placement_set_good(double ratio) {
 int hj_placement_check(const void *buf, int64_t bytes, double *ratio) {
     if (!buf || bytes <= 0 || !ratio) HJ_FAIL(HJ_ERR_ARG, "placement check: null buffer / ratio or no bytes");
     *ratio = 0.0;
-    int dev = 0, cus = 0;
-    HJ_HIP(hipGetDevice(&dev));
-    HJ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const int cus = hj::cu_count();
     float r = 0.0f;
     const hipError_t e = hj::placement_probe(const_cast<void *>(buf), (size_t)bytes, size_t(16) << hj::kPassPbl, cus, &r);
     if (e == hipErrorInvalidValue) HJ_FAIL(HJ_ERR_ARG, "placement check: buffer below 4 MiB per CU");

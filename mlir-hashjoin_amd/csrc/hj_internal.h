@@ -103,6 +103,10 @@ struct OutDev {
     unsigned long long *counter;  // device u64: total match count (all rows, even past cap)
 };
 
+// CUs of the current device (hj_radix.hip): asked once per process, then
+// remembered -- the devices of one process are taken to be alike
+int cu_count();
+
 // launchers (hipError_t of the launch; all asynchronous on `st`)
 hipError_t launch_init(const TableDev &t, int layout, unsigned long long cap, hipStream_t st);
 hipError_t launch_build(const TableDev &t, int layout, const SrcDev &src, hipStream_t st);

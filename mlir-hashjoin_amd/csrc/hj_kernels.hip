@@ -8,11 +8,26 @@
 //                                       -> k_probe<WRITE=true>: ILP slot
 //                                          reads, ballot-compacted output,
 //                                          one global cursor add per block
-// plus the radix partition used by the multi-GPU exchange and the
-// counter-based generators of the benchmark inputs.
+// plus the exists probes (k_probe_exists), the radix partition used by the
+// multi-GPU exchange, the selection, the counter-based generators of the
+// benchmark inputs and the copy floors.
 //
 // Wave64 throughout: 256-thread blocks (4 waves), all per-lane work
 // independent, no warp-32 idioms.  Integer/byte work: no MFMA.
+//
+// Written once, used by several kernels / launchers:
+//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists)
+//   wave_incl_add    every wave prefix sum (hj_internal.h: DPP, no LDS round trips)
+//   with_layout_form the (layout, form) -> template-argument dispatch of the launchers
+//   probe_grid       the tile probes' grid and LDS bytes
+//   cu_count         the CU count (hj_radix.hip)
+// k_probe and k_probe_exists still each spell out their row load, chain walk
+// and ballot compaction, and the three count kernels their block sum: as
+// shared functions these compiled to other instruction streams (DESIGN.md,
+// "Refactor check (global-table kernels)").  A fix to one copy belongs in
+// the other too.
+#include <type_traits>
+
 #include "hj_internal.h"
 #include "hj_gen.h"
 
@@ -186,6 +201,26 @@ __device__ __forceinline__ bool probe_row(const SrcDev &src, unsigned long long 
     return true;
 }
 
+// The table as the tile probes read it: from global memory, or (LDS) from
+// the copy that every workgroup makes once in s_tab, its dynamic LDS.
+template <int L, bool LDS>
+struct TableView {
+    using slot_t = typename Lay<L>::slot_t;
+    const slot_t *sl;
+    __device__ __forceinline__ TableView(const TableDev &t, ulonglong2 *s_tab) {
+        if constexpr (LDS) {
+            const unsigned long long n16 = (t.mask + 1) * sizeof(slot_t) / 16;
+            const ulonglong2 *g16 = (const ulonglong2 *)t.slots;
+            for (unsigned long long j = threadIdx.x; j < n16; j += kBlock) s_tab[j] = g16[j];
+            __syncthreads();
+            sl = (const slot_t *)s_tab;
+        } else {
+            sl = (const slot_t *)t.slots;
+        }
+    }
+    __device__ __forceinline__ slot_t at(unsigned long long h) const { return sl[h]; }
+};
+
 // ------------------------------------------------------------------ probe
 // count (join_v1.mlir:288-425, join_v2.mlir:311-439) and probe
 // (join_v1.mlir:436-521, join_v2.mlir:450-604) in one kernel family.
@@ -210,7 +245,8 @@ __device__ __forceinline__ bool probe_row(const SrcDev &src, unsigned long long 
 // capacity was too small still learns the exact M (rows past cap dropped).
 //
 // LDS (small tables, <= kLdsTableBytes): each workgroup first copies the
-// whole table into LDS and the fast path reads its slots there; the probes
+// whole table into LDS and the fast path reads its slots there (TableView:
+// the copy and the slot read, for this kernel and k_probe_exists); the probes
 // of a table that fits one XCD's L2 were random L2 reads (~82-96 G/s), well
 // below the rate the probe side streams at (profiles/r06/r06sr_small_build_sides.txt).
 template <int L, int FORM, bool WRITE, bool LDS = false>
@@ -225,20 +261,15 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
     __shared__ unsigned s_cw[kProbeItems * NW];
     extern __shared__ ulonglong2 s_tab[];
 
-    const slot_t *sl = (const slot_t *)t.slots;
-    if constexpr (LDS) {
-        const unsigned long long n16 = (t.mask + 1) * sizeof(slot_t) / 16;
-        const ulonglong2 *g16 = (const ulonglong2 *)t.slots;
-        for (unsigned long long j = threadIdx.x; j < n16; j += kBlock) s_tab[j] = g16[j];
-        __syncthreads();
-    }
-    auto slot_at = [&](unsigned long long h) -> slot_t {
-        if constexpr (LDS) return ((const slot_t *)s_tab)[h];
-        else return sl[h];
-    };
+    const TableView<L, LDS> tab(t, s_tab);
     const bool unique = (__hip_atomic_load(&t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
+    // A tile handed to the general path (to_slow) leaves the body by
+    // `continue` and so skips the barrier at its end.  That is safe only
+    // because nothing between the loop head and the last `continue` touches
+    // s_cw, st_base or wsum: the row loads, the chain walks and tab.at() use
+    // registers and the table alone.  Code moved above that point must keep it so.
     for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
         unsigned long long K[kProbeItems], P[kProbeItems];
         bool V[kProbeItems];
@@ -268,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
 #pragma unroll
         for (int i = 0; i < kProbeItems; ++i) {
             H[i] = slot_of(K[i], t.shift);
-            if (V[i]) S[i] = slot_at(H[i]);
+            if (V[i]) S[i] = tab.at(H[i]);
         }
         unsigned found = 0;
         unsigned long long RP[kProbeItems];
@@ -282,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
             unsigned long long hh = H[i];
             while (!LY::empty(sv) && LY::key(sv) != K[i]) {
                 hh = (hh + 1) & t.mask;
-                sv = slot_at(hh);
+                sv = tab.at(hh);
             }
             if (!LY::empty(sv)) {
                 found |= 1u << i;
@@ -300,17 +331,17 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
             for (int i = 0; i < kProbeItems; ++i) {
                 if (!((found >> i) & 1u)) continue;
                 unsigned long long hh = slot_of(K[i], t.shift);
-                slot_t sv = slot_at(hh);
+                slot_t sv = tab.at(hh);
                 while (!LY::empty(sv) && LY::key(sv) != K[i]) {   // (back to the first copy)
                     hh = (hh + 1) & t.mask;
-                    sv = slot_at(hh);
+                    sv = tab.at(hh);
                 }
                 hh = (hh + 1) & t.mask;
-                sv = slot_at(hh);
+                sv = tab.at(hh);
                 while (!LY::empty(sv) && !multi) {
                     multi = LY::key(sv) == K[i];
                     hh = (hh + 1) & t.mask;
-                    sv = slot_at(hh);
+                    sv = tab.at(hh);
                 }
             }
             if (__syncthreads_or(multi ? 1 : 0)) {
@@ -343,12 +374,7 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
             if (wv == 0) {   // exclusive scan of the kProbeItems * NW runs (<= 64)
                 static_assert(kProbeItems * NW <= 64, "one lane per run");
                 const unsigned v = lane < kProbeItems * NW ? s_cw[lane] : 0u;
-                unsigned x = v;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const unsigned y = __shfl_up(x, o, 64);
-                    if (lane >= o) x += y;
-                }
+                const unsigned x = wave_incl_add(v);
                 if (lane < kProbeItems * NW) s_cw[lane] = x - v;
                 if (lane == 63) st_base = x ? atomicAdd(out.counter, (unsigned long long)x) : 0ull;
             }
@@ -491,8 +517,9 @@ __global__ __launch_bounds__(kBlock) void k_probe_slow(TableDev t, SrcDev src, O
 // Semi- / anti-join probe (EXISTS / NOT EXISTS): the S rows that have / have
 // no partner in the built table.  k_probe's shape -- 2048-row tiles, every
 // row's first slot load issued before any is resolved, the LDS copy of small
-// tables, ballot compaction in row-slot-major order after ONE cursor add per
-// tile -- without its general path: a row yields at most one output element
+// tables (TableView), ballot compaction in row-slot-major order after ONE
+// cursor add per tile (k_probe<WRITE>'s, statement for statement: keep the
+// two equal) -- without its general path: a row yields at most one output element
 // whatever the build side repeats, so a chain walk ends at the first equal
 // key or at EMPTY, meta[1] is never read and no tile is handed on.  A wide
 // INT64_MIN probe key matches iff the side list holds a row (meta[0]).
@@ -510,17 +537,7 @@ __global__ __launch_bounds__(kBlock) void k_probe_exists(TableDev t, SrcDev src,
     __shared__ unsigned s_cw[kProbeItems * NW];
     extern __shared__ ulonglong2 s_tab[];
 
-    const slot_t *sl = (const slot_t *)t.slots;
-    if constexpr (LDS) {
-        const unsigned long long n16 = (t.mask + 1) * sizeof(slot_t) / 16;
-        const ulonglong2 *g16 = (const ulonglong2 *)t.slots;
-        for (unsigned long long j = threadIdx.x; j < n16; j += kBlock) s_tab[j] = g16[j];
-        __syncthreads();
-    }
-    auto slot_at = [&](unsigned long long h) -> slot_t {
-        if constexpr (LDS) return ((const slot_t *)s_tab)[h];
-        else return sl[h];
-    };
+    const TableView<L, LDS> tab(t, s_tab);
     const bool side_rows = L == kWide && t.meta[0] != 0ull;   // the build side holds an INT64_MIN key
     const unsigned flip = anti ? (1u << kProbeItems) - 1u : 0u;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -543,7 +560,7 @@ __global__ __launch_bounds__(kBlock) void k_probe_exists(TableDev t, SrcDev src,
 #pragma unroll
         for (int i = 0; i < kProbeItems; ++i) {
             H[i] = slot_of(K[i], t.shift);
-            if ((walk >> i) & 1u) S[i] = slot_at(H[i]);
+            if ((walk >> i) & 1u) S[i] = tab.at(H[i]);
         }
 #pragma unroll
         for (int i = 0; i < kProbeItems; ++i) {
@@ -552,7 +569,7 @@ __global__ __launch_bounds__(kBlock) void k_probe_exists(TableDev t, SrcDev src,
             unsigned long long hh = H[i];
             while (!LY::empty(sv) && LY::key(sv) != K[i]) {
                 hh = (hh + 1) & t.mask;
-                sv = slot_at(hh);
+                sv = tab.at(hh);
             }
             if (!LY::empty(sv)) found |= 1u << i;
         }
@@ -787,13 +804,7 @@ __global__ __launch_bounds__(NT) void k_route_scatter(SrcDev src, unsigned P, in
             c[j] = d < P ? cnt[d] : 0u;
             sum += c[j];
         }
-        unsigned x = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        unsigned run = x - sum;
+        unsigned run = wave_incl_add(sum) - sum;   // (the whole of wave 0 is here)
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
             const unsigned d = lane * PER + j;
@@ -988,14 +999,9 @@ __global__ __launch_bounds__(kBlock) void k_sel_write(const V *in, long long n, 
 #pragma unroll
         for (int w = 0; w < W; ++w)
             if (e0 + w < n && sel_pass(x[j].v[w], op, c)) pass[j] |= 1u << w;
-        // lane prefix within the wave for this slot
+        // lane prefix within the wave for this slot (every lane gets here)
         const unsigned k = (unsigned)__popc(pass[j]);
-        unsigned xs = k;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned y = __shfl_up(xs, o, 64);
-            if (lane >= o) xs += y;
-        }
+        const unsigned xs = wave_incl_add(k);
         lpre[j] = xs - k;
         if (lane == 63) s_cw[j * NW + wv] = xs;
     }
@@ -1032,6 +1038,45 @@ inline unsigned grid_for(long long n, int per_block) {
     return (unsigned)((n + per_block - 1) / per_block);
 }
 
+// The (layout, form) pairs the library has kernels for, as compile-time
+// constants: f(integral_constant<int, L>, integral_constant<int, FORM>);
+// any other pair is hipErrorInvalidValue and instantiates nothing.
+// with_form64: the two int64 forms alone (the partition takes no others).
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <typename F>
+hipError_t with_form64(int form, F &&f) {
+    if (form == kCols64) return f(int_c<kCols64>{});
+    if (form == kPacked64) return f(int_c<kPacked64>{});
+    return hipErrorInvalidValue;
+}
+template <typename F>
+hipError_t with_layout_form(int layout, int form, F &&f) {
+    if (layout == kWide) return with_form64(form, [&](auto fm) { return f(int_c<kWide>{}, fm); });
+    if (layout == kNarrow && form == kCol32) return f(int_c<kNarrow>{}, int_c<kCol32>{});
+    return hipErrorInvalidValue;
+}
+
+// Grid of the tile probes (k_probe, k_probe_exists) over n rows.  A table of
+// <= kLdsTableBytes: every workgroup copies it into LDS once (tbytes of
+// dynamic LDS) and strides over the tiles, as many workgroups as LDS lets a
+// CU hold; a larger one: one workgroup per tile.
+struct ProbeGrid {
+    bool lds;
+    size_t tbytes;
+    unsigned grid;
+};
+ProbeGrid probe_grid(const TableDev &t, int layout, long long n) {
+    const unsigned tiles = grid_for(n, kProbeTile);
+    const size_t tbytes = (size_t)(t.mask + 1) * (layout == kWide ? 16 : 8);
+    const bool lds = tbytes <= (size_t)kLdsTableBytes && tbytes >= 16;
+    unsigned per_cu = lds ? (unsigned)(kLdsPerCu / tbytes) : 1u;
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    const unsigned most = (unsigned)cu_count() * per_cu;
+    return {lds, tbytes, lds && most < tiles ? most : tiles};
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- launchers
@@ -1047,15 +1092,10 @@ hipError_t launch_init(const TableDev &t, int layout, unsigned long long cap, hi
 hipError_t launch_build(const TableDev &t, int layout, const SrcDev &src, hipStream_t st) {
     if (src.n <= 0) return hipSuccess;
     const unsigned g = grid_for(src.n, kBlock * kBuildItems);
-    if (layout == kWide) {
-        if (src.form == kCols64) hipLaunchKernelGGL((k_build<kWide, kCols64>), dim3(g), dim3(kBlock), 0, st, t, src);
-        else if (src.form == kPacked64) hipLaunchKernelGGL((k_build<kWide, kPacked64>), dim3(g), dim3(kBlock), 0, st, t, src);
-        else return hipErrorInvalidValue;
-    } else {
-        if (src.form == kCol32) hipLaunchKernelGGL((k_build<kNarrow, kCol32>), dim3(g), dim3(kBlock), 0, st, t, src);
-        else return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_layout_form(layout, src.form, [&](auto l, auto f) {
+        hipLaunchKernelGGL((k_build<decltype(l)::value, decltype(f)::value>), dim3(g), dim3(kBlock), 0, st, t, src);
+        return hipGetLastError();
+    });
 }
 
 size_t probe_tiles(long long n) {
@@ -1069,80 +1109,32 @@ hipError_t launch_probe(const TableDev &t, int layout, const SrcDev &src, const 
     hipError_t e = hipMemsetAsync(&t.meta[3], 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
     const unsigned long long cap = slow_cap;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const unsigned tiles = grid_for(src.n, kProbeTile);
-    const unsigned gs = tiles < (unsigned)(cus * 8) ? tiles : (unsigned)(cus * 8);
-    // a table of <= kLdsTableBytes: every workgroup copies it into LDS once
-    // and strides over the tiles (as many workgroups as LDS lets a CU hold)
-    const size_t tbytes = (size_t)(t.mask + 1) * (layout == kWide ? 16 : 8);
-    const bool lds = tbytes <= (size_t)kLdsTableBytes && tbytes >= 16;
-    unsigned per_cu = lds ? (unsigned)(kLdsPerCu / tbytes) : 1u;
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    const unsigned gl = tiles < (unsigned)cus * per_cu ? tiles : (unsigned)cus * per_cu;
-    const unsigned g = lds ? gl : tiles;   // (global table: one block per tile)
-#define HJ_PROBE(L, F)                                                                                        \
-    do {                                                                                                      \
-        if (count_only) {                                                                                     \
-            if (lds)                                                                                          \
-                hipLaunchKernelGGL((k_probe<L, F, false, true>), dim3(g), dim3(kBlock), tbytes, st, t, src,   \
-                                   out, slow, cap);                                                           \
-            else hipLaunchKernelGGL((k_probe<L, F, false>), dim3(g), dim3(kBlock), 0, st, t, src, out, slow, cap); \
-            hipLaunchKernelGGL((k_probe_slow<L, F, false>), dim3(gs), dim3(kBlock), 0, st, t, src, out,       \
-                               (const unsigned *)slow, cap);                                                  \
-        } else {                                                                                              \
-            if (lds)                                                                                          \
-                hipLaunchKernelGGL((k_probe<L, F, true, true>), dim3(g), dim3(kBlock), tbytes, st, t, src,    \
-                                   out, slow, cap);                                                           \
-            else hipLaunchKernelGGL((k_probe<L, F, true>), dim3(g), dim3(kBlock), 0, st, t, src, out, slow, cap); \
-            hipLaunchKernelGGL((k_probe_slow<L, F, true>), dim3(gs), dim3(kBlock), 0, st, t, src, out,        \
-                               (const unsigned *)slow, cap);                                                  \
-        }                                                                                                     \
-    } while (0)
-    if (layout == kWide) {
-        if (src.form == kCols64) HJ_PROBE(kWide, kCols64);
-        else if (src.form == kPacked64) HJ_PROBE(kWide, kPacked64);
-        else return hipErrorInvalidValue;
-    } else {
-        if (src.form == kCol32) HJ_PROBE(kNarrow, kCol32);
-        else return hipErrorInvalidValue;
-    }
-#undef HJ_PROBE
-    return hipGetLastError();
+    const ProbeGrid pg = probe_grid(t, layout, src.n);
+    // the general path's persistent workgroups: eight per CU, a tile each at most
+    const unsigned tiles = grid_for(src.n, kProbeTile), most = (unsigned)(cu_count() * 8);
+    const unsigned gs = tiles < most ? tiles : most;
+    return with_layout_form(layout, src.form, [&](auto l, auto f) {
+        constexpr int L = decltype(l)::value, F = decltype(f)::value;
+        const auto fast = count_only ? (pg.lds ? k_probe<L, F, false, true> : k_probe<L, F, false, false>)
+                                     : (pg.lds ? k_probe<L, F, true, true> : k_probe<L, F, true, false>);
+        const auto rest = count_only ? k_probe_slow<L, F, false> : k_probe_slow<L, F, true>;
+        hipLaunchKernelGGL(fast, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, slow, cap);
+        hipLaunchKernelGGL(rest, dim3(gs), dim3(kBlock), 0, st, t, src, out, (const unsigned *)slow, cap);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, bool anti,
                                hipStream_t st) {
     if (src.n <= 0) return hipSuccess;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const unsigned tiles = grid_for(src.n, kProbeTile);
-    // the grid of launch_probe: LDS-resident tables stride the tiles from as
-    // many workgroups as LDS lets a CU hold, else one workgroup per tile
-    const size_t tbytes = (size_t)(t.mask + 1) * (layout == kWide ? 16 : 8);
-    const bool lds = tbytes <= (size_t)kLdsTableBytes && tbytes >= 16;
-    unsigned per_cu = lds ? (unsigned)(kLdsPerCu / tbytes) : 1u;
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    const unsigned gl = tiles < (unsigned)cus * per_cu ? tiles : (unsigned)cus * per_cu;
-    const unsigned g = lds ? gl : tiles;
+    const ProbeGrid pg = probe_grid(t, layout, src.n);
     const unsigned a = anti ? 1u : 0u;
-#define HJ_EXISTS(L, F)                                                                                          \
-    do {                                                                                                         \
-        if (lds) hipLaunchKernelGGL((k_probe_exists<L, F, true>), dim3(g), dim3(kBlock), tbytes, st, t, src, out, a); \
-        else hipLaunchKernelGGL((k_probe_exists<L, F, false>), dim3(g), dim3(kBlock), 0, st, t, src, out, a);     \
-    } while (0)
-    if (layout == kWide) {
-        if (src.form == kCols64) HJ_EXISTS(kWide, kCols64);
-        else if (src.form == kPacked64) HJ_EXISTS(kWide, kPacked64);
-        else return hipErrorInvalidValue;
-    } else {
-        if (src.form == kCol32) HJ_EXISTS(kNarrow, kCol32);
-        else return hipErrorInvalidValue;
-    }
-#undef HJ_EXISTS
-    return hipGetLastError();
+    return with_layout_form(layout, src.form, [&](auto l, auto f) {
+        constexpr int L = decltype(l)::value, F = decltype(f)::value;
+        const auto k = pg.lds ? k_probe_exists<L, F, true> : k_probe_exists<L, F, false>;
+        hipLaunchKernelGGL(k, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, a);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_partition(const SrcDev &src, int nparts, void *out_tuples,
@@ -1151,39 +1143,27 @@ hipError_t launch_partition(const SrcDev &src, int nparts, void *out_tuples,
     if (rbits > 0 && (rbits > 13 || P != (1u << rbits))) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(counts, 0, sizeof(unsigned long long) * P, st);
     if (e != hipSuccess) return e;
-    if (src.n > 0) {
+    if (src.n <= 0) return hipGetLastError();
+    return with_form64(src.form, [&](auto f) {
+        constexpr int F = decltype(f)::value;
         const unsigned g = grid_for(src.n, kBlock * kPartItems);
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const unsigned gh = g < (unsigned)cus * 8u ? g : (unsigned)cus * 8u;
+        const unsigned most = (unsigned)cu_count() * 8u;
+        const unsigned gh = g < most ? g : most;
         const size_t lds_h = sizeof(unsigned) * P;
         const size_t lds_s = sizeof(unsigned) * ((P + 1) & ~1u) + sizeof(unsigned long long) * P;
-        if (src.form == kCols64) hipLaunchKernelGGL(k_part_hist<kCols64>, dim3(gh), dim3(kBlock), lds_h, st, src, P, rbits, counts);
-        else if (src.form == kPacked64) hipLaunchKernelGGL(k_part_hist<kPacked64>, dim3(gh), dim3(kBlock), lds_h, st, src, P, rbits, counts);
-        else return hipErrorInvalidValue;
+        ulonglong2 *rows = (ulonglong2 *)out_tuples;
+        hipLaunchKernelGGL(k_part_hist<F>, dim3(gh), dim3(kBlock), lds_h, st, src, P, rbits, counts);
         hipLaunchKernelGGL(k_part_offsets, dim3(1), dim3(64), 0, st, counts, P, cursors);
-        if (P >= 4u && P <= (unsigned)kRouteMaxPartsS) {
-            const unsigned gt = grid_for(src.n, kRouteTileS);
-            if (src.form == kCols64)
-                hipLaunchKernelGGL((k_route_scatter<kCols64, kRouteTileS, kRouteThreadsS, kRouteMaxPartsS>), dim3(gt),
-                                   dim3(kRouteThreadsS), 0, st, src, P, rbits, (ulonglong2 *)out_tuples, cursors);
-            else
-                hipLaunchKernelGGL((k_route_scatter<kPacked64, kRouteTileS, kRouteThreadsS, kRouteMaxPartsS>), dim3(gt),
-                                   dim3(kRouteThreadsS), 0, st, src, P, rbits, (ulonglong2 *)out_tuples, cursors);
-        } else if (P <= (unsigned)kRouteMaxParts) {
-            const unsigned gt = grid_for(src.n, kRouteTile);
-            if (src.form == kCols64)
-                hipLaunchKernelGGL((k_route_scatter<kCols64, kRouteTile, kRouteThreads, kRouteMaxParts>), dim3(gt),
-                                   dim3(kRouteThreads), 0, st, src, P, rbits, (ulonglong2 *)out_tuples, cursors);
-            else
-                hipLaunchKernelGGL((k_route_scatter<kPacked64, kRouteTile, kRouteThreads, kRouteMaxParts>), dim3(gt),
-                                   dim3(kRouteThreads), 0, st, src, P, rbits, (ulonglong2 *)out_tuples, cursors);
-        } else if (src.form == kCols64)
-            hipLaunchKernelGGL(k_part_scatter<kCols64>, dim3(g), dim3(kBlock), lds_s, st, src, P, rbits, (ulonglong2 *)out_tuples, cursors);
+        if (P >= 4u && P <= (unsigned)kRouteMaxPartsS)
+            hipLaunchKernelGGL((k_route_scatter<F, kRouteTileS, kRouteThreadsS, kRouteMaxPartsS>),
+                               dim3(grid_for(src.n, kRouteTileS)), dim3(kRouteThreadsS), 0, st, src, P, rbits, rows, cursors);
+        else if (P <= (unsigned)kRouteMaxParts)
+            hipLaunchKernelGGL((k_route_scatter<F, kRouteTile, kRouteThreads, kRouteMaxParts>),
+                               dim3(grid_for(src.n, kRouteTile)), dim3(kRouteThreads), 0, st, src, P, rbits, rows, cursors);
         else
-            hipLaunchKernelGGL(k_part_scatter<kPacked64>, dim3(g), dim3(kBlock), lds_s, st, src, P, rbits, (ulonglong2 *)out_tuples, cursors);
-    }
-    return hipGetLastError();
+            hipLaunchKernelGGL(k_part_scatter<F>, dim3(g), dim3(kBlock), lds_s, st, src, P, rbits, rows, cursors);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_gen_pkfk(unsigned long long seed, long long NR, unsigned long long hit_thr,

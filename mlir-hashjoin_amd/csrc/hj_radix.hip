@@ -3281,15 +3281,6 @@ constexpr int kTableLog = 12;   // LDS table slots of the int64-row joins (2^12 
 constexpr int kNarrowNT = 768, kNarrowRI = 4, kNarrowSI = 5, kNarrowWPS = 6, kNarrowPerCU = 2, kTableLogNarrow = 13,
               kPlanLogNarrow = 13;
 
-int cu_count() {
-    static int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return cus > 0 ? cus : 256;
-    }();
-    return n;
-}
-
 inline unsigned blocks_for(u64 n, u64 per) { return (unsigned)((n + per - 1) / per); }
 
 // Workgroups of a partition pass over n rows: one per CU, fewer for small
@@ -3358,6 +3349,15 @@ void chunk_map(const u64 *off_a, const u64 *off_b, int nseg, unsigned chunk, uns
 }
 
 }  // namespace
+
+int cu_count() {   // (hj_internal.h: hj_kernels.hip and hj_capi.cpp size their grids by it too)
+    static int n = [] {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        return cus > 0 ? cus : 256;
+    }();
+    return n;
+}
 
 // ----------------------------------------------------------------- planning
 RadixPlan radix_plan(long long n_build, int force_bits, bool wide) {

@@ -73,6 +73,109 @@ def test_small_table_i32(hj, oracle, nr):
     assert oracle.same_multiset(*o, *oracle.chained_join_i32(r, s, H=max(1, nr // 4)))
 
 
+I64_MIN = -(1 << 63)
+# 1026 tiles of 2048 rows, the last with 77: a 64-KiB table runs two
+# workgroups per CU (512 on 256 CUs), so every workgroup strides over two
+# tiles at least, workgroups 0 and 1 over three
+SEVERAL_NS = (1 << 21) + 2048 + 77
+# INT64_MIN probe keys: tile 3 (workgroup 3 hands on its first tile and keeps
+# its second), tile 512 + 7 (workgroup 7: the reverse), tiles 0 and 512
+# (workgroup 0 keeps only its third) and the ragged last tile
+NULL_ROWS = (3 * 2048 + 5, (512 + 7) * 2048 + 100, 1, 512 * 2048 + 2047, 1025 * 2048 + 10)
+
+
+def several_tiles_case(wide):
+    """Build and probe columns, and what numpy says they join to: a table of
+    exactly 64 KiB with five repeated keys (wide: and one INT64_MIN key), a
+    probe side a quarter of which hits it, forty rows of it a repeated key."""
+    nr, ns = (2048, SEVERAL_NS) if wide else (4096, SEVERAL_NS)
+    dt, top = (np.int64, 1 << 40) if wide else (np.int32, 1 << 29)
+    rng = np.random.default_rng(2048 if wide else 4096)
+    rk = rng.permutation(np.unique(rng.integers(1, top, 2 * nr)))[:nr].astype(dt)
+    assert len(rk) == nr
+    rk[nr - 5:] = rk[:5]                                    # five keys twice
+    plain = np.arange(5, nr - 5)                            # build rows whose key is neither repeated nor null
+    if wide:
+        rk[100] = I64_MIN
+        plain = plain[plain != 100]
+    rp = np.arange(nr, dtype=np.int64) + (7000 if wide else 0)   # (i32: the row id)
+    sk = rng.integers(2 * top, 4 * top - 1, ns).astype(dt)       # misses
+    hit = rng.permutation(ns)[:ns // 4]
+    sk[hit] = rk[rng.choice(plain, len(hit))]               # a quarter of S hits R once
+    sk[rng.permutation(ns)[:40]] = rk[0]                    # forty rows meet a repeated key
+    if wide:
+        sk[list(NULL_ROWS)] = I64_MIN
+    sp = np.arange(ns, dtype=np.int64) + (1 << 32 if wide else 0)
+    # sort + searchsorted: build rows lo[j] .. hi[j] of the sorted side match probe row j
+    order = np.argsort(rk, kind="stable")
+    lo, hi = np.searchsorted(rk[order], sk, "left"), np.searchsorted(rk[order], sk, "right")
+    cnt = hi - lo
+    first = np.cumsum(cnt) - cnt
+    within = np.arange(int(cnt.sum())) - np.repeat(first, cnt)
+    exp_r = rp[order[np.repeat(lo, cnt) + within]]
+    exp_s = np.repeat(sp, cnt)
+    assert int((cnt == 2).sum()) >= 40 and int((cnt > 0).sum()) >= ns // 4
+    return dict(rk=rk, rp=rp, sk=sk, sp=sp, cnt=cnt, exp_r=exp_r, exp_s=exp_s,
+                d_rk=dev(rk), d_rp=dev(rp) if wide else None, d_sk=dev(sk), d_sp=dev(sp) if wide else None)
+
+
+@pytest.fixture(scope="module")
+def several_i64():
+    return several_tiles_case(True)
+
+
+def sorted_pairs(a, b):
+    o = np.lexsort((b, a))
+    return np.stack([a[o], b[o]])
+
+
+def inner_pairs(hj, c):
+    """The join of case c through probe_relation, outputs sized M + 64."""
+    wide = c["rk"].dtype == np.int64
+    hj.build_table(c["d_rk"], c["d_rp"])
+    m = len(c["exp_r"])
+    o_r = torch.full((m + 64,), -7, dtype=torch.int64 if wide else torch.int32, device="cuda")
+    o_s = torch.full_like(o_r, -7)
+    got = int(hj.probe_relation(c["d_sk"], c["d_sp"], o_r, o_s).item())
+    assert hj.strategy_used == "global"
+    assert got == m
+    return o_r[:m].cpu().numpy().astype(np.int64), o_s[:m].cpu().numpy().astype(np.int64)
+
+
+@pytest.mark.parametrize("kind", ["inner", "count", "semi", "anti"])
+def test_workgroups_take_several_tiles(hj, several_i64, kind):
+    """k_probe's / k_probe_exists's grid-stride loop with more than one tile
+    per workgroup, some of them handed to the general path (NULL_ROWS, the
+    forty rows that meet a repeated key): exact count, exact rows."""
+    c = several_i64
+    if kind == "inner":
+        g_r, g_s = inner_pairs(hj, c)
+        assert np.array_equal(sorted_pairs(g_r, g_s), sorted_pairs(c["exp_r"], c["exp_s"]))
+        return
+    hj.build_table(c["d_rk"], c["d_rp"])
+    if kind == "count":
+        assert hj.count_rows(c["d_sk"]) == len(c["exp_r"])
+        assert hj.strategy_used == "global"
+        return
+    keep = c["cnt"] > 0 if kind == "semi" else c["cnt"] == 0
+    m = int(keep.sum())
+    o_s = torch.full((len(c["sk"]),), -7, dtype=torch.int64, device="cuda")
+    o_k = torch.full_like(o_s, -7)
+    got = int(hj.probe_exists(c["d_sk"], c["d_sp"], kind, o_s, o_k).item())
+    assert hj.strategy_used == "global"
+    assert got == m
+    assert np.array_equal(sorted_pairs(o_k[:m].cpu().numpy(), o_s[:m].cpu().numpy()),
+                          sorted_pairs(c["sk"][keep], c["sp"][keep]))
+    assert hj.count_exists(c["d_sk"], kind) == m
+
+
+def test_workgroups_take_several_tiles_i32(hj):
+    """The same shape for the i32 types: 4096 build rows, 8192 slots x 8 B = 64 KiB."""
+    c = several_tiles_case(False)
+    g_r, g_s = inner_pairs(hj, c)
+    assert np.array_equal(sorted_pairs(g_r, g_s), sorted_pairs(c["exp_r"], c["exp_s"]))
+
+
 @pytest.mark.parametrize("nr,wide", [(1500, True), (4000, True), (3000, False), (20000, False)])
 def test_few_repeated_build_keys(hj, oracle, nr, wide):
     """A handful of repeated build keys: only the tiles whose rows meet one go
