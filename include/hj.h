@@ -131,7 +131,7 @@ int hj_ctx_last_timing_ex(hj_ctx *ctx, float ms[8]);
 int hj_ctx_timing_accumulate(hj_ctx *ctx, int enable);
 int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 /* RADIX: the join kernel of the last probe, whichever entry point ran it
- * (hj_dev_probe_*, hj_dev_count_*, hj_dev_exists_*, and after a routed build
+ * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_count_*, hj_dev_exists_*, and after a routed build
  * hj_dev_probe_routed_i64 too).  A pure function of the row
  * width, the probe / build size ratio (>= 8: the probe-heavy shape) and the
  * build side's repeated keys, sampled at build time over up to 64 partitions
@@ -213,6 +213,48 @@ int hj_dev_exists_tuples_i64(hj_ctx *ctx, int kind, const int64_t *tuples, int64
                              int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
 int hj_dev_exists_i32(hj_ctx *ctx, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t *out_key,
                       int32_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
+
+/* Probe-side outer join (LEFT OUTER with the probe relation on the left) over
+ * the table an ordinary hj_dev_build_* left: one build serves inner, semi,
+ * anti and outer probes in any order.  For the built relation R and the probe
+ * relation S the result is the multiset
+ *   {(R.pay[i], S.pay[j]) : R.key[i] == S.key[j]}            (the inner join)
+ *   u {(null_pay, S.pay[j]) : no i has R.key[i] == S.key[j]}  (the null rows),
+ * so every S row appears at least once: M = sum over j of max(1, matches(j))
+ * >= |S|, with equality iff no S row has two partners.  Row order is
+ * unspecified; matched and null rows may interleave.
+ * null_pay (i32: null_row, with row ids row_base + row as hj_dev_probe_i32's)
+ * is written verbatim into out_r; the caller picks a value R's payloads (row
+ * ids) do not take -- -1 is the natural one for row ids.
+ * INT64_MIN is a key like any other: an INT64_MIN probe key pairs with every
+ * INT64_MIN build row, or yields one null row if R holds none.  R empty:
+ * every S row comes out as a null row.  S empty: M = 0.
+ * d_count = the exact M even when M > out_cap: rows past out_cap are dropped
+ * (which ones is unspecified) and nothing is written at or past index out_cap
+ * in either output; bit 63 as above.  out_cap == 0 with both outputs NULL is
+ * the count-only form (spay may be NULL then); with out_cap > 0 both outputs
+ * are required.
+ * Errors as hj_dev_probe_*: HJ_ERR_ARG (null context -- checked first --, bad
+ * relation, bad output), HJ_ERR_STATE (no build of that layout).
+ * Asynchronous on the stream, kernels only once hj_ctx_reserve /
+ * hj_ctx_reserve_probe sized the workspace (graph-capturable).  The strategy
+ * is chosen exactly as for hj_dev_probe_* (the AUTO dual build included) and
+ * hj_ctx_strategy_used reports it.  The probe timing covers the whole call;
+ * RADIX: [4] is the one partition of S, [5] everything after it (the join's
+ * kernels, then the unmatched-rows stage over the same partition), and
+ * hj_ctx_join_kernel reports the kernel that produced the pairs, as after
+ * hj_dev_probe_*.  The built table, R's partition and the side list are left
+ * untouched and hj_ctx_build_has_duplicates answers what it would after
+ * hj_dev_probe_* of the same S: inner, semi, anti and outer probes of one
+ * build may follow each other in any order and each returns what it returned
+ * before.  Valid after hj_dev_build_routed_i64 too, over unrouted rows, like
+ * hj_dev_probe_i64. */
+int hj_dev_probe_outer_i64(hj_ctx *ctx, const int64_t *skey, const int64_t *spay, int64_t n, int64_t null_pay,
+                           int64_t *out_r, int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_probe_outer_tuples_i64(hj_ctx *ctx, const int64_t *tuples, int64_t n, int64_t null_pay,
+                                  int64_t *out_r, int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_probe_outer_i32(hj_ctx *ctx, const int32_t *skey, int64_t n, int64_t row_base, int32_t null_row,
+                           int32_t *out_r, int32_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
 
 /* Radix partition of rows into nparts (1..8192) groups by a key hash independent of
  * the table's slot hash: out_tuples (2*n int64) receives packed {key, pay}

@@ -629,12 +629,13 @@ int do_build(hj_ctx *c, int layout, const hj::SrcDev &src, hipStream_t st) {
 }
 
 // One probe of the current build, after the entry point's argument checks.
-enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti };
+enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter };
 struct ProbeReq {
     RadixSrc in;       // S; routed: bins [bin0, bin0 + in.nbins) of the build's first pass
     int bin0 = 0;
-    hj::OutDev out;    // inner: R and S payloads; semi / anti: S keys (may be null) and S payloads
+    hj::OutDev out;    // inner, outer: R and S payloads; semi / anti: S keys (may be null) and S payloads
     ProbeKind kind = kProbeInner;
+    unsigned long long null_pay = 0;   // outer: the R payload of an S row without a partner (out.cap == 0 counts only)
 };
 
 int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
@@ -652,8 +653,12 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
         } else {
             const size_t slow_cap = hj::probe_tiles(src.n);
             HJ_TRY(ensure_buf(c->slow, slow_cap * sizeof(unsigned)));
-            HJ_HIP(hj::launch_probe(table_dev(c), c->layout, src, q.out, q.kind == kProbeCount, (unsigned *)c->slow.p,
-                                    slow_cap, st));
+            if (q.kind == kProbeOuter)
+                HJ_HIP(hj::launch_probe_outer(table_dev(c), c->layout, src, q.out, q.null_pay, (unsigned *)c->slow.p,
+                                              slow_cap, st));
+            else
+                HJ_HIP(hj::launch_probe(table_dev(c), c->layout, src, q.out, q.kind == kProbeCount,
+                                        (unsigned *)c->slow.p, slow_cap, st));
         }
     } else {
         // (the work-map kernel zeroes the counter: no memset launch)
@@ -680,12 +685,16 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
             // the kernel: a function of (row width, size ratio, build-time sample)
             o.dup_flag = c->meta + 1;
             o.sample = c->meta + 2;
-            o.count_only = q.kind == kProbeCount;
+            o.count_only = q.kind == kProbeCount || (q.kind == kProbeOuter && q.out.cap == 0);
             o.stream = src.n >= 8 * c->n_build;
             HJ_RADIX(c, st, hj::radix_join(wide, c->plan, radix_work(c), r, bucket_set(c->sset), q.out, o, st));
             c->join_ran = true;
             c->join_wide = wide;
             c->join_stream = o.stream;
+            // outer: the S rows without a partner, over the same S partition, behind the pairs
+            if (q.kind == kProbeOuter)
+                HJ_RADIX(c, st, hj::radix_unmatched(wide, q.null_pay, c->plan, radix_work(c), r, bucket_set(c->sset),
+                                                    q.out, st));
         }
         trace("probe: joined", st, q.out.cap);
     }
@@ -724,6 +733,23 @@ int do_exists(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, void *out_
     q.in.src = src;
     q.out = hj::OutDev{out_key, out_s, cap, (unsigned long long *)d_count};
     q.kind = kind == HJ_EXISTS_ANTI ? kProbeAnti : kProbeSemi;
+    return run_probe(c, q, st);
+}
+
+// Probe-side outer join (hj_dev_probe_outer_*): do_probe's checks; out_cap == 0
+// with both outputs null is the count-only form.  Reads what an inner probe reads.
+int do_probe_outer(hj_ctx *c, int layout, const hj::SrcDev &src, unsigned long long null_pay, void *out_r, void *out_s,
+                   int64_t cap, uint64_t *d_count, hipStream_t st) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, "probe without a matching build");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
+    if (cap < 0 || (cap > 0 && (!out_r || !out_s)) || (cap == 0 && (out_r || out_s))) HJ_FAIL(HJ_ERR_ARG, "bad output");
+    ProbeReq q;
+    q.in.src = src;
+    q.out = hj::OutDev{out_r, out_s, cap, (unsigned long long *)d_count};
+    q.kind = kProbeOuter;
+    q.null_pay = null_pay;
     return run_probe(c, q, st);
 }
 
@@ -1701,6 +1727,28 @@ int hj_dev_exists_i32(hj_ctx *c, int kind, const int32_t *skey, int64_t n, int64
     if (row_base < 0 || row_base + n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids out of range");
     return do_exists(c, kNarrow, kind, src_col32(skey, n, row_base), out_key, out_s, out_cap, d_count,
                      (hipStream_t)stream);
+}
+
+// (the null context is reported before any other argument, as the header says)
+int hj_dev_probe_outer_i64(hj_ctx *c, const int64_t *skey, const int64_t *spay, int64_t n, int64_t null_pay,
+                           int64_t *out_r, int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    // (the count-only form reads no payload: any readable column stands in)
+    if (n > 0 && !spay && (out_cap != 0 || out_r || out_s)) HJ_FAIL(HJ_ERR_ARG, "null probe payload");
+    return do_probe_outer(c, kWide, src_cols64(skey, spay ? spay : skey, n), (unsigned long long)null_pay, out_r, out_s,
+                          out_cap, d_count, (hipStream_t)stream);
+}
+int hj_dev_probe_outer_tuples_i64(hj_ctx *c, const int64_t *tuples, int64_t n, int64_t null_pay, int64_t *out_r,
+                                  int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream) {
+    return do_probe_outer(c, kWide, src_packed(tuples, n), (unsigned long long)null_pay, out_r, out_s, out_cap, d_count,
+                          (hipStream_t)stream);
+}
+int hj_dev_probe_outer_i32(hj_ctx *c, const int32_t *skey, int64_t n, int64_t row_base, int32_t null_row,
+                           int32_t *out_r, int32_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (row_base < 0 || row_base + n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids out of range");
+    return do_probe_outer(c, kNarrow, src_col32(skey, n, row_base), (unsigned long long)(uint32_t)null_row, out_r,
+                          out_s, out_cap, d_count, (hipStream_t)stream);
 }
 
 int hj_dev_partition_i64(hj_ctx *c, const int64_t *key, const int64_t *pay, int64_t n, int nparts,

@@ -122,6 +122,11 @@ hipError_t launch_probe(const TableDev &t, int layout, const SrcDev &src, const 
 // general path, meta[1] untouched
 hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, bool anti,
                                hipStream_t st);
+// probe-side outer join over the global table: launch_probe's pairs plus
+// (null_pay, S payload) for every S row without a partner; out.cap == 0
+// counts only; slow / slow_cap as launch_probe's
+hipError_t launch_probe_outer(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
+                              unsigned long long null_pay, unsigned *slow, size_t slow_cap, hipStream_t st);
 
 // ---------------------------------------------------------------- radix join
 // (hj_radix.hip) partitions both relations by the top bits of the key hash
@@ -222,6 +227,12 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
 // the repeat flag.
 hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
                         const BucketSet &s, const OutDev &out, hipStream_t st);
+// The outer join's second stage, after radix_join over the same r and s (and
+// out): the S rows without a partner in r are appended behind the pairs as
+// (null_pay, S payload) -- radix_exists' anti probe whose work map leaves
+// out.counter as the join left it.  out.cap == 0 counts only.
+hipError_t radix_unmatched(bool wide, unsigned long long null_pay, const RadixPlan &pl, const RadixWork &ws,
+                           const BucketSet &r, const BucketSet &s, const OutDev &out, hipStream_t st);
 // Folded routing's send side: rows (int64 columns or packed tuples) grouped
 // by the top rbits (<= 9) of radix_hash into out_tuples, exact and contiguous
 // per bin, bins in order; counts[2^rbits] their sizes.  One EXACT partition

@@ -8,7 +8,8 @@
 //                                       -> k_probe<WRITE=true>: ILP slot
 //                                          reads, ballot-compacted output,
 //                                          one global cursor add per block
-// plus the exists probes (k_probe_exists), the radix partition used by the
+// plus the exists probes (k_probe_exists), the outer probe (k_probe_outer),
+// the radix partition used by the
 // multi-GPU exchange, the selection, the counter-based generators of the
 // benchmark inputs and the copy floors.
 //
@@ -16,10 +17,11 @@
 // independent, no warp-32 idioms.  Integer/byte work: no MFMA.
 //
 // Written once, used by several kernels / launchers:
-//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists)
+//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists, k_probe_outer)
 //   wave_incl_add    every wave prefix sum (hj_internal.h: DPP, no LDS round trips)
 //   with_layout_form the (layout, form) -> template-argument dispatch of the launchers
 //   probe_grid       the tile probes' grid and LDS bytes
+//   k_probe_slow     the general path of k_probe and (with the null value) of k_probe_outer
 //   cu_count         the CU count (hj_radix.hip)
 // k_probe and k_probe_exists still each spell out their row load, chain walk
 // and ballot compaction, and the three count kernels their block sum: as
@@ -106,6 +108,20 @@ __device__ __forceinline__ T pick(const T (&a)[N], int i) {   // static-index se
 #pragma unroll
     for (int j = 1; j < N; ++j) r = (i == j) ? a[j] : r;
     return r;
+}
+// The same select with the indices as template arguments, for k_probe_slow's
+// outer instantiations: under pick() the compiler keeps the writing general
+// path's K and P in scratch (144 B per lane, one indexed load per row); with
+// no loop index ever applied to the arrays they stay in registers.  The inner
+// instantiations keep pick(): their machine code is held as it was.
+template <int J, int N, typename T>
+__device__ __forceinline__ T pick_c(const T (&a)[N], int i) {
+    if constexpr (J == N - 1) {
+        return a[J];
+    } else {
+        const T r = pick_c<J + 1>(a, i);
+        return i == J ? a[J] : r;
+    }
 }
 
 // ------------------------------------------------------------------ init
@@ -397,9 +413,15 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
 
 // General path over the tiles k_probe handed over (slow[0 .. meta[3])):
 // persistent workgroups, one tile at a time.
-template <int L, int FORM, bool WRITE>
+// NULLV: empty (the inner join), or one unsigned long long -- k_probe_outer's
+// general path: a row whose walk ended without a match emits (null, S.pay).
+// A pack, not a flag plus an argument: the inner instantiations keep their
+// kernel arguments, and with them their machine code, as they were.
+template <int L, int FORM, bool WRITE, typename... NULLV>
 __global__ __launch_bounds__(kBlock) void k_probe_slow(TableDev t, SrcDev src, OutDev out, const unsigned *slow,
-                                                       unsigned long long slow_cap) {
+                                                       unsigned long long slow_cap, NULLV... null_pay) {
+    constexpr bool OUTER = sizeof...(NULLV) == 1;
+    static_assert(sizeof...(NULLV) <= 1, "at most the null value");
     using LY = Lay<L>;
     using slot_t = typename LY::slot_t;
     using out_t = typename LY::out_t;
@@ -452,28 +474,41 @@ __global__ __launch_bounds__(kBlock) void k_probe_slow(TableDev t, SrcDev src, O
 
         int it = -1;
         bool have = false;
+        [[maybe_unused]] bool hit = false;   // OUTER: the current row has matched
         unsigned long long k = 0, p = 0, hh = 0;
         while (true) {
             while (!have) {
                 if (++it >= kProbeItems) break;
-                if (!pick(V, it)) continue;
-                k = pick(K, it);
-                p = pick(P, it);
+                if constexpr (OUTER) {
+                    if (!pick_c<0>(V, it)) continue;
+                    k = pick_c<0>(K, it);
+                    p = pick_c<0>(P, it);
+                } else {
+                    if (!pick(V, it)) continue;
+                    k = pick(K, it);
+                    p = pick(P, it);
+                }
                 if (LY::null_key(k)) {   // wide: INT64_MIN probe key matches every side row
                     const unsigned long long ns = t.meta[0];
                     for (unsigned long long q = 0; q < ns; ++q) emit(t.side[q], p);
+                    if constexpr (OUTER)
+                        if (ns == 0ull) emit(null_pay..., p);
                     continue;
                 }
                 hh = slot_of(k, t.shift);
                 have = true;
+                if constexpr (OUTER) hit = false;
             }
             if (!have) break;
             const slot_t s = sl[hh];
             if (LY::empty(s)) {
+                if constexpr (OUTER)
+                    if (!hit) emit(null_pay..., p);
                 have = false;
             } else {
                 if (LY::key(s) == k) {
                     emit(LY::pay(s), p);
+                    if constexpr (OUTER) hit = true;
                     if (unique) have = false;
                 }
                 hh = (hh + 1) & t.mask;
@@ -603,6 +638,129 @@ __global__ __launch_bounds__(kBlock) void k_probe_exists(TableDev t, SrcDev src,
             }
         }
         __syncthreads();   // s_cw / st_base reused by the next tile
+    }
+}
+
+// ------------------------------------------------------------------ outer probe
+// Probe-side outer join (LEFT OUTER with S on the left): every pair of the
+// inner join, plus (null_pay, S.pay) for every S row without a partner.
+// k_probe's shape and its two paths -- 2048-row tiles, every row's first slot
+// load issued before any is resolved, TableView, one cursor add per tile; a
+// tile with an INT64_MIN probe key or (repeated build keys) a row with more
+// than one match goes to the general path, k_probe_slow with the null value,
+// which emits the null row when a walk ends without a match.
+// What the fast path does not need is k_probe's compaction: every valid row
+// of a tile that stays here emits exactly one element, (RP, P) or (null, P),
+// the valid rows are a prefix of the tile, so the tile's count is known from
+// src.n alone and row slot i of thread x writes at cursor + i * kBlock + x:
+// no ballots, no scan, whole-wave contiguous stores.  out.cap == 0 is the
+// count-only form (the walks still run when build keys repeat: they decide
+// which tiles leave).  The chain walks are k_probe's, statement for statement.
+template <int L, int FORM, bool LDS>
+__global__ __launch_bounds__(kBlock) void k_probe_outer(TableDev t, SrcDev src, OutDev out, unsigned *slow,
+                                                        unsigned long long slow_cap, unsigned long long null_pay) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    __shared__ unsigned long long st_base;
+    extern __shared__ ulonglong2 s_tab[];
+
+    const TableView<L, LDS> tab(t, s_tab);
+    const bool unique = (__hip_atomic_load(&t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull);
+    const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
+    // (as in k_probe: a tile handed on leaves by `continue` past the closing
+    // barrier, and nothing before the last `continue` touches st_base)
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long K[kProbeItems], P[kProbeItems];
+        bool V[kProbeItems];
+        bool has_null = false;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            Tuple tp{0ull, 0ull};
+            V[i] = probe_row<L, FORM>(src, q, i, tp);
+            K[i] = tp.k;
+            P[i] = tp.p;
+            has_null |= V[i] && LY::null_key(K[i]);
+        }
+        auto to_slow = [&]() {
+            if (threadIdx.x == 0) {
+                const unsigned long long j = atomicAdd(&t.meta[3], 1ull);
+                if (j < slow_cap) slow[j] = (unsigned)q;   // (sized so it always is; else k_probe_slow flags the count)
+            }
+        };
+        if (__syncthreads_or(has_null ? 1 : 0)) {
+            to_slow();
+            continue;
+        }
+        slot_t S[kProbeItems];
+        unsigned long long H[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            H[i] = slot_of(K[i], t.shift);
+            if (V[i]) S[i] = tab.at(H[i]);
+        }
+        unsigned found = 0;
+        unsigned long long RP[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            RP[i] = null_pay;
+            if (!V[i]) continue;
+            slot_t sv = S[i];
+            unsigned long long hh = H[i];
+            while (!LY::empty(sv) && LY::key(sv) != K[i]) {
+                hh = (hh + 1) & t.mask;
+                sv = tab.at(hh);
+            }
+            if (!LY::empty(sv)) {
+                found |= 1u << i;
+                RP[i] = LY::pay(sv);
+            }
+        }
+        if (!unique) {
+            // repeated build keys: a matched row walks on to EMPTY; a second
+            // copy of its key sends the tile to the general path
+            bool multi = false;
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i) {
+                if (!((found >> i) & 1u)) continue;
+                unsigned long long hh = slot_of(K[i], t.shift);
+                slot_t sv = tab.at(hh);
+                while (!LY::empty(sv) && LY::key(sv) != K[i]) {   // (back to the first copy)
+                    hh = (hh + 1) & t.mask;
+                    sv = tab.at(hh);
+                }
+                hh = (hh + 1) & t.mask;
+                sv = tab.at(hh);
+                while (!LY::empty(sv) && !multi) {
+                    multi = LY::key(sv) == K[i];
+                    hh = (hh + 1) & t.mask;
+                    sv = tab.at(hh);
+                }
+            }
+            if (__syncthreads_or(multi ? 1 : 0)) {
+                to_slow();
+                continue;
+            }
+        }
+        // the tile's valid rows: [q * kProbeTile, min(src.n, (q + 1) * kProbeTile)), never none
+        const unsigned long long left = (unsigned long long)src.n - q * kProbeTile;
+        const unsigned long long rows = left < (unsigned long long)kProbeTile ? left : (unsigned long long)kProbeTile;
+        if (threadIdx.x == 0) st_base = atomicAdd(out.counter, rows);
+        if (out.cap != 0) {   // (uniform)
+            __syncthreads();
+            out_t *orr = (out_t *)out.r;
+            out_t *oss = (out_t *)out.s;
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i) {
+                if (!V[i]) continue;
+                const unsigned long long gi = st_base + (unsigned long long)(i * kBlock) + threadIdx.x;
+                if (gi < (unsigned long long)out.cap) {
+                    orr[gi] = (out_t)RP[i];
+                    oss[gi] = (out_t)P[i];
+                }
+            }
+            __syncthreads();   // st_base reused by the next tile
+        }
     }
 }
 
@@ -1133,6 +1291,28 @@ hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src,
         constexpr int L = decltype(l)::value, F = decltype(f)::value;
         const auto k = pg.lds ? k_probe_exists<L, F, true> : k_probe_exists<L, F, false>;
         hipLaunchKernelGGL(k, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, a);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_probe_outer(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
+                              unsigned long long null_pay, unsigned *slow, size_t slow_cap, hipStream_t st) {
+    if (src.n <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(&t.meta[3], 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+    const unsigned long long cap = slow_cap;
+    const ProbeGrid pg = probe_grid(t, layout, src.n);
+    // the general path's persistent workgroups, as launch_probe's
+    const unsigned tiles = grid_for(src.n, kProbeTile), most = (unsigned)(cu_count() * 8);
+    const unsigned gs = tiles < most ? tiles : most;
+    return with_layout_form(layout, src.form, [&](auto l, auto f) {
+        constexpr int L = decltype(l)::value, F = decltype(f)::value;
+        const auto fast = pg.lds ? k_probe_outer<L, F, true> : k_probe_outer<L, F, false>;
+        const auto rest = out.cap == 0 ? k_probe_slow<L, F, false, unsigned long long>
+                                       : k_probe_slow<L, F, true, unsigned long long>;
+        hipLaunchKernelGGL(fast, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, slow, cap,
+                           null_pay);
+        hipLaunchKernelGGL(rest, dim3(gs), dim3(kBlock), 0, st, t, src, out, (const unsigned *)slow, cap, null_pay);
         return hipGetLastError();
     });
 }

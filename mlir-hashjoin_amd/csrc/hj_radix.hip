@@ -3070,8 +3070,14 @@ constexpr int kExistsTableLog = 13;
 // 1024 threads x 5 build keys + 3 probe rows, 8 waves per SIMD: both
 // workgroups a CU's LDS admits are resident (<= 64 VGPRs)
 constexpr int kExistsNT = 1024, kExistsSI = 3, kExistsWPS = 8;
-template <bool WIDE, int NT, int SI, int WPS>
-__global__ __launch_bounds__(NT, WPS) void k_join_exists(JoinArgs a, unsigned anti) {
+// NULLV: empty, or one u64 -- the outer join's unmatched-rows stage (an anti
+// probe behind radix_join's pairs: a.counter is NOT zeroed by its work map,
+// so the cursor goes on behind them): out_r receives that null value instead
+// of the S key.  A pack, so the exists instantiations keep their kernel
+// arguments and their machine code.
+template <bool WIDE, int NT, int SI, int WPS, typename... NULLV>
+__global__ __launch_bounds__(NT, WPS) void k_join_exists(JoinArgs a, unsigned anti, NULLV... null_pay) {
+    static_assert(sizeof...(NULLV) <= 1, "at most the null value");
     typedef Row<WIDE> R;
     typedef typename R::T T;
     typedef typename std::conditional<WIDE, u64, unsigned>::type PT;   // output element
@@ -3215,7 +3221,8 @@ __global__ __launch_bounds__(NT, WPS) void k_join_exists(JoinArgs a, unsigned an
                 const u64 gi = s_base + s_cw[i * NW + wave] + lpre[i];
                 if (gi < (u64)a.cap) {
                     st_s<kNtJoinSt>(oss + gi, (PT)R::pay(sv[i]));
-                    if (okk) st_s<kNtJoinSt>(okk + gi, (PT)R::key(sv[i]));
+                    if constexpr (sizeof...(NULLV) == 1) st_s<kNtJoinSt>(okk + gi, (PT)(null_pay, ...));
+                    else if (okk) st_s<kNtJoinSt>(okk + gi, (PT)R::key(sv[i]));
                 }
             }
             __syncthreads();   // s_cw / s_base reused by the next sub-chunk
@@ -3908,8 +3915,11 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
     return hipGetLastError();
 }
 
-hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
-                        const BucketSet &s, const OutDev &out, hipStream_t st) {
+namespace {
+// k_join_exists over a work map of its own.  null_pay: the outer join's
+// unmatched-rows stage (radix_unmatched), else the plain semi / anti probe.
+hipError_t exists_stage(bool wide, bool anti, const unsigned long long *null_pay, const RadixPlan &pl,
+                        const RadixWork &ws, const BucketSet &r, const BucketSet &s, const OutDev &out, hipStream_t st) {
     const int P = 1 << pl.total_bits;
     const unsigned pg = (unsigned)(2 * cu_count());   // two 64-KiB tables per CU
     WorkMapSpec m;
@@ -3918,20 +3928,46 @@ hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWo
     // semi: partitions without build rows have nothing to emit; anti: those S
     // rows are exactly the ones to emit, so every non-empty S partition is live
     m.r_gates = !anti;
-    m.counter = out.counter;
+    // the unmatched-rows stage appends behind the pairs: the counter stays
+    m.counter = null_pay ? nullptr : out.counter;
     const WorkMap w = work_map(pl, P, ws, r, &s, m, st);
     if (!w.items) return hipErrorInvalidValue;
     JoinArgs a = join_args(wide, pl, r, s, P, ws, out, nullptr, nullptr);
     a.tshift = 64 - pl.skip - pl.total_bits - kExistsTableLog;
     const unsigned grid = w.items < pg ? w.items : pg;
     const unsigned kind = anti ? 1u : 0u;
-    if (wide)
-        hipLaunchKernelGGL((k_join_exists<true, kExistsNT, kExistsSI, kExistsWPS>), dim3(grid), dim3(kExistsNT), 0, st,
-                           a, kind);
-    else
-        hipLaunchKernelGGL((k_join_exists<false, kExistsNT, kExistsSI, kExistsWPS>), dim3(grid), dim3(kExistsNT), 0, st,
-                           a, kind);
+    auto launch = [&](auto w_, auto... nullv) {
+        constexpr bool W = decltype(w_)::value;
+        hipLaunchKernelGGL((k_join_exists<W, kExistsNT, kExistsSI, kExistsWPS, decltype(nullv)...>), dim3(grid),
+                           dim3(kExistsNT), 0, st, a, kind, nullv...);
+    };
+    if (null_pay) {
+        const u64 nv = *null_pay;
+        if (wide) launch(std::true_type{}, nv);
+        else launch(std::false_type{}, nv);
+    } else {
+        if (wide) launch(std::true_type{});
+        else launch(std::false_type{});
+    }
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
+                        const BucketSet &s, const OutDev &out, hipStream_t st) {
+    return exists_stage(wide, anti, nullptr, pl, ws, r, s, out, st);
+}
+
+// The outer join's second stage.  Its work map is built in the work area
+// radix_join's kernels have finished with (stream order).  The area covers it: the map takes P + 1 starts, one
+// owner word and one descriptor per item and no deferred lists, the items are
+// at most s.max_runs / (kJoinSub x the exists sub-chunk) + P + 1, and
+// radix_join_items counts with the smallest sub-chunk of any kernel (its
+// static_assert names the exists shape), which radix_work_words and the
+// descriptor buffer are sized from.
+hipError_t radix_unmatched(bool wide, unsigned long long null_pay, const RadixPlan &pl, const RadixWork &ws,
+                           const BucketSet &r, const BucketSet &s, const OutDev &out, hipStream_t st) {
+    return exists_stage(wide, true, &null_pay, pl, ws, r, s, out, st);
 }
 
 // radix_detect's deferred partitions: rows[1] += the rows of every listed

@@ -83,6 +83,9 @@ def _load():
         "hj_dev_exists_i64": (_int, [_vp, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_exists_tuples_i64": (_int, [_vp, _int, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_exists_i32": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_probe_outer_i64": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_probe_outer_tuples_i64": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_probe_outer_i32": (_int, [_vp, _vp, _i64, _i64, C.c_int32, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_partition_i64": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_dev_partition_tuples_i64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_partition_of": (_int, [_i64, _int]),

@@ -302,6 +302,84 @@ class HashJoin:
         """As semi_join, for the S rows whose key R does not hold."""
         return self._exists_join("anti", rkey, skey, spay, rpay, with_keys, capacity, stream)
 
+    # ---- probe-side outer join (hj.h "Probe-side outer join")
+    def probe_outer(self, skey, spay=None, out_r=None, out_s=None, null=-1, count=None, row_base=0, stream=None):
+        """LEFT OUTER probe of the built table, S on the left: every pair of the
+        inner join plus (null, S payload) for every S row without a partner.
+        Writes min(M, cap) rows into out_r / out_s (i32: row ids, row_base +
+        row on the S side); `count` (int64 device tensor) receives M >= |S|.
+        `null` is written verbatim.  out_r and out_s None is the count-only
+        form.  Returns count."""
+        _need_cuda(skey, spay, out_r, out_s)
+        st = _stream(self.device, stream)
+        count = self._count if count is None else count
+        if (out_r is None) != (out_s is None):
+            raise ValueError("outer probe needs both outputs, or neither to count")
+        cap = 0 if out_r is None else out_r.numel()
+        if out_s is not None and out_s.numel() != cap:
+            raise ValueError("output columns differ in length")
+        for o in (out_r, out_s):
+            if o is not None and o.dtype != skey.dtype:
+                raise ValueError("outer outputs carry the probe key's dtype")
+        if skey.dtype == torch.int64:
+            if spay is None and out_s is not None:
+                raise ValueError("int64 probe needs an int64 payload column")
+            if spay is not None and (spay.dtype != torch.int64 or spay.numel() != skey.numel()):
+                raise ValueError("int64 probe needs an int64 payload column of the same length")
+            check(lib.hj_dev_probe_outer_i64(self._ctx, _ptr(skey), _ptr(spay), skey.numel(), int(null), _ptr(out_r),
+                                             _ptr(out_s), cap, _ptr(count), st), "hj_dev_probe_outer_i64")
+        elif skey.dtype == torch.int32:
+            if spay is not None:
+                raise ValueError("i32 joins carry row ids, not payloads (reference types)")
+            check(lib.hj_dev_probe_outer_i32(self._ctx, _ptr(skey), skey.numel(), int(row_base), int(null),
+                                             _ptr(out_r), _ptr(out_s), cap, _ptr(count), st),
+                  "hj_dev_probe_outer_i32")
+        else:
+            raise TypeError("keys must be int32 or int64")
+        return count
+
+    def probe_outer_tuples(self, tuples, out_r, out_s, null=-1, count=None, stream=None):
+        """probe_outer over packed (n, 2) int64 {key, payload} rows."""
+        _need_cuda(tuples, out_r, out_s)
+        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
+            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        if (out_r is None) != (out_s is None) or (out_r is not None and out_r.numel() != out_s.numel()):
+            raise ValueError("outer probe needs two outputs of one length, or neither to count")
+        count = self._count if count is None else count
+        cap = 0 if out_r is None else out_r.numel()
+        check(lib.hj_dev_probe_outer_tuples_i64(self._ctx, _ptr(tuples), tuples.shape[0], int(null), _ptr(out_r),
+                                                _ptr(out_s), cap, _ptr(count), _stream(self.device, stream)),
+              "hj_dev_probe_outer_tuples_i64")
+        return count
+
+    def count_outer(self, skey, stream=None, sync=True):
+        """M of the outer probe: the inner join's pairs plus the S rows without a partner."""
+        cnt = self.probe_outer(skey, stream=stream)
+        return int(cnt.item()) if sync else cnt
+
+    def outer_join(self, rkey, rpay, skey, spay=None, null=-1, capacity=None, stream=None):
+        """join() keeping every S row: build R, then the outer probe into an
+        output sized |S| rows (exact when no S row has two partners), or
+        `capacity`, re-probing once at the exact M if that was too small.
+        Returns (R payloads or `null`, S payloads); row ids for int32 keys."""
+        self.probe_hint(skey.numel())
+        try:
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+        dt = torch.int64 if rkey.dtype == torch.int64 else torch.int32
+        cap = max(1, skey.numel() if capacity is None else int(capacity))
+        for _ in range(2):
+            out_r = torch.empty(cap, dtype=dt, device=self.device)
+            out_s = torch.empty(cap, dtype=dt, device=self.device)
+            m = int(self.probe_outer(skey, spay, out_r, out_s, null=null, stream=stream).item())
+            if m < 0:   # bit 63: an internal work list overflowed (hj.h)
+                raise RuntimeError("hash join: internal work list overflow (count flagged)")
+            if m <= cap:
+                return out_r[:m], out_s[:m]
+            cap = m
+        raise RuntimeError("outer join output did not fit after resizing")
+
     # ---- folded routing (hj.h "Folded routing"): the owner and the
     # receiver's first radix-pass bin from one hash, so receivers skip a pass
     @staticmethod
