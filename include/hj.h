@@ -131,7 +131,7 @@ int hj_ctx_last_timing_ex(hj_ctx *ctx, float ms[8]);
 int hj_ctx_timing_accumulate(hj_ctx *ctx, int enable);
 int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 /* RADIX: the join kernel of the last probe, whichever entry point ran it
- * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_count_*, hj_dev_exists_*, and after a routed build
+ * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_probe_full_*, hj_dev_count_*, hj_dev_exists_*, and after a routed build
  * hj_dev_probe_routed_i64 too).  A pure function of the row
  * width, the probe / build size ratio (>= 8: the probe-heavy shape) and the
  * build side's repeated keys, sampled at build time over up to 64 partitions
@@ -255,6 +255,60 @@ int hj_dev_probe_outer_tuples_i64(hj_ctx *ctx, const int64_t *tuples, int64_t n,
                                   int64_t *out_r, int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
 int hj_dev_probe_outer_i32(hj_ctx *ctx, const int32_t *skey, int64_t n, int64_t row_base, int32_t null_row,
                            int32_t *out_r, int32_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
+
+/* Build-side and full outer join (RIGHT OUTER / FULL OUTER with the probe
+ * relation S on the left) over the table an ordinary hj_dev_build_* left: the
+ * kinds that keep the BUILD relation's rows, so the smaller relation can stay
+ * the build side and a full outer join needs one build.  The result is the
+ * multiset
+ *   {(R.pay[i], S.pay[j]) : R.key[i] == S.key[j]}            (the inner join)
+ *   u {(R.pay[i], null_s) : no j has S.key[j] == R.key[i]}    (R's null rows)
+ *   u {(null_r, S.pay[j]) : no i has R.key[i] == S.key[j]}    (S's null rows, HJ_OUTER_FULL only);
+ * M is the sum of the three sizes.  Row order is unspecified and the three
+ * kinds of rows may interleave.  null_r and null_s (i32: null_row_r,
+ * null_row_s; row ids as hj_dev_probe_i32's) are written verbatim; null_r is
+ * ignored for HJ_OUTER_BUILD.
+ * "Without a partner" refers to the S of THIS call: nothing carries over
+ * between calls.  Each unmatched R row comes out once; every copy of a
+ * repeated build key is a row of its own, and all copies of a key that some
+ * S row holds are matched.  INT64_MIN is a key like any other: INT64_MIN
+ * build rows are unmatched iff S holds no INT64_MIN key, and (FULL) INT64_MIN
+ * probe rows are null rows iff R holds none.  R empty: BUILD gives M = 0,
+ * FULL every S row as a null row.  S empty: every R row as (pay, null_s).
+ * d_count = the exact M even when M > out_cap: rows past out_cap are dropped
+ * (which ones is unspecified) and nothing is written at or past index out_cap
+ * in either output; bit 63 as above.  out_cap == 0 with both outputs NULL is
+ * the count-only form (spay may be NULL then).
+ * Errors in hj_dev_probe_outer_*'s order: a null context first, then a kind
+ * other than the two (both HJ_ERR_ARG); no build of that layout
+ * (HJ_ERR_STATE); a null count pointer, a bad relation, bad outputs
+ * (HJ_ERR_ARG).
+ * Asynchronous on the stream, kernels and memsets only once hj_ctx_reserve /
+ * hj_ctx_reserve_probe sized the workspace (graph-capturable).  The strategy
+ * is chosen exactly as for hj_dev_probe_* (the AUTO dual build included) and
+ * hj_ctx_strategy_used reports it.  The probe timing covers the whole call;
+ * RADIX: [4] is the one partition of S, [5] everything after it;
+ * hj_ctx_join_kernel reports the kernel that produced the pairs.  GLOBAL: a
+ * mark bitmap (one bit per slot, allocated with the table) is cleared, set
+ * where the probe finds its matches and scanned inside the call.  The table, R's partition, the side
+ * list and the "build keys repeat" flag are left as hj_dev_probe_* of the
+ * same S leaves them: inner, semi, anti, outer, build and full probes of one
+ * build may follow each other in any order, each returns what it returned
+ * before, and hj_ctx_build_has_duplicates keeps its answer.
+ * Valid after hj_dev_build_routed_i64 too, over unrouted rows.  Routed
+ * bin-range probes (hj_dev_probe_routed_i64) have no full form: an R row's
+ * partner may lie in a bin that has not arrived. */
+#define HJ_OUTER_BUILD 1 /* inner pairs + R rows without a partner (RIGHT OUTER, S on the left) */
+#define HJ_OUTER_FULL 2  /* inner pairs + S rows without a partner + R rows without a partner */
+int hj_dev_probe_full_i64(hj_ctx *ctx, int kind, const int64_t *skey, const int64_t *spay, int64_t n, int64_t null_r,
+                          int64_t null_s, int64_t *out_r, int64_t *out_s, int64_t out_cap, uint64_t *d_count,
+                          void *stream);
+int hj_dev_probe_full_tuples_i64(hj_ctx *ctx, int kind, const int64_t *tuples, int64_t n, int64_t null_r,
+                                 int64_t null_s, int64_t *out_r, int64_t *out_s, int64_t out_cap, uint64_t *d_count,
+                                 void *stream);
+int hj_dev_probe_full_i32(hj_ctx *ctx, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t null_row_r,
+                          int32_t null_row_s, int32_t *out_r, int32_t *out_s, int64_t out_cap, uint64_t *d_count,
+                          void *stream);
 
 /* Radix partition of rows into nparts (1..8192) groups by a key hash independent of
  * the table's slot hash: out_tuples (2*n int64) receives packed {key, pay}

@@ -129,6 +129,8 @@ struct hj_ctx {
     size_t table_bytes = 0;
     unsigned long long *side = nullptr;   // wide-layout side list (INT64_MIN keys)
     size_t side_rows = 0;
+    unsigned *marks = nullptr;            // build-side outer probes: one bit per slot + the INT64_MIN word (hj::mark_words)
+    size_t mark_words = 0;
     unsigned long long *meta = nullptr;   // [0] side count, [1] dup flag, [8..] partition cursors
     size_t meta_words = 0;
     // current table
@@ -255,6 +257,15 @@ int ensure_table(hj_ctx *c, int64_t n, int layout) {
         const size_t rows = (size_t)(n > 0 ? n : 1);
         if (hipMalloc(&c->side, rows * 8) != hipSuccess) HJ_FAIL(HJ_ERR_NOMEM, "hipMalloc side list");
         c->side_rows = rows;
+    }
+    // (with the table, so a reserved context's build-side outer probe allocates nothing)
+    const size_t mw = hj::mark_words(1ull << bits);
+    if (c->mark_words < mw) {
+        if (c->marks) HJ_HIP(hipFree(c->marks));
+        c->marks = nullptr;
+        c->mark_words = 0;
+        if (hipMalloc(&c->marks, mw * sizeof(unsigned)) != hipSuccess) HJ_FAIL(HJ_ERR_NOMEM, "hipMalloc mark bitmap");
+        c->mark_words = mw;
     }
     return ensure_meta(c, 64);
 }
@@ -629,19 +640,23 @@ int do_build(hj_ctx *c, int layout, const hj::SrcDev &src, hipStream_t st) {
 }
 
 // One probe of the current build, after the entry point's argument checks.
-enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter };
+enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter, kProbeBuild, kProbeFull };
 struct ProbeReq {
     RadixSrc in;       // S; routed: bins [bin0, bin0 + in.nbins) of the build's first pass
     int bin0 = 0;
-    hj::OutDev out;    // inner, outer: R and S payloads; semi / anti: S keys (may be null) and S payloads
+    hj::OutDev out;    // inner, outer, build, full: R and S payloads; semi / anti: S keys (may be null) and S payloads
     ProbeKind kind = kProbeInner;
-    unsigned long long null_pay = 0;   // outer: the R payload of an S row without a partner (out.cap == 0 counts only)
+    unsigned long long null_pay = 0;   // outer, full: the R payload of an S row without a partner (out.cap == 0 counts only)
+    unsigned long long null_s = 0;     // build, full: the S payload of an R row without a partner
 };
 
 int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
     HJ_TRY(set_device(c));
     const hj::SrcDev &src = q.in.src;
     const bool exists = q.kind == kProbeSemi || q.kind == kProbeAnti;
+    // outer / full: S's null rows behind the pairs; build / full: then R's
+    const bool s_nulls = q.kind == kProbeOuter || q.kind == kProbeFull;
+    const bool r_nulls = q.kind == kProbeBuild || q.kind == kProbeFull;
     const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
     c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
     c->join_ran = c->exists_ran = false;
@@ -653,12 +668,20 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
         } else {
             const size_t slow_cap = hj::probe_tiles(src.n);
             HJ_TRY(ensure_buf(c->slow, slow_cap * sizeof(unsigned)));
-            if (q.kind == kProbeOuter)
+            // build / full: stage 1 marks the slots its fast path matched (a bitmap cleared per call)
+            unsigned *marks = r_nulls ? c->marks : nullptr;
+            if (r_nulls) HJ_HIP(hj::launch_marks_clear(table_dev(c), marks, st));
+            if (s_nulls)
                 HJ_HIP(hj::launch_probe_outer(table_dev(c), c->layout, src, q.out, q.null_pay, (unsigned *)c->slow.p,
-                                              slow_cap, st));
+                                              slow_cap, st, marks));
             else
-                HJ_HIP(hj::launch_probe(table_dev(c), c->layout, src, q.out, q.kind == kProbeCount,
-                                        (unsigned *)c->slow.p, slow_cap, st));
+                HJ_HIP(hj::launch_probe(table_dev(c), c->layout, src, q.out,
+                                        q.kind == kProbeCount || (r_nulls && q.out.cap == 0), (unsigned *)c->slow.p,
+                                        slow_cap, st, marks));
+            // then the handed-over tiles are marked, and the unmarked rows emitted behind stage 1's
+            if (r_nulls)
+                HJ_HIP(hj::launch_unmatched_build(table_dev(c), c->layout, src, q.out, q.null_s, marks,
+                                                  (const unsigned *)c->slow.p, slow_cap, st));
         }
     } else {
         // (the work-map kernel zeroes the counter: no memset launch)
@@ -685,16 +708,21 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
             // the kernel: a function of (row width, size ratio, build-time sample)
             o.dup_flag = c->meta + 1;
             o.sample = c->meta + 2;
-            o.count_only = q.kind == kProbeCount || (q.kind == kProbeOuter && q.out.cap == 0);
+            o.count_only = q.kind == kProbeCount || ((s_nulls || r_nulls) && q.out.cap == 0);
             o.stream = src.n >= 8 * c->n_build;
             HJ_RADIX(c, st, hj::radix_join(wide, c->plan, radix_work(c), r, bucket_set(c->sset), q.out, o, st));
             c->join_ran = true;
             c->join_wide = wide;
             c->join_stream = o.stream;
             // outer: the S rows without a partner, over the same S partition, behind the pairs
-            if (q.kind == kProbeOuter)
+            if (s_nulls)
                 HJ_RADIX(c, st, hj::radix_unmatched(wide, q.null_pay, c->plan, radix_work(c), r, bucket_set(c->sset),
                                                     q.out, st));
+            // build / full: the R rows without a partner, the same stage with the bucket sets exchanged
+            // (never after a routed bin-range probe: r is the whole of R's partition here)
+            if (r_nulls)
+                HJ_RADIX(c, st, hj::radix_unmatched_build(wide, q.null_s, c->plan, radix_work(c), r,
+                                                          bucket_set(c->sset), q.out, st));
         }
         trace("probe: joined", st, q.out.cap);
     }
@@ -750,6 +778,29 @@ int do_probe_outer(hj_ctx *c, int layout, const hj::SrcDev &src, unsigned long l
     q.out = hj::OutDev{out_r, out_s, cap, (unsigned long long *)d_count};
     q.kind = kProbeOuter;
     q.null_pay = null_pay;
+    return run_probe(c, q, st);
+}
+
+// Build-side and full outer join (hj_dev_probe_full_*): do_probe_outer's checks
+// behind the kind's; rel_err: the entry point found its relation bad (reported
+// in do_probe_outer's order, after the state and the count pointer).
+int do_probe_full(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, const char *rel_err,
+                  unsigned long long null_r, unsigned long long null_s, void *out_r, void *out_s, int64_t cap,
+                  uint64_t *d_count, hipStream_t st) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (kind != HJ_OUTER_BUILD && kind != HJ_OUTER_FULL)
+        HJ_FAIL(HJ_ERR_ARG, "kind must be HJ_OUTER_BUILD or HJ_OUTER_FULL");
+    if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, "probe without a matching build");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (rel_err) HJ_FAIL(HJ_ERR_ARG, rel_err);
+    if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
+    if (cap < 0 || (cap > 0 && (!out_r || !out_s)) || (cap == 0 && (out_r || out_s))) HJ_FAIL(HJ_ERR_ARG, "bad output");
+    ProbeReq q;
+    q.in.src = src;
+    q.out = hj::OutDev{out_r, out_s, cap, (unsigned long long *)d_count};
+    q.kind = kind == HJ_OUTER_FULL ? kProbeFull : kProbeBuild;
+    q.null_pay = null_r;
+    q.null_s = null_s;
     return run_probe(c, q, st);
 }
 
@@ -1505,6 +1556,7 @@ void hj_ctx_destroy(hj_ctx *c) {
     (void)hipDeviceSynchronize();
     if (c->table) (void)hipFree(c->table);
     if (c->side) (void)hipFree(c->side);
+    if (c->marks) (void)hipFree(c->marks);
     if (c->meta) (void)hipFree(c->meta);
     if (c->dcount) (void)hipFree(c->dcount);
     for (int i = 0; i < hj_ctx::kDbufs; ++i)
@@ -1749,6 +1801,29 @@ int hj_dev_probe_outer_i32(hj_ctx *c, const int32_t *skey, int64_t n, int64_t ro
     if (row_base < 0 || row_base + n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids out of range");
     return do_probe_outer(c, kNarrow, src_col32(skey, n, row_base), (unsigned long long)(uint32_t)null_row, out_r,
                           out_s, out_cap, d_count, (hipStream_t)stream);
+}
+
+int hj_dev_probe_full_i64(hj_ctx *c, int kind, const int64_t *skey, const int64_t *spay, int64_t n, int64_t null_r,
+                          int64_t null_s, int64_t *out_r, int64_t *out_s, int64_t out_cap, uint64_t *d_count,
+                          void *stream) {
+    // (the count-only form reads no payload: any readable column stands in)
+    const bool no_pay = n > 0 && !spay && (out_cap != 0 || out_r || out_s);
+    return do_probe_full(c, kWide, kind, src_cols64(skey, spay ? spay : skey, n), no_pay ? "null probe payload" : nullptr,
+                         (unsigned long long)null_r, (unsigned long long)null_s, out_r, out_s, out_cap, d_count,
+                         (hipStream_t)stream);
+}
+int hj_dev_probe_full_tuples_i64(hj_ctx *c, int kind, const int64_t *tuples, int64_t n, int64_t null_r, int64_t null_s,
+                                 int64_t *out_r, int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream) {
+    return do_probe_full(c, kWide, kind, src_packed(tuples, n), nullptr, (unsigned long long)null_r,
+                         (unsigned long long)null_s, out_r, out_s, out_cap, d_count, (hipStream_t)stream);
+}
+int hj_dev_probe_full_i32(hj_ctx *c, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t null_row_r,
+                          int32_t null_row_s, int32_t *out_r, int32_t *out_s, int64_t out_cap, uint64_t *d_count,
+                          void *stream) {
+    const bool bad_ids = row_base < 0 || row_base + n > 0x7fffffffll;
+    return do_probe_full(c, kNarrow, kind, src_col32(skey, n, bad_ids ? 0 : row_base),
+                         bad_ids ? "i32 row ids out of range" : nullptr, (unsigned long long)(uint32_t)null_row_r,
+                         (unsigned long long)(uint32_t)null_row_s, out_r, out_s, out_cap, d_count, (hipStream_t)stream);
 }
 
 int hj_dev_partition_i64(hj_ctx *c, const int64_t *key, const int64_t *pay, int64_t n, int nparts,

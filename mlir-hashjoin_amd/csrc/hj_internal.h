@@ -115,8 +115,11 @@ hipError_t launch_build(const TableDev &t, int layout, const SrcDev &src, hipStr
 size_t probe_tiles(long long n);
 // slow_cap: entries of `slow` (tiles beyond it are never written; the
 // callers size it from probe_tiles so that cannot happen)
+// marks (launch_probe, launch_probe_outer): non-null for the build-side outer
+// probes -- tiles that stay on the fast path set the bits of the slots they
+// matched (launch_marks_clear before, launch_unmatched_build after)
 hipError_t launch_probe(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
-                        bool count_only, unsigned *slow, size_t slow_cap, hipStream_t st);
+                        bool count_only, unsigned *slow, size_t slow_cap, hipStream_t st, unsigned *marks = nullptr);
 // semi- (anti: anti-) join probe of the global table: out.r = S keys (may be
 // null), out.s = S payloads, out.cap == 0 counts only; one launch, no
 // general path, meta[1] untouched
@@ -126,7 +129,20 @@ hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src,
 // (null_pay, S payload) for every S row without a partner; out.cap == 0
 // counts only; slow / slow_cap as launch_probe's
 hipError_t launch_probe_outer(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
-                              unsigned long long null_pay, unsigned *slow, size_t slow_cap, hipStream_t st);
+                              unsigned long long null_pay, unsigned *slow, size_t slow_cap, hipStream_t st,
+                              unsigned *marks = nullptr);
+// build-side outer join over the global table: launch_marks_clear, then
+// launch_probe (RIGHT OUTER) or launch_probe_outer (FULL OUTER) with marks,
+// then launch_unmatched_build of the same src, out, slow and slow_cap: the
+// tiles stage 1 handed to the general path are marked too, and the R rows no
+// row of src matches are appended as (R payload, null_s).  marks:
+// mark_words(slots) 32-bit words: one bit per slot, then the "src held
+// INT64_MIN" word.  out.cap == 0 counts only.
+size_t mark_words(unsigned long long slots);
+hipError_t launch_marks_clear(const TableDev &t, unsigned *marks, hipStream_t st);
+hipError_t launch_unmatched_build(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
+                                  unsigned long long null_s, unsigned *marks, const unsigned *slow, size_t slow_cap,
+                                  hipStream_t st);
 
 // ---------------------------------------------------------------- radix join
 // (hj_radix.hip) partitions both relations by the top bits of the key hash
@@ -233,6 +249,15 @@ hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWo
 // out.counter as the join left it.  out.cap == 0 counts only.
 hipError_t radix_unmatched(bool wide, unsigned long long null_pay, const RadixPlan &pl, const RadixWork &ws,
                            const BucketSet &r, const BucketSet &s, const OutDev &out, hipStream_t st);
+// The build-side outer join's last stage, after radix_join (and, FULL OUTER,
+// radix_unmatched) over the same r, s and out: the R rows without a partner
+// in s are appended as (R payload, null_s).  The same anti stage with the two
+// bucket sets exchanged -- s's keys go into the LDS table, r's rows are
+// tested and emitted -- over a work map that cuts R's runs into items and
+// keeps every non-empty R partition live, S rows or not.  ws.work_start /
+// ws.work_desc must cover r.max_runs too (every build sizes them for it).
+hipError_t radix_unmatched_build(bool wide, unsigned long long null_s, const RadixPlan &pl, const RadixWork &ws,
+                                 const BucketSet &r, const BucketSet &s, const OutDev &out, hipStream_t st);
 // Folded routing's send side: rows (int64 columns or packed tuples) grouped
 // by the top rbits (<= 9) of radix_hash into out_tuples, exact and contiguous
 // per bin, bins in order; counts[2^rbits] their sizes.  One EXACT partition

@@ -9,6 +9,7 @@
 //                                          reads, ballot-compacted output,
 //                                          one global cursor add per block
 // plus the exists probes (k_probe_exists), the outer probe (k_probe_outer),
+// the build-side outer stages (k_probe_mark, k_emit_unmatched),
 // the radix partition used by the
 // multi-GPU exchange, the selection, the counter-based generators of the
 // benchmark inputs and the copy floors.
@@ -237,6 +238,33 @@ struct TableView {
     __device__ __forceinline__ slot_t at(unsigned long long h) const { return sl[h]; }
 };
 
+// ------------------------------------------------------------------ slot marks
+// The build-side outer probes' mark bitmap (one bit per slot, "some S row of
+// this call matched it"; see "build-side outer probe" below).  mark_first
+// sets slot h's bit and says whether this call was the first to: the word is
+// read before the atomic OR, which is skipped when the bit is already set --
+// at PK-FK fan-in all S rows of a build key but the first issue no atomic.
+__device__ __forceinline__ bool mark_first(unsigned *marks, unsigned long long h) {
+    unsigned *w = marks + (h >> 5);
+    const unsigned bit = 1u << (unsigned)(h & 31ull);
+    if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) return false;
+    return !(atomicOr(w, bit) & bit);
+}
+// Marks the matched slots MH[i] (bits of `found`) of a tile the fast path
+// keeps: the 8 words are read before any atomic is issued.
+template <int N>
+__device__ __forceinline__ void mark_found(unsigned *marks, unsigned found, const unsigned long long (&MH)[N]) {
+    unsigned W[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        if ((found >> i) & 1u) W[i] = __hip_atomic_load(marks + (MH[i] >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const unsigned bit = 1u << (unsigned)(MH[i] & 31ull);
+        if (((found >> i) & 1u) && !(W[i] & bit)) atomicOr(marks + (MH[i] >> 5), bit);
+    }
+}
+
 // ------------------------------------------------------------------ probe
 // count (join_v1.mlir:288-425, join_v2.mlir:311-439) and probe
 // (join_v1.mlir:436-521, join_v2.mlir:450-604) in one kernel family.
@@ -265,9 +293,16 @@ struct TableView {
 // the copy and the slot read, for this kernel and k_probe_exists); the probes
 // of a table that fits one XCD's L2 were random L2 reads (~82-96 G/s), well
 // below the rate the probe side streams at (profiles/r06/r06sr_small_build_sides.txt).
-template <int L, int FORM, bool WRITE, bool LDS = false>
+//
+// MARKS: empty, or one unsigned * -- the build-side outer probes' mark bitmap:
+// a tile that stays on the fast path sets the bit of every slot a row matched
+// (one per found row: a tile with a multi-match row has left), so only the
+// tiles handed to the general path need k_probe_mark afterwards.  A pack, so
+// the instantiations without it keep their kernel arguments and machine code.
+template <int L, int FORM, bool WRITE, bool LDS = false, typename... MARKS>
 __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev out, unsigned *slow,
-                                                  unsigned long long slow_cap) {
+                                                  unsigned long long slow_cap, MARKS... marks) {
+    static_assert(sizeof...(MARKS) <= 1, "at most the mark bitmap");
     using LY = Lay<L>;
     using slot_t = typename LY::slot_t;
     using out_t = typename LY::out_t;
@@ -319,9 +354,11 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
         }
         unsigned found = 0;
         unsigned long long RP[kProbeItems];
+        [[maybe_unused]] unsigned long long MH[kProbeItems];   // MARKS: the matched slots
 #pragma unroll
         for (int i = 0; i < kProbeItems; ++i) {
             RP[i] = 0;
+            if constexpr (sizeof...(MARKS) == 1) MH[i] = 0;
             if (!V[i]) continue;
             // duplicate-free table: the chain ends at the match or at EMPTY
             // (a two-exit loop with nothing else in it)
@@ -334,6 +371,7 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
             if (!LY::empty(sv)) {
                 found |= 1u << i;
                 RP[i] = LY::pay(sv);
+                if constexpr (sizeof...(MARKS) == 1) MH[i] = hh;
             }
         }
         if (!unique) {
@@ -365,6 +403,7 @@ __global__ __launch_bounds__(kBlock) void k_probe(TableDev t, SrcDev src, OutDev
                 continue;
             }
         }
+        if constexpr (sizeof...(MARKS) == 1) mark_found((marks, ...), found, MH);
         if constexpr (!WRITE) {
             unsigned long long c = (unsigned long long)__popc(found);
 #pragma unroll
@@ -656,9 +695,12 @@ __global__ __launch_bounds__(kBlock) void k_probe_exists(TableDev t, SrcDev src,
 // no ballots, no scan, whole-wave contiguous stores.  out.cap == 0 is the
 // count-only form (the walks still run when build keys repeat: they decide
 // which tiles leave).  The chain walks are k_probe's, statement for statement.
-template <int L, int FORM, bool LDS>
+// MARKS: as k_probe's (the full outer probe).
+template <int L, int FORM, bool LDS, typename... MARKS>
 __global__ __launch_bounds__(kBlock) void k_probe_outer(TableDev t, SrcDev src, OutDev out, unsigned *slow,
-                                                        unsigned long long slow_cap, unsigned long long null_pay) {
+                                                        unsigned long long slow_cap, unsigned long long null_pay,
+                                                        MARKS... marks) {
+    static_assert(sizeof...(MARKS) <= 1, "at most the mark bitmap");
     using LY = Lay<L>;
     using slot_t = typename LY::slot_t;
     using out_t = typename LY::out_t;
@@ -701,9 +743,11 @@ __global__ __launch_bounds__(kBlock) void k_probe_outer(TableDev t, SrcDev src, 
         }
         unsigned found = 0;
         unsigned long long RP[kProbeItems];
+        [[maybe_unused]] unsigned long long MH[kProbeItems];   // MARKS: the matched slots
 #pragma unroll
         for (int i = 0; i < kProbeItems; ++i) {
             RP[i] = null_pay;
+            if constexpr (sizeof...(MARKS) == 1) MH[i] = 0;
             if (!V[i]) continue;
             slot_t sv = S[i];
             unsigned long long hh = H[i];
@@ -714,6 +758,7 @@ __global__ __launch_bounds__(kBlock) void k_probe_outer(TableDev t, SrcDev src, 
             if (!LY::empty(sv)) {
                 found |= 1u << i;
                 RP[i] = LY::pay(sv);
+                if constexpr (sizeof...(MARKS) == 1) MH[i] = hh;
             }
         }
         if (!unique) {
@@ -742,6 +787,7 @@ __global__ __launch_bounds__(kBlock) void k_probe_outer(TableDev t, SrcDev src, 
                 continue;
             }
         }
+        if constexpr (sizeof...(MARKS) == 1) mark_found((marks, ...), found, MH);
         // the tile's valid rows: [q * kProbeTile, min(src.n, (q + 1) * kProbeTile)), never none
         const unsigned long long left = (unsigned long long)src.n - q * kProbeTile;
         const unsigned long long rows = left < (unsigned long long)kProbeTile ? left : (unsigned long long)kProbeTile;
@@ -760,6 +806,191 @@ __global__ __launch_bounds__(kBlock) void k_probe_outer(TableDev t, SrcDev src, 
                 }
             }
             __syncthreads();   // st_base reused by the next tile
+        }
+    }
+}
+
+// ------------------------------------------------------------------ build-side outer probe
+// RIGHT / FULL OUTER with S on the left: behind the pairs (k_probe) or the
+// pairs and S's null rows (k_probe_outer), the R rows no S row of this call
+// matched come out as (R.pay, null_s), found through a mark bitmap, one bit
+// per slot, zeroed on the stream before every call:
+//   stage 1          k_probe / k_probe_outer with the MARKS pack: a tile that
+//                    stays on the fast path marks the slots its rows matched
+//                    where the walk found them (no second read of S, no
+//                    second walk);
+//   k_probe_mark     the tiles stage 1 handed to the general path (the slow
+//                    list: an INT64_MIN probe key, or a multi-match row):
+//                    every S key walks its chain and sets the bit of each
+//                    slot that holds it;
+//   k_emit_unmatched scans the slot array and emits occupied, unmarked slots.
+// marks[words] (the word behind the bitmap) is "an S row held INT64_MIN":
+// the side list's rows are matched iff it is set.
+//
+// k_probe_mark: k_probe_exists' shape -- 2048-row tiles, a lane's 8 first-slot
+// loads in flight before any is resolved -- over S's KEYS alone (load_key: no
+// payload column is read), persistent workgroups over slow[0 .. meta[3]) as
+// k_probe_slow's.  Bits are set through mark_first.
+// Duplicate-free build (meta[1] == 0): the walk ends at the first equal key.
+// Repeated build keys: every copy must end up marked.  All walks for key k
+// start at the same slot and pass k's copies c1, c2, ... in the same order.
+// A walk that is FIRST to set a copy's bit (its atomic OR returned the bit
+// clear) goes on towards EMPTY; a walk that finds a copy's bit already set
+// (by the read, or by the OR's return value) stops there.  Why every copy is
+// still marked: the bit of copy c_i can only be set by a walk for k, and the
+// walk that set it first does not stop at c_i, so it reaches c_{i+1} and
+// either sets that bit first and goes on, or finds it set by another walk
+// that, by the same rule, went on.  By induction from c1 (the first walk to
+// reach it sets it) every copy up to EMPTY is marked when the kernel ends,
+// and k_emit_unmatched is a later launch on the stream.  A hot build key of
+// c copies is thus walked to its end once per first-setter, not once per S row.
+// (Stage 1's fast path never sets a bit of a repeated key: a row matching one
+// sends its tile here.)
+template <int FORM>
+__device__ __forceinline__ unsigned long long load_key(const SrcDev &s, long long row);
+template <>
+__device__ __forceinline__ unsigned long long load_key<kCols64>(const SrcDev &s, long long row) {
+    return ((const unsigned long long *)s.key)[row];
+}
+template <>
+__device__ __forceinline__ unsigned long long load_key<kPacked64>(const SrcDev &s, long long row) {
+    return ((const unsigned long long *)s.key)[2 * row];
+}
+template <>
+__device__ __forceinline__ unsigned long long load_key<kCol32>(const SrcDev &s, long long row) {
+    return (unsigned long long)(unsigned)((const int *)s.key)[row];
+}
+
+template <int L, int FORM>
+__global__ __launch_bounds__(kBlock) void k_probe_mark(TableDev t, SrcDev src, unsigned *marks,
+                                                       unsigned long long words, const unsigned *slow,
+                                                       unsigned long long slow_cap) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    const slot_t *sl = (const slot_t *)t.slots;
+    const bool unique = (__hip_atomic_load(&t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull);
+    // (a slow list too short is flagged in the count by k_probe_slow)
+    const unsigned long long nt = t.meta[3] < slow_cap ? t.meta[3] : slow_cap;
+    for (unsigned long long j = blockIdx.x; j < nt; j += gridDim.x) {
+        const unsigned long long q = slow[j];
+        unsigned long long K[kProbeItems], H[kProbeItems];
+        unsigned walk = 0;
+        bool has_null = false;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const long long row = (long long)q * kProbeTile + (long long)i * kBlock + threadIdx.x;
+            K[i] = 0ull;
+            if (row < src.n) {
+                K[i] = load_key<FORM>(src, row);
+                if (LY::null_key(K[i])) has_null = true;
+                else walk |= 1u << i;
+            }
+        }
+        slot_t S[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            H[i] = slot_of(K[i], t.shift);
+            if ((walk >> i) & 1u) S[i] = sl[H[i]];
+        }
+        if constexpr (L == kWide) {
+            // (read first: one store per call and lane at most, none once the word is set)
+            if (has_null && __hip_atomic_load(&marks[words], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+                __hip_atomic_store(&marks[words], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((walk >> i) & 1u)) continue;
+            slot_t sv = S[i];
+            unsigned long long hh = H[i];
+            while (!LY::empty(sv)) {
+                // unique: the only copy; else only the first setter goes on (see above)
+                if (LY::key(sv) == K[i] && (!mark_first(marks, hh) || unique)) break;
+                hh = (hh + 1) & t.mask;
+                sv = sl[hh];
+            }
+        }
+    }
+}
+
+// k_emit_unmatched: 2048-slot tiles of the slot array (wide: one 16-B load
+// per slot), the mark word of a slot read beside it (a wave's 64 slots share
+// two words); occupied and unmarked slots are compacted with wave ballots in
+// row-slot-major order after ONE cursor add per tile (k_probe_exists'
+// compaction) and written as (pay, null_s), each element under out.cap;
+// out.cap == 0 counts only (uniform).  Wide: workgroup 0 then appends the side
+// list's payloads when no S row held INT64_MIN.
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_emit_unmatched(TableDev t, OutDev out, const unsigned *marks,
+                                                           unsigned long long words, unsigned long long null_s) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    constexpr int NW = kBlock / 64;
+    __shared__ unsigned long long st_base;
+    __shared__ unsigned s_cw[kProbeItems * NW];
+    const slot_t *sl = (const slot_t *)t.slots;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long cap = t.mask + 1ull;
+    const unsigned long long nt = (cap + kProbeTile - 1) / kProbeTile;
+    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+    out_t *orr = (out_t *)out.r;
+    out_t *oss = (out_t *)out.s;
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long P[kProbeItems];
+        unsigned found = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const unsigned long long j = q * kProbeTile + (unsigned long long)(i * kBlock) + threadIdx.x;
+            P[i] = 0ull;
+            if (j < cap) {
+                const slot_t sv = sl[j];
+                const unsigned m = marks[j >> 5];
+                P[i] = LY::pay(sv);
+                if (!LY::empty(sv) && !((m >> (unsigned)(j & 31ull)) & 1u)) found |= 1u << i;
+            }
+        }
+        unsigned lpre[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const unsigned long long bal = __ballot((found >> i) & 1u);
+            lpre[i] = (unsigned)__popcll(bal & lt);
+            if (lane == 0) s_cw[i * NW + wv] = (unsigned)__popcll(bal);
+        }
+        __syncthreads();
+        if (wv == 0) {   // exclusive scan of the kProbeItems * NW runs (<= 64)
+            static_assert(kProbeItems * NW <= 64, "one lane per run");
+            const unsigned v = lane < kProbeItems * NW ? s_cw[lane] : 0u;
+            const unsigned x = wave_incl_add(v);
+            if (lane < kProbeItems * NW) s_cw[lane] = x - v;
+            if (lane == 63) st_base = x ? atomicAdd(out.counter, (unsigned long long)x) : 0ull;
+        }
+        __syncthreads();
+        if (out.cap != 0) {   // (uniform)
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i) {
+                if (!((found >> i) & 1u)) continue;
+                const unsigned long long gi = st_base + s_cw[i * NW + wv] + lpre[i];
+                if (gi < (unsigned long long)out.cap) {
+                    orr[gi] = (out_t)P[i];
+                    oss[gi] = (out_t)null_s;
+                }
+            }
+        }
+        __syncthreads();   // s_cw / st_base reused by the next tile
+    }
+    if constexpr (L == kWide) {
+        if (blockIdx.x != 0) return;
+        const unsigned long long ns = t.meta[0];
+        if (ns == 0ull || marks[words] != 0u) return;   // (uniform)
+        if (threadIdx.x == 0) st_base = atomicAdd(out.counter, ns);
+        __syncthreads();
+        if (out.cap == 0) return;
+        for (unsigned long long j = threadIdx.x; j < ns; j += kBlock) {
+            const unsigned long long gi = st_base + j;
+            if (gi < (unsigned long long)out.cap) {
+                orr[gi] = (out_t)t.side[j];
+                oss[gi] = (out_t)null_s;
+            }
         }
     }
 }
@@ -1262,7 +1493,7 @@ size_t probe_tiles(long long n) {
 }
 
 hipError_t launch_probe(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
-                        bool count_only, unsigned *slow, size_t slow_cap, hipStream_t st) {
+                        bool count_only, unsigned *slow, size_t slow_cap, hipStream_t st, unsigned *marks) {
     if (src.n <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(&t.meta[3], 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
@@ -1276,7 +1507,12 @@ hipError_t launch_probe(const TableDev &t, int layout, const SrcDev &src, const 
         const auto fast = count_only ? (pg.lds ? k_probe<L, F, false, true> : k_probe<L, F, false, false>)
                                      : (pg.lds ? k_probe<L, F, true, true> : k_probe<L, F, true, false>);
         const auto rest = count_only ? k_probe_slow<L, F, false> : k_probe_slow<L, F, true>;
-        hipLaunchKernelGGL(fast, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, slow, cap);
+        if (marks) {
+            const auto fm = count_only ? (pg.lds ? k_probe<L, F, false, true, unsigned *> : k_probe<L, F, false, false, unsigned *>)
+                                       : (pg.lds ? k_probe<L, F, true, true, unsigned *> : k_probe<L, F, true, false, unsigned *>);
+            hipLaunchKernelGGL(fm, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, slow, cap, marks);
+        } else
+            hipLaunchKernelGGL(fast, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, slow, cap);
         hipLaunchKernelGGL(rest, dim3(gs), dim3(kBlock), 0, st, t, src, out, (const unsigned *)slow, cap);
         return hipGetLastError();
     });
@@ -1296,7 +1532,8 @@ hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src,
 }
 
 hipError_t launch_probe_outer(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
-                              unsigned long long null_pay, unsigned *slow, size_t slow_cap, hipStream_t st) {
+                              unsigned long long null_pay, unsigned *slow, size_t slow_cap, hipStream_t st,
+                              unsigned *marks) {
     if (src.n <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(&t.meta[3], 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
@@ -1310,11 +1547,50 @@ hipError_t launch_probe_outer(const TableDev &t, int layout, const SrcDev &src, 
         const auto fast = pg.lds ? k_probe_outer<L, F, true> : k_probe_outer<L, F, false>;
         const auto rest = out.cap == 0 ? k_probe_slow<L, F, false, unsigned long long>
                                        : k_probe_slow<L, F, true, unsigned long long>;
-        hipLaunchKernelGGL(fast, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, slow, cap,
-                           null_pay);
+        if (marks) {
+            const auto fm = pg.lds ? k_probe_outer<L, F, true, unsigned *> : k_probe_outer<L, F, false, unsigned *>;
+            hipLaunchKernelGGL(fm, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, slow, cap,
+                               null_pay, marks);
+        } else
+            hipLaunchKernelGGL(fast, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, slow, cap,
+                               null_pay);
         hipLaunchKernelGGL(rest, dim3(gs), dim3(kBlock), 0, st, t, src, out, (const unsigned *)slow, cap, null_pay);
         return hipGetLastError();
     });
+}
+
+size_t mark_words(unsigned long long cap) { return (size_t)(cap >> 5 ? cap >> 5 : 1) + 1; }
+
+hipError_t launch_marks_clear(const TableDev &t, unsigned *marks, hipStream_t st) {
+    return hipMemsetAsync(marks, 0, mark_words(t.mask + 1ull) * sizeof(unsigned), st);
+}
+
+hipError_t launch_unmatched_build(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,
+                                  unsigned long long null_s, unsigned *marks, const unsigned *slow, size_t slow_cap,
+                                  hipStream_t st) {
+    const unsigned long long cap = t.mask + 1ull, words = mark_words(cap) - 1;
+    if (src.n > 0) {
+        // the handed-over tiles' persistent workgroups, as k_probe_slow's
+        const unsigned tl = grid_for(src.n, kProbeTile), mx = (unsigned)(cu_count() * 8);
+        const unsigned g = tl < mx ? tl : mx;
+        const hipError_t e = with_layout_form(layout, src.form, [&](auto l, auto f) {
+            hipLaunchKernelGGL((k_probe_mark<decltype(l)::value, decltype(f)::value>), dim3(g), dim3(kBlock), 0, st, t,
+                               src, marks, words, slow, (unsigned long long)slow_cap);
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return e;
+    }
+    // the scan's persistent workgroups: eight per CU, a tile each at most
+    const unsigned tiles = grid_for((long long)cap, kProbeTile), most = (unsigned)(cu_count() * 8);
+    const unsigned g = tiles < most ? tiles : most;
+    if (layout == kWide)
+        hipLaunchKernelGGL(k_emit_unmatched<kWide>, dim3(g), dim3(kBlock), 0, st, t, out, (const unsigned *)marks, words,
+                           null_s);
+    else if (layout == kNarrow)
+        hipLaunchKernelGGL(k_emit_unmatched<kNarrow>, dim3(g), dim3(kBlock), 0, st, t, out, (const unsigned *)marks,
+                           words, null_s);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 
 hipError_t launch_partition(const SrcDev &src, int nparts, void *out_tuples,

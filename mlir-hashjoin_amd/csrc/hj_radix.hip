@@ -3970,6 +3970,27 @@ hipError_t radix_unmatched(bool wide, unsigned long long null_pay, const RadixPl
     return exists_stage(wide, true, &null_pay, pl, ws, r, s, out, st);
 }
 
+// The build-side outer join's last stage: radix_unmatched with the roles
+// exchanged.  k_join_exists reads its "r" side as the rows whose keys go into
+// the LDS table and its "s" side as the rows tested and emitted, and both
+// relations were partitioned by one plan, so S's set is passed as r and R's
+// as s; the anti map (r_gates = false) then keeps every non-empty R
+// partition, S rows or not -- those R rows are exactly the ones to emit.
+// The kernel writes the emitted row's payload to out.s and the null value to
+// out.r: the caller's columns are exchanged too, so R's payload lands in its
+// out_r and null_s in its out_s.
+// The work map now cuts R's runs, so the area must cover r.max_runs: every
+// build sizes it for (its plan, R's run list) in ensure_radix_scratch, the
+// probe for S's, and the buffers only grow -- max(R runs, S runs) holds.
+// An S partition is usually several 5120-row build rounds here (S is the
+// larger side), so the kernel's sub-chunks-outermost path is the common one:
+// an R sub-chunk stays in registers while every round of S's partition is
+// built and probed, and is emitted after the last.
+hipError_t radix_unmatched_build(bool wide, unsigned long long null_s, const RadixPlan &pl, const RadixWork &ws,
+                                 const BucketSet &r, const BucketSet &s, const OutDev &out, hipStream_t st) {
+    return exists_stage(wide, true, &null_s, pl, ws, s, r, OutDev{out.s, out.r, out.cap, out.counter}, st);
+}
+
 // radix_detect's deferred partitions: rows[1] += the rows of every listed
 // item (sum of its R run counts); the last workgroup to finish sets
 // *dup_flag when the self-join's pair count rows[0] exceeds them.

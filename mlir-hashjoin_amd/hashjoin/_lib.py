@@ -27,6 +27,8 @@ HJ_STRATEGY_RADIX = 2
 HJ_EXISTS_SEMI = 0
 HJ_EXISTS_ANTI = 1
 HJ_JOIN_KERNEL_EXISTS = 6
+HJ_OUTER_BUILD = 1
+HJ_OUTER_FULL = 2
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -86,6 +88,10 @@ def _load():
         "hj_dev_probe_outer_i64": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_probe_outer_tuples_i64": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_probe_outer_i32": (_int, [_vp, _vp, _i64, _i64, C.c_int32, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_probe_full_i64": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_probe_full_tuples_i64": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_probe_full_i32": (_int, [_vp, _int, _vp, _i64, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp,
+                                         _vp]),
         "hj_dev_partition_i64": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_dev_partition_tuples_i64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_partition_of": (_int, [_i64, _int]),

@@ -21,11 +21,12 @@ import os
 
 import torch
 
-from ._lib import (HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_STRATEGY_AUTO, HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, check,
-                   lib)
+from ._lib import (HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
+                   HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, check, lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
 EXISTS_KINDS = {"semi": HJ_EXISTS_SEMI, "anti": HJ_EXISTS_ANTI}
+FULL_KINDS = {"build": HJ_OUTER_BUILD, "full": HJ_OUTER_FULL}
 
 
 def _ptr(t):
@@ -379,6 +380,93 @@ class HashJoin:
                 return out_r[:m], out_s[:m]
             cap = m
         raise RuntimeError("outer join output did not fit after resizing")
+
+    # ---- build-side and full outer join (hj.h "Build-side and full outer join")
+    def probe_full(self, skey, spay=None, out_r=None, out_s=None, kind="full", null_r=-1, null_s=-1, count=None,
+                   row_base=0, stream=None):
+        """RIGHT OUTER (kind="build") or FULL OUTER (kind="full") probe of the
+        built table, S on the left: every pair of the inner join, plus
+        (R payload, null_s) for every R row no S row of this call matches,
+        plus (full only) (null_r, S payload) for every S row without a
+        partner.  Writes min(M, cap) rows into out_r / out_s (i32: row ids,
+        row_base + row on the S side); `count` (int64 device tensor) receives
+        M.  Both null values are written verbatim.  out_r and out_s None is
+        the count-only form.  Returns count."""
+        _need_cuda(skey, spay, out_r, out_s)
+        st = _stream(self.device, stream)
+        k = FULL_KINDS[kind]
+        count = self._count if count is None else count
+        if (out_r is None) != (out_s is None):
+            raise ValueError("full probe needs both outputs, or neither to count")
+        cap = 0 if out_r is None else out_r.numel()
+        if out_s is not None and out_s.numel() != cap:
+            raise ValueError("output columns differ in length")
+        for o in (out_r, out_s):
+            if o is not None and o.dtype != skey.dtype:
+                raise ValueError("full outputs carry the probe key's dtype")
+        if skey.dtype == torch.int64:
+            if spay is None and out_s is not None:
+                raise ValueError("int64 probe needs an int64 payload column")
+            if spay is not None and (spay.dtype != torch.int64 or spay.numel() != skey.numel()):
+                raise ValueError("int64 probe needs an int64 payload column of the same length")
+            check(lib.hj_dev_probe_full_i64(self._ctx, k, _ptr(skey), _ptr(spay), skey.numel(), int(null_r),
+                                            int(null_s), _ptr(out_r), _ptr(out_s), cap, _ptr(count), st),
+                  "hj_dev_probe_full_i64")
+        elif skey.dtype == torch.int32:
+            if spay is not None:
+                raise ValueError("i32 joins carry row ids, not payloads (reference types)")
+            check(lib.hj_dev_probe_full_i32(self._ctx, k, _ptr(skey), skey.numel(), int(row_base), int(null_r),
+                                            int(null_s), _ptr(out_r), _ptr(out_s), cap, _ptr(count), st),
+                  "hj_dev_probe_full_i32")
+        else:
+            raise TypeError("keys must be int32 or int64")
+        return count
+
+    def probe_full_tuples(self, tuples, out_r, out_s, kind="full", null_r=-1, null_s=-1, count=None, stream=None):
+        """probe_full over packed (n, 2) int64 {key, payload} rows."""
+        _need_cuda(tuples, out_r, out_s)
+        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
+            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        if (out_r is None) != (out_s is None) or (out_r is not None and out_r.numel() != out_s.numel()):
+            raise ValueError("full probe needs two outputs of one length, or neither to count")
+        count = self._count if count is None else count
+        cap = 0 if out_r is None else out_r.numel()
+        check(lib.hj_dev_probe_full_tuples_i64(self._ctx, FULL_KINDS[kind], _ptr(tuples), tuples.shape[0], int(null_r),
+                                               int(null_s), _ptr(out_r), _ptr(out_s), cap, _ptr(count),
+                                               _stream(self.device, stream)), "hj_dev_probe_full_tuples_i64")
+        return count
+
+    def count_full(self, skey, kind="full", stream=None, sync=True):
+        """M of the full (or build-side) outer probe."""
+        cnt = self.probe_full(skey, kind=kind, stream=stream)
+        return int(cnt.item()) if sync else cnt
+
+    def full_join(self, rkey, rpay, skey, spay=None, how="full", null_r=-1, null_s=-1, capacity=None, stream=None):
+        """join() keeping every R row and (how="full") every S row: build R,
+        then the full probe into an output sized |S| + |R| rows (exact when
+        no S row has two partners), or `capacity`, re-probing once at the
+        exact M if that was too small.  Returns (R payloads or null_r, S
+        payloads or null_s); row ids for int32 keys."""
+        if how not in FULL_KINDS:
+            raise ValueError("how must be 'full' or 'build'")
+        self.probe_hint(skey.numel())
+        try:
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+        dt = torch.int64 if rkey.dtype == torch.int64 else torch.int32
+        cap = max(1, skey.numel() + rkey.numel() if capacity is None else int(capacity))
+        for _ in range(2):
+            out_r = torch.empty(cap, dtype=dt, device=self.device)
+            out_s = torch.empty(cap, dtype=dt, device=self.device)
+            m = int(self.probe_full(skey, spay, out_r, out_s, kind=how, null_r=null_r, null_s=null_s,
+                                    stream=stream).item())
+            if m < 0:   # bit 63: an internal work list overflowed (hj.h)
+                raise RuntimeError("hash join: internal work list overflow (count flagged)")
+            if m <= cap:
+                return out_r[:m], out_s[:m]
+            cap = m
+        raise RuntimeError("full join output did not fit after resizing")
 
     # ---- folded routing (hj.h "Folded routing"): the owner and the
     # receiver's first radix-pass bin from one hash, so receivers skip a pass
