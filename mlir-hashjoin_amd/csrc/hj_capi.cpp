@@ -596,8 +596,9 @@ int radix_build(hj_ctx *c, const RadixSrc &in, hipStream_t st) {
     const bool wide = c->layout == kWide;
     HJ_TRY(ensure_radix_scratch(c, c->rset, in.src.n, wide, c->plan, in.nsrc));
     record(c, kEvInit0, st);
-    // meta[0] side count, [1] dup flag, [2..3] the build-side sample
-    HJ_HIP(hipMemsetAsync(c->meta, 0, 4 * sizeof(unsigned long long), st));
+    // meta[0] side count, [1] dup flag, [2..3] the build-side sample (zeroed by
+    // a kernel: a memset node of a captured build was replayed with a stale pattern)
+    HJ_HIP(hj::radix_state_clear(c->meta, st));
     record(c, kEvInit1, st);
     trace("build: workspace", st, in.src.n);
     HJ_TRY(radix_partition_src(c, in, c->rset, st));

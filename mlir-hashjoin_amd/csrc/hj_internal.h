@@ -274,6 +274,14 @@ hipError_t radix_route(const SrcDev &src, int rbits, void *out_tuples, unsigned 
 // rows each).  Runs the plan's second pass only (pl.passes == 2) into `out`.
 hipError_t radix_partition_routed(const void *tuples, long long n, const unsigned long long *cnt, int nsrc, int nseg,
                                   const RadixPlan &pl, const RadixWork &ws, const BucketSet &out, hipStream_t st);
+// Before R's partition: zeroes the radix build's four state words (the side
+// count, the repeat flag and the sample) with a kernel.  Not hipMemsetAsync:
+// as a node of a captured graph that 32-byte fill was replayed with a stale
+// 16-byte pattern (words seen on an MI355X: {garbage, -9, garbage + rows,
+// -9 + repeats} where -9 was the caller's own fill value of another tensor),
+// which turned the repeat flag on and the kernel choice round.  A kernel's
+// arguments travel in its node.
+hipError_t radix_state_clear(unsigned long long *meta4, hipStream_t st);
 // After R's partition: sample up to 64 build partitions for repeated keys,
 // adding {rows sampled, rows whose key repeated} into sample[0..1] (zeroed by
 // the caller).  Deterministic for given data.

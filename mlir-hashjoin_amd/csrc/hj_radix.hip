@@ -4076,6 +4076,15 @@ hipError_t radix_detect(bool wide, const RadixPlan &pl, const RadixWork &ws, con
     return hipGetLastError();
 }
 
+__global__ __launch_bounds__(64) void k_state_clear(u64 *meta4) {
+    if (threadIdx.x < 4) meta4[threadIdx.x] = 0ull;
+}
+
+hipError_t radix_state_clear(unsigned long long *meta4, hipStream_t st) {
+    hipLaunchKernelGGL(k_state_clear, dim3(1), dim3(64), 0, st, meta4);
+    return hipGetLastError();
+}
+
 hipError_t radix_sample(bool wide, const RadixPlan &pl, const BucketSet &r, unsigned long long *sample,
                         hipStream_t st) {
     const int P = 1 << pl.total_bits;

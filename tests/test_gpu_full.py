@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import outer_cases as OC
 import routed_layout as RL
 from hashjoin import HashJoin
 
@@ -195,6 +196,60 @@ def test_global_null_values_are_passed_through(glob_hj, oracle):
     assert int((gr == null_r).sum()) == e.n_s > 0 and int((gs == null_s).sum()) == e.n_r > 0
     gr, gs = probe(glob_hj, sk, sp, "build", null_r, null_s)   # null_r is ignored
     assert not (gr == null_r).any() and int((gs == null_s).sum()) == e.n_r
+
+
+@pytest.fixture(scope="module")
+def strided():
+    """outer_cases.strided_general_case on the device: more handed-over tiles
+    and more slot tiles than the general path's 8 x CUs persistent workgroups."""
+    c = dict(OC.strided_general_case(torch.cuda.get_device_properties(0).multi_processor_count))
+    nr, ns = len(c["rk"]), len(c["sk"])
+    c["rp"], c["sp"] = np.arange(nr, dtype=np.int64) + OC.R_OFF, np.arange(ns, dtype=np.int64) + OC.S_OFF
+    c["row_r"], c["row_s"] = np.arange(nr, dtype=np.int64), np.arange(ns, dtype=np.int64)   # i32: row ids
+    c["d_rk"], c["d_rp"], c["d_sk"], c["d_sp"] = dev(c["rk"]), dev(c["rp"]), dev(c["sk"]), dev(c["sp"])
+    return c
+
+
+@pytest.mark.parametrize("kind", ["full", "build", "full-count", "build-count"])
+def test_global_general_path_and_slot_scan_stride(glob_hj, strided, kind):
+    """Every probe tile is handed to the general path, 60 more of them than
+    k_probe_slow's / k_probe_mark's persistent workgroups, the slow list filled
+    to its exact tile count; the table is more slot tiles than
+    k_emit_unmatched's workgroups: each loop takes a second tile -- exact M, exact rows."""
+    c, e = strided, strided["exp"]
+    base = kind.split("-")[0]
+    glob_hj.build_table(c["d_rk"], c["d_rp"])
+    assert glob_hj.capacity == c["slots"]
+    m = e.m(base)
+    if kind.endswith("-count"):
+        assert glob_hj.count_full(c["d_sk"], kind=base) == m
+        assert glob_hj.strategy_used == "global"
+        return
+    out_r = torch.full((m + 64,), -7, dtype=torch.int64, device="cuda")
+    out_s = torch.full_like(out_r, -7)
+    got = int(glob_hj.probe_full(c["d_sk"], c["d_sp"], out_r, out_s, kind=base, null_r=-1, null_s=-2).item())
+    assert glob_hj.strategy_used == "global"
+    assert got == m
+    g_r, g_s = out_r.cpu().numpy(), out_s.cpu().numpy()
+    assert (g_r[m:] == -7).all() and (g_s[m:] == -7).all()
+    assert OC.same_rows(g_r[:m], g_s[:m], *e.rows(base, c["rp"], c["sp"], -1, -2), -1, -2)
+
+
+def test_global_general_path_and_slot_scan_stride_i32(glob_hj, strided):
+    """The same shape for the i32 types (row ids for payloads), full kind."""
+    c, e = strided, strided["exp"]
+    glob_hj.build_table(dev(c["rk"].astype(np.int32)))
+    assert glob_hj.capacity == c["slots"]
+    m = e.m("full")
+    d_sk = dev(c["sk"].astype(np.int32))
+    out_r = torch.full((m + 64,), -7, dtype=torch.int32, device="cuda")
+    out_s = torch.full_like(out_r, -7)
+    got = int(glob_hj.probe_full(d_sk, None, out_r, out_s, kind="full", null_r=-1, null_s=-2).item())
+    assert glob_hj.strategy_used == "global"
+    assert got == m
+    g_r, g_s = out_r.cpu().numpy().astype(np.int64), out_s.cpu().numpy().astype(np.int64)
+    assert (g_r[m:] == -7).all() and (g_s[m:] == -7).all()
+    assert OC.same_rows(g_r[:m], g_s[:m], *e.rows("full", c["row_r"], c["row_s"], -1, -2), -1, -2)
 
 
 # ------------------------------------------------------------------ radix
@@ -585,8 +640,12 @@ def test_graph_replay(hj, oracle, n, strategy, wide):
     sk = torch.empty(n, dtype=kt, device="cuda")
     rp = torch.arange(n, dtype=torch.int64, device="cuda") * 3 + 2 if wide else None
     sp = torch.arange(n, dtype=torch.int64, device="cuda") * 2 + 1 if wide else None
+    grp = None
     if wide:
         sets = [oracle.gen_pkfk_i64(61 + j, n, n, f)[0::2] for j, f in enumerate((1.0, 0.5, 0.1))]
+        if strategy == "radix":   # the replays also leave k_join_b and fill the deferral lists
+            grp, with_nulls = OC.replay_sets_other_kernels(oracle, n, 10 * n)
+            sets += [grp, with_nulls]
     else:
         sets = [(oracle.gen_uniform_i32(65 + j, 1, 1, hi, n), oracle.gen_uniform_i32(65 + j, 2, 1, hi, n))
                 for j, hi in enumerate((4 * n, n // 4, 1 << 30))]
@@ -633,6 +692,8 @@ def test_graph_replay(hj, oracle, n, strategy, wide):
             assert m == e.m <= cap
             assert oracle.same_multiset(out_r[:m].cpu().numpy().astype(np.int64),
                                         out_s[:m].cpu().numpy().astype(np.int64), e.r, e.s)
+            if data is grp:   # the replay chose its kernel from this data, on the device
+                assert e.m < cap and hj.join_kernel == "k_join_grp"
     finally:
         del g
         torch.cuda.synchronize()

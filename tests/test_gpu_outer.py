@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import outer_cases as OC
 import routed_layout as RL
 from hashjoin import HashJoin
 
@@ -165,6 +166,30 @@ def test_global_null_value_is_passed_through(glob_hj, oracle):
     n_un = check_outer(glob_hj, oracle, rk, sk, rp, sp, null=null)
     gr, _ = probe(glob_hj, sk, sp, null)
     assert int((gr == null).sum()) == n_un > 0 and not (gr == -1).any()
+
+
+@pytest.mark.parametrize("kind", ["outer", "outer-count"])
+def test_global_general_path_strides(glob_hj, kind):
+    """Every probe tile is handed to the general path, 60 more of them than
+    k_probe_slow's persistent workgroups, the slow list filled to its exact
+    tile count: the OUTER general path takes a second tile -- exact M, exact rows."""
+    c = OC.strided_general_case(torch.cuda.get_device_properties(0).multi_processor_count)
+    e, nr, ns = c["exp"], len(c["rk"]), len(c["sk"])
+    rp, sp = np.arange(nr, dtype=np.int64) + OC.R_OFF, np.arange(ns, dtype=np.int64) + OC.S_OFF
+    glob_hj.build_table(dev(c["rk"]), dev(rp))
+    d_sk, m = dev(c["sk"]), e.m("outer")
+    if kind == "outer-count":
+        assert glob_hj.count_outer(d_sk) == m
+        assert glob_hj.strategy_used == "global"
+        return
+    out_r = torch.full((m + 64,), -7, dtype=torch.int64, device="cuda")
+    out_s = torch.full_like(out_r, -7)
+    got = int(glob_hj.probe_outer(d_sk, dev(sp), out_r, out_s, null=-1).item())
+    assert glob_hj.strategy_used == "global"
+    assert got == m
+    g_r, g_s = out_r.cpu().numpy(), out_s.cpu().numpy()
+    assert (g_r[m:] == -7).all() and (g_s[m:] == -7).all()
+    assert OC.same_rows(g_r[:m], g_s[:m], *e.rows("outer", rp, sp, -1, -2), -1, -2)
 
 
 # ------------------------------------------------------------------ radix
@@ -508,8 +533,12 @@ def test_graph_replay(hj, oracle, n, strategy, wide):
     sk = torch.empty(n, dtype=kt, device="cuda")
     rp = torch.arange(n, dtype=torch.int64, device="cuda") * 3 + 2 if wide else None
     sp = torch.arange(n, dtype=torch.int64, device="cuda") * 2 + 1 if wide else None
+    grp = None
     if wide:
         sets = [oracle.gen_pkfk_i64(61 + j, n, n, f)[0::2] for j, f in enumerate((1.0, 0.5, 0.1, 0.8))]
+        if strategy == "radix":   # the replays also leave k_join_b and fill the deferral lists
+            grp, with_nulls = OC.replay_sets_other_kernels(oracle, n, 8 * n)
+            sets += [grp, with_nulls]
     else:
         sets = [(oracle.gen_uniform_i32(65 + j, 1, 1, hi, n), oracle.gen_uniform_i32(65 + j, 2, 1, hi, n))
                 for j, hi in enumerate((4 * n, n // 4, 1 << 30, 2 * n))]
@@ -558,6 +587,8 @@ def test_graph_replay(hj, oracle, n, strategy, wide):
             assert m == len(er) <= cap
             assert oracle.same_multiset(out_r[:m].cpu().numpy().astype(np.int64),
                                         out_s[:m].cpu().numpy().astype(np.int64), er, es)
+            if data is grp:   # the replay chose its kernel from this data, on the device
+                assert m < cap and hj.join_kernel == "k_join_grp"
     finally:
         del g
         torch.cuda.synchronize()

@@ -84,10 +84,13 @@ SEVERAL_NS = (1 << 21) + 2048 + 77
 NULL_ROWS = (3 * 2048 + 5, (512 + 7) * 2048 + 100, 1, 512 * 2048 + 2047, 1025 * 2048 + 10)
 
 
-def several_tiles_case(wide):
+def several_tiles_case(wide, hits=slice(None), s_nulls=True):
     """Build and probe columns, and what numpy says they join to: a table of
     exactly 64 KiB with five repeated keys (wide: and one INT64_MIN key), a
-    probe side a quarter of which hits it, forty rows of it a repeated key."""
+    probe side a quarter of which hits it, forty rows of it a repeated key.
+    hits: the slice of the plain build rows that the hits are drawn from (the
+    rest, like four of the repeated keys, then have no partner in S);
+    s_nulls=False leaves NULL_ROWS as misses, so S holds no INT64_MIN key."""
     nr, ns = (2048, SEVERAL_NS) if wide else (4096, SEVERAL_NS)
     dt, top = (np.int64, 1 << 40) if wide else (np.int32, 1 << 29)
     rng = np.random.default_rng(2048 if wide else 4096)
@@ -101,9 +104,9 @@ def several_tiles_case(wide):
     rp = np.arange(nr, dtype=np.int64) + (7000 if wide else 0)   # (i32: the row id)
     sk = rng.integers(2 * top, 4 * top - 1, ns).astype(dt)       # misses
     hit = rng.permutation(ns)[:ns // 4]
-    sk[hit] = rk[rng.choice(plain, len(hit))]               # a quarter of S hits R once
+    sk[hit] = rk[rng.choice(plain[hits], len(hit))]         # a quarter of S hits R once
     sk[rng.permutation(ns)[:40]] = rk[0]                    # forty rows meet a repeated key
-    if wide:
+    if wide and s_nulls:
         sk[list(NULL_ROWS)] = I64_MIN
     sp = np.arange(ns, dtype=np.int64) + (1 << 32 if wide else 0)
     # sort + searchsorted: build rows lo[j] .. hi[j] of the sorted side match probe row j
@@ -115,7 +118,13 @@ def several_tiles_case(wide):
     exp_r = rp[order[np.repeat(lo, cnt) + within]]
     exp_s = np.repeat(sp, cnt)
     assert int((cnt == 2).sum()) >= 40 and int((cnt > 0).sum()) >= ns // 4
-    return dict(rk=rk, rp=rp, sk=sk, sp=sp, cnt=cnt, exp_r=exp_r, exp_s=exp_s,
+    # the rows without a partner: S's by the counts, R's by np.isin (every copy of a key no S row holds)
+    r_un = ~np.isin(rk, sk)
+    pairs, n_s, n_r = len(exp_r), int((cnt == 0).sum()), int(r_un.sum())
+    assert pairs > 0 and n_s > 0 and n_r > (0 if hits == slice(None) else 1000)
+    assert r_un[[1, 2, 3, 4]].all() and r_un[nr - 4:].all() and not r_un[0] and not r_un[nr - 5]
+    return dict(rk=rk, rp=rp, sk=sk, sp=sp, cnt=cnt, exp_r=exp_r, exp_s=exp_s, null_s_rows=sp[cnt == 0],
+                null_r_rows=rp[r_un],
                 d_rk=dev(rk), d_rp=dev(rp) if wide else None, d_sk=dev(sk), d_sp=dev(sp) if wide else None)
 
 
@@ -174,6 +183,97 @@ def test_workgroups_take_several_tiles_i32(hj):
     c = several_tiles_case(False)
     g_r, g_s = inner_pairs(hj, c)
     assert np.array_equal(sorted_pairs(g_r, g_s), sorted_pairs(c["exp_r"], c["exp_s"]))
+
+
+HALF = slice(None, None, 2)   # hits drawn from every second plain build row: a thousand R rows keep no partner
+NULL_R, NULL_S, SENTINEL = -1, -2, -7   # payloads are >= 0 (i32: row ids)
+OUTER_KINDS = ["outer", "outer-count", "full", "build", "full-count", "build-count"]
+
+
+@pytest.fixture(scope="module")
+def several_i64_half():
+    return several_tiles_case(True, HALF)
+
+
+def assert_strides(c):
+    """More tiles than two workgroups per CU: every workgroup of the LDS-table
+    probes takes a second tile (on a part with more CUs this must fail, not pass unstrided)."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert -(-len(c["sk"]) // 2048) > 2 * cus, (len(c["sk"]), cus)
+
+
+def outer_expected(c, kind):
+    """The rows of kind outer / full / build: the pairs, (NULL_R, S.pay) of the
+    S rows without a partner, (R.pay, NULL_S) of the R rows without one."""
+    r, s = [c["exp_r"]], [c["exp_s"]]
+    if kind in ("outer", "full"):
+        r.append(np.full(len(c["null_s_rows"]), NULL_R, np.int64))
+        s.append(c["null_s_rows"])
+    if kind in ("full", "build"):
+        r.append(c["null_r_rows"])
+        s.append(np.full(len(c["null_r_rows"]), NULL_S, np.int64))
+    return np.concatenate(r), np.concatenate(s)
+
+
+def outer_probe(hj, c, kind, m):
+    """Probe kind of the current build into outputs of m + 64 sentinel rows:
+    exact M, and the 64 rows past it untouched."""
+    dt = torch.int64 if c["rk"].dtype == np.int64 else torch.int32
+    o_r = torch.full((m + 64,), SENTINEL, dtype=dt, device="cuda")
+    o_s = torch.full_like(o_r, SENTINEL)
+    if kind == "outer":
+        cnt = hj.probe_outer(c["d_sk"], c["d_sp"], o_r, o_s, null=NULL_R)
+    else:
+        cnt = hj.probe_full(c["d_sk"], c["d_sp"], o_r, o_s, kind=kind, null_r=NULL_R, null_s=NULL_S)
+    got = int(cnt.item())
+    assert hj.strategy_used == "global"
+    assert got == m
+    g_r, g_s = o_r.cpu().numpy().astype(np.int64), o_s.cpu().numpy().astype(np.int64)
+    assert (g_r[m:] == SENTINEL).all() and (g_s[m:] == SENTINEL).all()
+    return g_r[:m], g_s[:m]
+
+
+def check_outer_kind(hj, c, kind):
+    assert_strides(c)
+    assert min(c["rp"].min(), c["sp"].min()) >= 0   # no payload is a null value or the sentinel
+    hj.build_table(c["d_rk"], c["d_rp"])
+    base = kind.split("-")[0]
+    e_r, e_s = outer_expected(c, base)
+    if kind.endswith("-count"):
+        got = hj.count_outer(c["d_sk"]) if base == "outer" else hj.count_full(c["d_sk"], kind=base)
+        assert hj.strategy_used == "global"
+        assert got == len(e_r)
+        return None
+    g_r, g_s = outer_probe(hj, c, base, len(e_r))
+    assert np.array_equal(sorted_pairs(g_r, g_s), sorted_pairs(e_r, e_s))
+    return g_r, g_s
+
+
+@pytest.mark.parametrize("kind", OUTER_KINDS)
+@pytest.mark.parametrize("hits", ["all", "half"])
+def test_workgroups_take_several_tiles_outer(hj, several_i64, several_i64_half, hits, kind):
+    """k_probe_outer<LDS> (outer, full) and k_probe<LDS, MARKS> (build) with
+    more than one tile per workgroup, some tiles handed to the general path
+    between tiles that stay, then k_probe_mark and k_emit_unmatched: exact M,
+    exact rows, nothing written past M.  half: a thousand build rows, and both
+    copies of four repeated keys, come out as R's null rows."""
+    check_outer_kind(hj, several_i64 if hits == "all" else several_i64_half, kind)
+
+
+def test_side_list_row_without_partner(hj):
+    """S holds no INT64_MIN key: build row 100 (INT64_MIN, the side list's only
+    row) comes out once, as (rp[100], NULL_S), behind workgroup 0's tiles."""
+    c = several_tiles_case(True, HALF, s_nulls=False)
+    assert c["rk"][100] == I64_MIN and not (c["sk"] == I64_MIN).any()
+    assert np.isin(c["rp"][100], c["null_r_rows"])
+    g_r, g_s = check_outer_kind(hj, c, "full")
+    assert g_s[g_r == c["rp"][100]].tolist() == [NULL_S]
+
+
+@pytest.mark.parametrize("kind", ["outer", "full"])
+def test_workgroups_take_several_tiles_outer_i32(hj, kind):
+    """The same for the i32 types (4096 build rows, row ids for payloads)."""
+    check_outer_kind(hj, several_tiles_case(False, HALF), kind)
 
 
 @pytest.mark.parametrize("nr,wide", [(1500, True), (4000, True), (3000, False), (20000, False)])
