@@ -131,7 +131,7 @@ int hj_ctx_last_timing_ex(hj_ctx *ctx, float ms[8]);
 int hj_ctx_timing_accumulate(hj_ctx *ctx, int enable);
 int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 /* RADIX: the join kernel of the last probe, whichever entry point ran it
- * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_probe_full_*, hj_dev_count_*, hj_dev_exists_*, and after a routed build
+ * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_probe_full_*, hj_dev_count_*, hj_dev_exists_*, hj_dev_lookup_*, and after a routed build
  * hj_dev_probe_routed_i64 too).  A pure function of the row
  * width, the probe / build size ratio (>= 8: the probe-heavy shape) and the
  * build side's repeated keys, sampled at build time over up to 64 partitions
@@ -149,6 +149,8 @@ int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 #define HJ_JOIN_KERNEL_GENERAL 5
 /* k_join_exists: the last probe was a radix semi- / anti-join (hj_dev_exists_*) */
 #define HJ_JOIN_KERNEL_EXISTS 6
+/* k_join_lookup: the last probe was a radix positional lookup (hj_dev_lookup_*) */
+#define HJ_JOIN_KERNEL_LOOKUP 7
 int hj_ctx_join_kernel(hj_ctx *ctx);
 
 /* ------------------------------------------------------------ device phases
@@ -213,6 +215,56 @@ int hj_dev_exists_tuples_i64(hj_ctx *ctx, int kind, const int64_t *tuples, int64
                              int64_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
 int hj_dev_exists_i32(hj_ctx *ctx, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t *out_key,
                       int32_t *out_s, int64_t out_cap, uint64_t *d_count, void *stream);
+
+/* Positional lookup probe (the SINGLE and MARK joins of a query engine's
+ * join-kind list; a dimension lookup, an id -> index mapping, Series.map) over
+ * the table an ordinary hj_dev_build_* left: one result per probe row, at the
+ * row's own position.  For the built relation R and the probe relation S of n
+ * rows, with j the row's position in S as passed in,
+ *   out_cnt[j] = the number of R rows i with R.key[i] == S.key[j];
+ *   out_r[j]   = the smallest (signed) R payload among those rows, or
+ *                null_pay (i32: null_row), written verbatim, when there is none.
+ * i32 payloads are R's row ids (hj_dev_build_i32's row_base + row), so the
+ * smallest is the first partner in R's order; "smallest" makes the result
+ * deterministic and equal across strategies and kernels, and with a unique
+ * build key it is simply the partner.  A caller that needs SINGLE-join
+ * strictness checks out_cnt or hj_ctx_build_has_duplicates.
+ * Every position 0 .. n-1 of each output that was passed is written exactly
+ * once and nothing at or past n; there is no out_cap.  Either output may be
+ * NULL (MARK only, or payload only); both NULL with n > 0 is HJ_ERR_ARG --
+ * hj_dev_exists_*'s count-only form answers that.  d_count = the number of S
+ * rows with at least one partner (the semi-join count), zeroed by the call;
+ * bit 63 as above.
+ * INT64_MIN is a key like any other: an INT64_MIN probe key counts R's
+ * INT64_MIN rows and takes their smallest payload.  R empty: every row is
+ * (null_pay, 0).  S empty: nothing is written, d_count = 0.
+ * Errors in hj_dev_probe_outer_*'s order: a null context (HJ_ERR_ARG); no
+ * build of that layout (HJ_ERR_STATE); a null count pointer, a bad relation,
+ * both outputs null (HJ_ERR_ARG); a current build of more than INT32_MAX rows
+ * (HJ_ERR_ARG: counts are int32); for i32, n > INT32_MAX (HJ_ERR_ARG).
+ * Asynchronous on the stream, kernels and memsets only once hj_ctx_reserve /
+ * hj_ctx_reserve_probe sized the workspace (graph-capturable).  The strategy
+ * is chosen exactly as for hj_dev_probe_* (the AUTO dual build included) and
+ * hj_ctx_strategy_used reports it; the probe timing works as for
+ * hj_dev_exists_* (RADIX: [4] the partition of S, whose rows carry their
+ * index through the passes, [5] the rest) and hj_ctx_join_kernel returns
+ * HJ_JOIN_KERNEL_LOOKUP after a radix lookup.  The table, R's partition, the
+ * side list, the "build keys repeat" flag and the full outer probes' mark
+ * bitmap are left untouched: lookup, inner, semi, anti, outer, build and full
+ * probes of one build may follow each other in any order and each returns
+ * what it returned before.  Valid after hj_dev_build_routed_i64 too, over
+ * unrouted rows, like hj_dev_exists_i64.
+ * Cost: GLOBAL stores both columns in whole contiguous
+ * runs; RADIX joins S in hash order, so each output column passed costs one
+ * scattered store per row -- pass only the column that is needed.
+ * There is no tuples form -- a packed S payload has no meaning where the
+ * result is addressed by position -- and no routed bin-range form: a bin
+ * range sees only part of S, so the positions of the rest would stay
+ * unwritten. */
+int hj_dev_lookup_i64(hj_ctx *ctx, const int64_t *skey, int64_t n, int64_t null_pay,
+                      int64_t *out_r, int32_t *out_cnt, uint64_t *d_count, void *stream);
+int hj_dev_lookup_i32(hj_ctx *ctx, const int32_t *skey, int64_t n, int32_t null_row,
+                      int32_t *out_r, int32_t *out_cnt, uint64_t *d_count, void *stream);
 
 /* Probe-side outer join (LEFT OUTER with the probe relation on the left) over
  * the table an ordinary hj_dev_build_* left: one build serves inner, semi,

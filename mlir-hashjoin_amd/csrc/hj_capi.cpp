@@ -218,6 +218,7 @@ struct hj_ctx {
     // follows from these and the build-time sample in meta[2..3])
     bool join_ran = false, join_wide = false, join_stream = false;
     bool exists_ran = false;   // the last probe was a radix semi- / anti-join (HJ_JOIN_KERNEL_EXISTS)
+    bool lookup_ran = false;   // the last probe was a radix lookup (HJ_JOIN_KERNEL_LOOKUP)
     bool routed = false;   // the current build came from hj_dev_build_routed_i64 (plan.skip owner bits)
     bool dup_checked = false;   // hj_ctx_build_has_duplicates ran its DETECT build for this build
     bool host_building = false;  // host_join's build is running (do_build keeps the memo's input copies)
@@ -581,7 +582,7 @@ int begin_build(hj_ctx *c, int layout, int64_t n, int used, bool dual, bool rout
     c->routed = routed;
     c->plan = plan;
     c->probe_used = -1;
-    c->join_ran = c->exists_ran = c->dup_checked = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = c->dup_checked = false;
     // (hj_count_*'s kept table is gone; a host join's own build keeps the
     // EXACT copies it has just taken of its inputs)
     if (c->host_building) c->memo.valid = false;
@@ -641,13 +642,15 @@ int do_build(hj_ctx *c, int layout, const hj::SrcDev &src, hipStream_t st) {
 }
 
 // One probe of the current build, after the entry point's argument checks.
-enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter, kProbeBuild, kProbeFull };
+enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter, kProbeBuild, kProbeFull, kProbeLookup };
 struct ProbeReq {
     RadixSrc in;       // S; routed: bins [bin0, bin0 + in.nbins) of the build's first pass
     int bin0 = 0;
-    hj::OutDev out;    // inner, outer, build, full: R and S payloads; semi / anti: S keys (may be null) and S payloads
+    hj::OutDev out;    // inner, outer, build, full: R and S payloads; semi / anti: S keys (may be null) and S payloads;
+                       // lookup: out.r the per-row R payload (may be null), out.s unused, out.cap = |S|
+    int *out_cnt = nullptr;   // lookup: the per-row partner count (may be null)
     ProbeKind kind = kProbeInner;
-    unsigned long long null_pay = 0;   // outer, full: the R payload of an S row without a partner (out.cap == 0 counts only)
+    unsigned long long null_pay = 0;   // outer, full, lookup: the R payload of an S row without a partner (outer, full: out.cap == 0 counts only)
     unsigned long long null_s = 0;     // build, full: the S payload of an R row without a partner
 };
 
@@ -660,12 +663,14 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
     const bool r_nulls = q.kind == kProbeBuild || q.kind == kProbeFull;
     const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
     c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
-    c->join_ran = c->exists_ran = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = false;
     if (!radix) {
         HJ_HIP(hipMemsetAsync(q.out.counter, 0, sizeof(uint64_t), st));
         record(c, kEvProbe0, st);
         if (exists) {
             HJ_HIP(hj::launch_probe_exists(table_dev(c), c->layout, src, q.out, q.kind == kProbeAnti, st));
+        } else if (q.kind == kProbeLookup) {
+            HJ_HIP(hj::launch_probe_lookup(table_dev(c), c->layout, src, q.out, q.out_cnt, q.null_pay, st));
         } else {
             const size_t slow_cap = hj::probe_tiles(src.n);
             HJ_TRY(ensure_buf(c->slow, slow_cap * sizeof(unsigned)));
@@ -691,7 +696,15 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
         HJ_TRY(ensure_radix_scratch(c, c->sset, src.n, wide, c->plan, q.in.nsrc));
         trace("probe: workspace", st, (long long)c->sset.max_buckets);
         record(c, kEvProbe0, st);
-        HJ_TRY(radix_partition_src(c, q.in, c->sset, st));
+        if (q.kind == kProbeLookup && wide) {
+            // S's rows carry their index through the passes: the key column alone is read
+            RadixSrc in = q.in;
+            in.src.form = hj::kKeyRow64;
+            in.src.pay = nullptr;
+            HJ_TRY(radix_partition_src(c, in, c->sset, st));
+        } else {
+            HJ_TRY(radix_partition_src(c, q.in, c->sset, st));
+        }
         trace("probe: S partitioned", st, src.n);
         record(c, kEvProbeMid, st);
         hj::BucketSet r = bucket_set(c->rset);
@@ -705,6 +718,10 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
             HJ_RADIX(c, st, hj::radix_exists(wide, q.kind == kProbeAnti, c->plan, radix_work(c), r, bucket_set(c->sset),
                                              q.out, st));
             c->exists_ran = true;
+        } else if (q.kind == kProbeLookup) {
+            HJ_RADIX(c, st, hj::radix_lookup(wide, q.null_pay, src.n, c->plan, radix_work(c), r, bucket_set(c->sset),
+                                             q.out, q.out_cnt, st));
+            c->lookup_ran = true;
         } else {
             // the kernel: a function of (row width, size ratio, build-time sample)
             o.dup_flag = c->meta + 1;
@@ -762,6 +779,27 @@ int do_exists(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, void *out_
     q.in.src = src;
     q.out = hj::OutDev{out_key, out_s, cap, (unsigned long long *)d_count};
     q.kind = kind == HJ_EXISTS_ANTI ? kProbeAnti : kProbeSemi;
+    return run_probe(c, q, st);
+}
+
+// Positional lookup (hj_dev_lookup_*): one (payload, count) per S row at the
+// row's own index.  Reads what do_exists reads and the repeat flag.
+int do_lookup(hj_ctx *c, int layout, const hj::SrcDev &src, unsigned long long null_pay, void *out_r, int32_t *out_cnt,
+              uint64_t *d_count, hipStream_t st) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, "probe without a matching build");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
+    if (src.n > 0 && !out_r && !out_cnt)
+        HJ_FAIL(HJ_ERR_ARG, "both outputs null (hj_dev_exists_* counts the rows with a partner)");
+    if (c->n_build > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "int32 counts: the build side must have < 2^31 rows");
+    if (layout == kNarrow && src.n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids: probe side must have < 2^31 rows");
+    ProbeReq q;
+    q.in.src = src;
+    q.out = hj::OutDev{out_r, nullptr, src.n, (unsigned long long *)d_count};
+    q.out_cnt = out_cnt;
+    q.kind = kProbeLookup;
+    q.null_pay = null_pay;
     return run_probe(c, q, st);
 }
 
@@ -1625,6 +1663,7 @@ int hj_ctx_build_has_duplicates(hj_ctx *c) {
 int hj_ctx_join_kernel(hj_ctx *c) {
     if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
     if (c->exists_ran && c->layout >= 0) return HJ_JOIN_KERNEL_EXISTS;
+    if (c->lookup_ran && c->layout >= 0) return HJ_JOIN_KERNEL_LOOKUP;
     if (!c->join_ran || c->layout < 0) return 0;
     HJ_TRY(set_device(c));
     unsigned long long v[2] = {0, 0};
@@ -1780,6 +1819,18 @@ int hj_dev_exists_i32(hj_ctx *c, int kind, const int32_t *skey, int64_t n, int64
     if (row_base < 0 || row_base + n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids out of range");
     return do_exists(c, kNarrow, kind, src_col32(skey, n, row_base), out_key, out_s, out_cap, d_count,
                      (hipStream_t)stream);
+}
+
+int hj_dev_lookup_i64(hj_ctx *c, const int64_t *skey, int64_t n, int64_t null_pay, int64_t *out_r, int32_t *out_cnt,
+                      uint64_t *d_count, void *stream) {
+    // (the key column stands in for the payload column, which no lookup kernel reads)
+    return do_lookup(c, kWide, src_cols64(skey, skey, n), (unsigned long long)null_pay, out_r, out_cnt, d_count,
+                     (hipStream_t)stream);
+}
+int hj_dev_lookup_i32(hj_ctx *c, const int32_t *skey, int64_t n, int32_t null_row, int32_t *out_r, int32_t *out_cnt,
+                      uint64_t *d_count, void *stream) {
+    return do_lookup(c, kNarrow, src_col32(skey, n, 0), (unsigned long long)(long long)null_row, out_r, out_cnt,
+                     d_count, (hipStream_t)stream);
 }
 
 // (the null context is reported before any other argument, as the header says)

@@ -86,7 +86,9 @@ struct TableDev {
 enum Layout : int { kWide = 0, kNarrow = 1 };
 
 // Source forms of a relation on the device.
-enum SrcForm : int { kCols64 = 0, kPacked64 = 1, kCol32 = 2 };
+// (3 and 4 are the radix passes' own; kKeyRow64, radix_partition only: an
+// int64 key column whose payload is the row's index -- the lookup probe's S)
+enum SrcForm : int { kCols64 = 0, kPacked64 = 1, kCol32 = 2, kKeyRow64 = 5 };
 
 struct SrcDev {
     const void *key;    // int64 column, packed {key,pay} tuples or int32 column
@@ -125,6 +127,13 @@ hipError_t launch_probe(const TableDev &t, int layout, const SrcDev &src, const 
 // general path, meta[1] untouched
 hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, bool anti,
                                hipStream_t st);
+// positional lookup over the global table: for S row j, out.r[j] = the
+// smallest (signed) payload of the R rows with its key or null_pay, cnt[j] =
+// their number (either may be null); out.counter += the S rows with a
+// partner.  src: a key column (kCols64 -- its pay is not read -- or kCol32).
+// One launch; reads meta[0..1], writes no build state.
+hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, int *cnt,
+                               unsigned long long null_pay, hipStream_t st);
 // probe-side outer join over the global table: launch_probe's pairs plus
 // (null_pay, S payload) for every S row without a partner; out.cap == 0
 // counts only; slow / slow_cap as launch_probe's
@@ -243,6 +252,17 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
 // the repeat flag.
 hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
                         const BucketSet &s, const OutDev &out, hipStream_t st);
+// Positional lookup over the partitioned relations (k_join_lookup).  s was
+// partitioned with each row's index in S as its payload (kKeyRow64, or kCol32
+// with row_base 0), n = |S|: for S row j, out.r[j] = the smallest (signed)
+// payload of the R rows with its key or null_pay, cnt[j] = their number
+// (int64 / int32 payloads by width; either output may be null), out.counter =
+// the S rows with a partner.  out.cap is ignored: every store is bounded by n.
+// radix_exists' anti work map (every non-empty S partition is an item), so
+// each row index is written exactly once and nothing needs a prefill.  Reads
+// r, writes neither it nor the repeat flag.
+hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, const RadixPlan &pl, const RadixWork &ws,
+                        const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt, hipStream_t st);
 // The outer join's second stage, after radix_join over the same r and s (and
 // out): the S rows without a partner in r are appended behind the pairs as
 // (null_pay, S payload) -- radix_exists' anti probe whose work map leaves

@@ -8,7 +8,8 @@
 //                                       -> k_probe<WRITE=true>: ILP slot
 //                                          reads, ballot-compacted output,
 //                                          one global cursor add per block
-// plus the exists probes (k_probe_exists), the outer probe (k_probe_outer),
+// plus the exists probes (k_probe_exists), the positional lookup probe
+// (k_probe_lookup), the outer probe (k_probe_outer),
 // the build-side outer stages (k_probe_mark, k_emit_unmatched),
 // the radix partition used by the
 // multi-GPU exchange, the selection, the counter-based generators of the
@@ -18,7 +19,7 @@
 // independent, no warp-32 idioms.  Integer/byte work: no MFMA.
 //
 // Written once, used by several kernels / launchers:
-//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists, k_probe_outer)
+//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists, k_probe_lookup, k_probe_outer)
 //   wave_incl_add    every wave prefix sum (hj_internal.h: DPP, no LDS round trips)
 //   with_layout_form the (layout, form) -> template-argument dispatch of the launchers
 //   probe_grid       the tile probes' grid and LDS bytes
@@ -680,6 +681,159 @@ __global__ __launch_bounds__(kBlock) void k_probe_exists(TableDev t, SrcDev src,
     }
 }
 
+// The key of row `row` alone (k_probe_lookup, k_probe_mark: no payload column is read).
+template <int FORM>
+__device__ __forceinline__ unsigned long long load_key(const SrcDev &s, long long row);
+template <>
+__device__ __forceinline__ unsigned long long load_key<kCols64>(const SrcDev &s, long long row) {
+    return ((const unsigned long long *)s.key)[row];
+}
+template <>
+__device__ __forceinline__ unsigned long long load_key<kPacked64>(const SrcDev &s, long long row) {
+    return ((const unsigned long long *)s.key)[2 * row];
+}
+template <>
+__device__ __forceinline__ unsigned long long load_key<kCol32>(const SrcDev &s, long long row) {
+    return (unsigned long long)(unsigned)((const int *)s.key)[row];
+}
+
+// ------------------------------------------------------------------ lookup probe
+// Positional lookup (SINGLE / MARK join): for S row j, out.r[j] = the smallest
+// (signed) payload among the R rows with its key, or null_pay; cnt[j] = how
+// many there are.  k_probe_exists' shape -- 2048-row tiles, every row's first
+// slot load issued before any is resolved, TableView -- over S's KEYS alone
+// (load_key), without its compaction: row slot i of thread x stores to its own
+// row index, so there are no ballots, no scan and no cursor, and every store
+// instruction writes one contiguous run per wave.  The chain walk ends at the
+// first equal key when the build's repeat flag (meta[1]) is clear, else it
+// goes on to EMPTY, counting and taking the minimum.  A wide INT64_MIN probe
+// key answers from the side list: its count is meta[0] and its minimum is
+// taken once per workgroup (only when the list holds a row).  Either output
+// may be null (wave-uniform branches).  The rows with a partner are summed per
+// lane and added to out.counter once per workgroup, after its last tile.
+// LDS: the next tile's keys are loaded ahead (see load_keys below).
+template <int L, int FORM, bool LDS>
+__global__ __launch_bounds__(kBlock) void k_probe_lookup(TableDev t, SrcDev src, OutDev out, int *cnt,
+                                                         unsigned long long null_pay) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    constexpr int NW = kBlock / 64;
+    constexpr long long kMaxPay = 0x7fffffffffffffffll;
+    __shared__ long long s_side_min;
+    __shared__ unsigned s_hits[NW];
+    extern __shared__ ulonglong2 s_tab[];
+
+    const TableView<L, LDS> tab(t, s_tab);
+    const bool unique = (__hip_atomic_load(&t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull);
+    const unsigned long long side_n = L == kWide ? t.meta[0] : 0ull;   // INT64_MIN build rows
+    long long side_min = (long long)null_pay;
+    if (side_n != 0ull) {   // (uniform)
+        if (threadIdx.x == 0) s_side_min = kMaxPay;
+        __syncthreads();
+        long long m = kMaxPay;
+        for (unsigned long long j = threadIdx.x; j < side_n; j += kBlock) {
+            const long long p = (long long)t.side[j];
+            m = p < m ? p : m;
+        }
+        atomicMin(&s_side_min, m);
+        __syncthreads();
+        side_min = s_side_min;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
+    out_t *orr = (out_t *)out.r;
+    unsigned hits = 0;
+    // the keys of tile q (bits of the result: the rows the source holds)
+    auto load_keys = [&](unsigned long long q, unsigned long long (&K)[kProbeItems]) {
+        unsigned valid = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const long long row = (long long)q * kProbeTile + (long long)i * kBlock + threadIdx.x;
+            K[i] = 0ull;
+            if (row < src.n) {
+                valid |= 1u << i;
+                K[i] = load_key<FORM>(src, row);
+            }
+        }
+        return valid;
+    };
+    // LDS: a persistent loop of few waves per CU (the table copies fill the
+    // LDS), so the next tile's keys are loaded before this tile's walks and
+    // stores -- loads issued behind a tile's stores would wait for them.  A
+    // global table runs one workgroup per tile: nothing to load ahead.
+    [[maybe_unused]] unsigned long long KN[kProbeItems];
+    [[maybe_unused]] unsigned valid_n = 0;
+    if constexpr (LDS) {
+        if (blockIdx.x < nt) valid_n = load_keys(blockIdx.x, KN);
+    }
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long K[kProbeItems], H[kProbeItems];
+        long long RP[kProbeItems];
+        unsigned C[kProbeItems];
+        unsigned valid, walk = 0;
+        if constexpr (LDS) {
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i) K[i] = KN[i];
+            valid = valid_n;
+            if (q + gridDim.x < nt) valid_n = load_keys(q + gridDim.x, KN);
+        } else {
+            valid = load_keys(q, K);
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            C[i] = 0u;
+            RP[i] = kMaxPay;
+            if (!((valid >> i) & 1u)) continue;
+            if (LY::null_key(K[i])) {
+                C[i] = (unsigned)side_n;
+                RP[i] = side_min;
+            } else {
+                walk |= 1u << i;
+            }
+        }
+        slot_t S[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            H[i] = slot_of(K[i], t.shift);
+            if ((walk >> i) & 1u) S[i] = tab.at(H[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((walk >> i) & 1u)) continue;
+            slot_t sv = S[i];
+            unsigned long long hh = H[i];
+            while (!LY::empty(sv)) {
+                if (LY::key(sv) == K[i]) {
+                    const long long p = (long long)LY::pay(sv);
+                    RP[i] = p < RP[i] ? p : RP[i];
+                    ++C[i];
+                    if (unique) break;
+                }
+                hh = (hh + 1) & t.mask;
+                sv = tab.at(hh);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((valid >> i) & 1u)) continue;
+            const long long row = (long long)q * kProbeTile + (long long)i * kBlock + threadIdx.x;
+            if (orr) orr[row] = (out_t)(C[i] ? RP[i] : (long long)null_pay);
+            if (cnt) cnt[row] = (int)C[i];
+            hits += C[i] ? 1u : 0u;
+        }
+    }
+    const unsigned x = wave_incl_add(hits);
+    if (lane == 63) s_hits[wv] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sum = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sum += s_hits[w];
+        if (sum) atomicAdd(out.counter, sum);
+    }
+}
+
 // ------------------------------------------------------------------ outer probe
 // Probe-side outer join (LEFT OUTER with S on the left): every pair of the
 // inner join, plus (null_pay, S.pay) for every S row without a partner.
@@ -846,21 +1000,6 @@ __global__ __launch_bounds__(kBlock) void k_probe_outer(TableDev t, SrcDev src, 
 // c copies is thus walked to its end once per first-setter, not once per S row.
 // (Stage 1's fast path never sets a bit of a repeated key: a row matching one
 // sends its tile here.)
-template <int FORM>
-__device__ __forceinline__ unsigned long long load_key(const SrcDev &s, long long row);
-template <>
-__device__ __forceinline__ unsigned long long load_key<kCols64>(const SrcDev &s, long long row) {
-    return ((const unsigned long long *)s.key)[row];
-}
-template <>
-__device__ __forceinline__ unsigned long long load_key<kPacked64>(const SrcDev &s, long long row) {
-    return ((const unsigned long long *)s.key)[2 * row];
-}
-template <>
-__device__ __forceinline__ unsigned long long load_key<kCol32>(const SrcDev &s, long long row) {
-    return (unsigned long long)(unsigned)((const int *)s.key)[row];
-}
-
 template <int L, int FORM>
 __global__ __launch_bounds__(kBlock) void k_probe_mark(TableDev t, SrcDev src, unsigned *marks,
                                                        unsigned long long words, const unsigned *slow,
@@ -1529,6 +1668,22 @@ hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src,
         hipLaunchKernelGGL(k, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, a);
         return hipGetLastError();
     });
+}
+
+hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, int *cnt,
+                               unsigned long long null_pay, hipStream_t st) {
+    if (src.n <= 0) return hipSuccess;
+    const ProbeGrid pg = probe_grid(t, layout, src.n);
+    // (a key column only: the int64 column form or the i32 one)
+    auto launch = [&](auto l, auto f) {
+        constexpr int L = decltype(l)::value, F = decltype(f)::value;
+        const auto k = pg.lds ? k_probe_lookup<L, F, true> : k_probe_lookup<L, F, false>;
+        hipLaunchKernelGGL(k, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, cnt, null_pay);
+        return hipGetLastError();
+    };
+    if (layout == kWide && src.form == kCols64) return launch(int_c<kWide>{}, int_c<kCols64>{});
+    if (layout == kNarrow && src.form == kCol32) return launch(int_c<kNarrow>{}, int_c<kCol32>{});
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_probe_outer(const TableDev &t, int layout, const SrcDev &src, const OutDev &out,

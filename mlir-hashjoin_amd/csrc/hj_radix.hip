@@ -128,6 +128,8 @@ __device__ __forceinline__ typename Row<WIDE>::T load_row(const SrcDev &s, long 
         return ((const typename R::T *)s.key)[row];
     } else if constexpr (FORM == kCol32) {
         return R::make((u64)(unsigned)((const int *)s.key)[row], (u64)(s.row_base + row));
+    } else if constexpr (FORM == kKeyRow64) {
+        return R::make(((const u64 *)s.key)[row], (u64)row);
     } else {   // kCols64
         return R::make(((const u64 *)s.key)[row], ((const u64 *)s.pay)[row]);
     }
@@ -581,6 +583,22 @@ __global__ __launch_bounds__(NT) void k_pass(PassArgs a) {
                 }
                 // (one assignment per element: stores in both branches made
                 // the compiler keep br in scratch memory)
+                br[2 * i] = v0 ? 0u : 0xFFFFFFFFu;
+                br[2 * i + 1] = v1 ? 0u : 0xFFFFFFFFu;
+            }
+        } else if constexpr (WIDE && FORM == kKeyRow64) {
+            // kCols64's load shape with the row index for the payload column:
+            // one 16-B key load per two rows, nothing else read
+            const u64 *kc = (const u64 *)a.in.key;
+#pragma unroll
+            for (int i = 0; i < IT / 2; ++i) {
+                const u64 r = tlo + 2ull * ((u64)i * kPassThreads + threadIdx.x);
+                const bool v0 = r < a.n, v1 = r + 1 < a.n;
+                ulonglong2 k2 = make_ulonglong2(0ull, 0ull);
+                if (a.cols_aligned && v1) k2 = ld_s<kNtPassLd>((const ulonglong2 *)(kc + r));
+                else if (v0) k2 = make_ulonglong2(kc[r], v1 ? kc[r + 1] : 0ull);
+                row[2 * i] = v0 ? R::make(k2.x, r) : R::zero();
+                row[2 * i + 1] = v1 ? R::make(k2.y, r + 1) : R::zero();
                 br[2 * i] = v0 ? 0u : 0xFFFFFFFFu;
                 br[2 * i + 1] = v1 ? 0u : 0xFFFFFFFFu;
             }
@@ -3230,6 +3248,192 @@ __global__ __launch_bounds__(NT, WPS) void k_join_exists(JoinArgs a, unsigned an
     }
 }
 
+// --------------------------------------------------------------- lookup join
+// Positional lookup over the work items: for each S row, the smallest (signed)
+// payload and the number of the R rows with its key, stored at the row index
+// the S row carries as its payload (radix_lookup).  k_join_exists' structure
+// -- its work map, its sub-chunks of S rows in registers, its build rounds of
+// RCAP = 5120 rows into 2^13 slots holding each key once, its
+// sub-chunks-outermost path when a partition's build side is more than one
+// round -- with two more words per slot: the running minimum payload (LDS
+// atomicMin: 64-bit signed for int64 rows, the 32-bit row id for i32 rows) and
+// the count of the round's rows with that key.  A round holds at most 5120
+// rows, so its counts fit 16 bits: two slots share a 32-bit word and an insert
+// adds 1 or 1 << 16 to it (no carry can reach the neighbour).  int64 rows:
+// 64 + 64 + 16 = 144 KiB, i32 rows 64 + 32 + 16 = 112 KiB: ONE workgroup per
+// CU (4 waves per SIMD), where k_join_exists runs two.  The alternative, 2^12
+// slots and two workgroups, halves the round to 2560 rows, and the planner's
+// ~4096-row partitions would then take two rounds and re-read R once per
+// sub-chunk.  INT64_MIN build keys (wide) are counted and minimised in two LDS
+// words of their own beside the table.
+// A probing lane adds the round's count to its row's and keeps the minimum in
+// registers; after the last round it stores both at the row's index (bounded
+// by n).  Rows of an item without build rows store (null, 0): the anti map
+// keeps those items, so every S row is written by this kernel.  No cursor, no
+// ballots, no emit barriers: the rows with a partner are summed per lane and
+// added to the counter once per wave when the workgroup has run out of items.
+constexpr int kLookupNT = 1024, kLookupSI = 3, kLookupWPS = 4;
+// the scattered result stores are plain: with the payload column alone the
+// kernel took 12.98 ms with non-temporal stores against 12.19 ms (and 12.46 in
+// another process) at 2^28 x 2^28 (profiles/lookup_probe_stores_ab.jsonl,
+// profiles/lookup_probe.jsonl)
+constexpr bool kNtLookupSt = false;
+template <bool WIDE, int NT, int SI, int WPS>
+__global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cnt, u64 null_pay, u64 n) {
+    typedef Row<WIDE> R;
+    typedef typename R::T T;
+    typedef typename std::conditional<WIDE, u64, unsigned>::type PT;          // output element, LDS payload word
+    typedef typename std::conditional<WIDE, long long, unsigned>::type MT;    // its order (row ids are < 2^31)
+    constexpr int TS = 1 << kExistsTableLog;
+    constexpr unsigned kMask = TS - 1;
+    constexpr int RCAP = TS * 5 / 8;          // build rows per round
+    constexpr int RI = RCAP / NT;             // build rows per thread per round
+    constexpr int NW = NT / 64;
+    constexpr unsigned rb = (unsigned)RCAP >> kRunLog;         // runs per build round
+    constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;  // runs per sub-chunk
+    static_assert(RI * NT == RCAP, "a build round must load exactly RCAP rows");
+    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
+    static_assert(RCAP < 65536, "a round's count of one key must fit 16 bits");
+    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    constexpr MT kMaxPay = WIDE ? (MT)0x7fffffffffffffffll : (MT)0xffffffffu;
+    __shared__ u64 tkey[TS];
+    __shared__ MT tpay[TS];
+    __shared__ unsigned tcnt[TS / 2];
+    __shared__ unsigned s_nullc;
+    __shared__ MT s_nullmin;
+
+    const unsigned total = a.work_start[a.P];
+    if (blockIdx.x >= total) return;
+    const T *rrows = (const T *)a.r;
+    const T *srows = (const T *)a.s;
+    PT *orr = (PT *)a.out_r;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
+    const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
+    unsigned hits = 0;
+
+    for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
+        const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
+        const bool rounds = it.r_hi - it.r_lo > (u64)rb;   // more than one build round
+        bool built = false;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += subb) {
+            const u64 shi = sb + subb < it.s_hi ? sb + subb : it.s_hi;
+            T sv[SI];
+            unsigned sok = 0;
+            unsigned cnt[SI];
+            MT best[SI];
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                const u64 li = sb + (u64)i * NW + wave;
+                const u64 e = li < shi ? sload(a.s_runs + li) : 0ull;
+                cnt[i] = 0u;
+                best[i] = kMaxPay;
+                if (off < (unsigned)(e & 127u)) {
+                    sv[i] = ld_s<kNtJoinLd>(srows + (e >> 7) + off);
+                    sok |= 1u << i;
+                } else {
+                    sv[i] = R::zero();
+                }
+            }
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += rb) {
+                if (rounds || !built) {
+                    // ---- build rows of runs [r0, rhi): each key once, with its minimum payload and count
+                    const u64 rhi = r0 + rb < it.r_hi ? r0 + rb : it.r_hi;
+                    T br[RI];
+                    unsigned rok = 0;
+#pragma unroll
+                    for (int i = 0; i < RI; ++i) {
+                        const u64 li = r0 + (u64)i * NW + wave;
+                        const u64 e = li < rhi ? sload(a.r_runs + li) : 0ull;
+                        br[i] = R::zero();
+                        if (off < (unsigned)(e & 127u)) {
+                            br[i] = rrows[(e >> 7) + off];
+                            rok |= 1u << i;
+                        }
+                    }
+                    __syncthreads();   // the previous table's probes are done
+                    for (int j = threadIdx.x; j < TS / 2; j += NT)
+                        ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+                    for (int j = threadIdx.x; j < TS; j += NT) tpay[j] = kMaxPay;
+                    for (int j = threadIdx.x; j < TS / 2; j += NT) tcnt[j] = 0u;
+                    if (threadIdx.x == 0) {
+                        s_nullc = 0u;
+                        s_nullmin = kMaxPay;
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int i = 0; i < RI; ++i) {
+                        if (!((rok >> i) & 1u)) continue;
+                        const u64 key = R::key(br[i]);
+                        const MT pay = (MT)R::pay(br[i]);
+                        if (WIDE && key == kEmptyKey64) {
+                            atomicAdd(&s_nullc, 1u);
+                            atomicMin(&s_nullmin, pay);
+                            continue;
+                        }
+                        unsigned h = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                        while (true) {   // ends at EMPTY (claimed) or at the key itself
+                            const u64 old = atomicCAS(&tkey[h], kEmpty, key);
+                            if (old == kEmpty || old == key) break;
+                            h = (h + 1) & kMask;
+                        }
+                        atomicMin(&tpay[h], pay);
+                        atomicAdd(&tcnt[h >> 1], 1u << ((h & 1u) * 16u));
+                    }
+                    __syncthreads();
+                    built = true;
+                }
+                // ---- probe every row of the sub-chunk: first slots read before any is resolved
+                unsigned hp[SI];
+                u64 e0[SI];
+                unsigned open = sok;
+                const unsigned nullc = s_nullc;
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    const u64 key = R::key(sv[i]);
+                    if (WIDE && key == kEmptyKey64) {
+                        if (((open >> i) & 1u) && nullc) {
+                            const MT m = s_nullmin;
+                            cnt[i] += nullc;
+                            best[i] = m < best[i] ? m : best[i];
+                        }
+                        open &= ~(1u << i);
+                    }
+                    hp[i] = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                    e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
+                }
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    if (!((open >> i) & 1u)) continue;
+                    const u64 key = R::key(sv[i]);
+                    unsigned h = hp[i];
+                    u64 e = e0[i];
+                    while (e != kEmpty && e != key) {
+                        h = (h + 1) & kMask;
+                        e = tkey[h];
+                    }
+                    if (e == key) {
+                        const MT m = tpay[h];
+                        cnt[i] += (tcnt[h >> 1] >> ((h & 1u) * 16u)) & 0xffffu;
+                        best[i] = m < best[i] ? m : best[i];
+                    }
+                }
+            }
+            // ---- store this sub-chunk's rows at their own indices
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                if (!((sok >> i) & 1u)) continue;
+                const u64 row = R::pay(sv[i]);
+                if (row >= n) continue;   // (never: the partition wrote row indices below n)
+                if (orr) st_s<kNtLookupSt>(orr + row, cnt[i] ? (PT)best[i] : (PT)null_pay);
+                if (out_cnt) st_s<kNtLookupSt>(out_cnt + row, (int)cnt[i]);
+                hits += cnt[i] ? 1u : 0u;
+            }
+        }
+    }
+    const unsigned x = wave_incl_add(hits);
+    if (off == 63 && x) atomicAdd(a.counter, (u64)x);
+}
+
 // --------------------------------------------------------------- join shapes
 // One product kernel per (row width, shape), chosen from facts known when
 // the join is launched -- never from an earlier join's statistics:
@@ -3659,6 +3863,7 @@ hipError_t radix_passes(const SrcDev &src, u64 n, bool wide, const RadixPlan &pl
                 else HJ_PASS(false, kBucketed);
             } else if (wide) {
                 if (src.form == kCols64) HJ_PASS(true, kCols64);
+                else if (src.form == kKeyRow64) HJ_PASS(true, kKeyRow64);
                 else HJ_PASS(true, kPackedRow);   // kPacked64 input == packed row layout
             } else {
                 if (src.form == kCol32) HJ_PASS(false, kCol32);
@@ -3956,6 +4161,34 @@ hipError_t exists_stage(bool wide, bool anti, const unsigned long long *null_pay
 hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r,
                         const BucketSet &s, const OutDev &out, hipStream_t st) {
     return exists_stage(wide, anti, nullptr, pl, ws, r, s, out, st);
+}
+
+// k_join_lookup over the exists stage's anti work map (the same sub-chunk, so
+// the work area covers it as it covers that stage's): every non-empty S
+// partition is an item, build rows or not.  One workgroup per CU (its table).
+hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, const RadixPlan &pl, const RadixWork &ws,
+                        const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt, hipStream_t st) {
+    static_assert(kLookupNT * kLookupSI == kExistsNT * kExistsSI, "the lookup's items are the exists stage's");
+    const int P = 1 << pl.total_bits;
+    const unsigned pg = (unsigned)cu_count();
+    WorkMapSpec m;
+    m.subb = (unsigned)((kLookupNT * kLookupSI) >> kRunLog);
+    m.grid = pg;
+    m.r_gates = false;
+    m.counter = out.counter;
+    const WorkMap w = work_map(pl, P, ws, r, &s, m, st);
+    if (!w.items) return hipErrorInvalidValue;
+    JoinArgs a = join_args(wide, pl, r, s, P, ws, out, nullptr, nullptr);
+    a.tshift = 64 - pl.skip - pl.total_bits - kExistsTableLog;
+    const unsigned grid = w.items < pg ? w.items : pg;
+    const u64 rows = (u64)(n > 0 ? n : 0);
+    if (wide)
+        hipLaunchKernelGGL((k_join_lookup<true, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, a,
+                           cnt, (u64)null_pay, rows);
+    else
+        hipLaunchKernelGGL((k_join_lookup<false, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, a,
+                           cnt, (u64)null_pay, rows);
+    return hipGetLastError();
 }
 
 // The outer join's second stage.  Its work map is built in the work area

@@ -27,6 +27,7 @@ HJ_STRATEGY_RADIX = 2
 HJ_EXISTS_SEMI = 0
 HJ_EXISTS_ANTI = 1
 HJ_JOIN_KERNEL_EXISTS = 6
+HJ_JOIN_KERNEL_LOOKUP = 7
 HJ_OUTER_BUILD = 1
 HJ_OUTER_FULL = 2
 
@@ -85,6 +86,8 @@ def _load():
         "hj_dev_exists_i64": (_int, [_vp, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_exists_tuples_i64": (_int, [_vp, _int, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_exists_i32": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_lookup_i64": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+        "hj_dev_lookup_i32": (_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp, _vp]),
         "hj_dev_probe_outer_i64": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_probe_outer_tuples_i64": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_probe_outer_i32": (_int, [_vp, _vp, _i64, _i64, C.c_int32, _vp, _vp, _i64, _vp, _vp]),

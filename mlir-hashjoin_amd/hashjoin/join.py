@@ -118,13 +118,14 @@ class HashJoin:
         return bool(r)
 
     JOIN_KERNELS = {1: "k_join_b", 2: "k_join_u", 3: "k_join_u_stream", 4: "k_join_grp", 5: "k_join",
-                    6: "k_join_exists"}
+                    6: "k_join_exists", 7: "k_join_lookup"}
 
     @property
     def join_kernel(self):
         """Kernel of the last radix join (hj_ctx_join_kernel): 'k_join_b',
         'k_join_u_stream', 'k_join_grp', 'k_join', 'k_join_exists' (a radix
-        semi- / anti-join), or None (no radix join)."""
+        semi- / anti-join), 'k_join_lookup' (a radix lookup), or None (no radix
+        join)."""
         r = lib.hj_ctx_join_kernel(self._ctx)
         if r < 0:
             check(r, "hj_ctx_join_kernel")
@@ -302,6 +303,51 @@ class HashJoin:
     def anti_join(self, rkey, skey, spay=None, rpay=None, with_keys=False, capacity=None, stream=None):
         """As semi_join, for the S rows whose key R does not hold."""
         return self._exists_join("anti", rkey, skey, spay, rpay, with_keys, capacity, stream)
+
+    # ---- positional lookup probe (hj.h "Positional lookup probe")
+    def probe_lookup(self, skey, out_r=None, out_cnt=None, null=-1, count=None, stream=None):
+        """One result per probe row, in input order: out_r[j] = the smallest R
+        payload (i32: R row id) among the R rows with key skey[j], or `null`
+        written verbatim; out_cnt[j] (int32) = how many there are.  Either
+        output may be None, not both; each has the length of skey at least and
+        only its first len(skey) elements are written.  `count` (int64 device
+        tensor) receives the number of S rows with a partner.  Returns count."""
+        _need_cuda(skey, out_r, out_cnt)
+        st = _stream(self.device, stream)
+        count = self._count if count is None else count
+        n = skey.numel()
+        if skey.dtype not in (torch.int64, torch.int32):
+            raise TypeError("keys must be int32 or int64")
+        if out_r is None and out_cnt is None and n > 0:
+            raise ValueError("lookup needs out_r or out_cnt (count_exists counts the rows with a partner)")
+        if out_r is not None and (out_r.dtype != skey.dtype or out_r.numel() < n):
+            raise ValueError("out_r carries the probe key's dtype and at least its length")
+        if out_cnt is not None and (out_cnt.dtype != torch.int32 or out_cnt.numel() < n):
+            raise ValueError("out_cnt is an int32 column of at least the probe key's length")
+        f, name = ((lib.hj_dev_lookup_i64, "hj_dev_lookup_i64") if skey.dtype == torch.int64
+                   else (lib.hj_dev_lookup_i32, "hj_dev_lookup_i32"))
+        check(f(self._ctx, _ptr(skey), n, int(null), _ptr(out_r), _ptr(out_cnt), _ptr(count), st), name)
+        return count
+
+    def lookup(self, rkey, rpay, skey, null=-1, with_counts=False, stream=None):
+        """Build R, then probe_lookup: out_r of length |S| (the R payload each S
+        key maps to, the smallest when R repeats the key, `null` when R lacks
+        it), or (out_r, out_cnt) if with_counts.  int64 keys with rpay None:
+        the payload is R's row index (the id -> index mapping); int32 keys
+        always carry R's row ids."""
+        self.probe_hint(skey.numel())
+        try:
+            if rkey.dtype == torch.int64 and rpay is None:
+                rpay = torch.arange(rkey.numel(), dtype=torch.int64, device=self.device)
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+        out_r = torch.empty(skey.numel(), dtype=skey.dtype, device=self.device)
+        out_cnt = torch.empty(skey.numel(), dtype=torch.int32, device=self.device) if with_counts else None
+        m = int(self.probe_lookup(skey, out_r, out_cnt, null=null, stream=stream).item())
+        if m < 0:   # bit 63 (hj.h)
+            raise RuntimeError("hash join: internal work list overflow (count flagged)")
+        return (out_r, out_cnt) if with_counts else out_r
 
     # ---- probe-side outer join (hj.h "Probe-side outer join")
     def probe_outer(self, skey, spay=None, out_r=None, out_s=None, null=-1, count=None, row_base=0, stream=None):
