@@ -151,6 +151,8 @@ int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 #define HJ_JOIN_KERNEL_EXISTS 6
 /* k_join_lookup: the last probe was a radix positional lookup (hj_dev_lookup_*) */
 #define HJ_JOIN_KERNEL_LOOKUP 7
+/* k_join_group: the last probe was a radix group probe (hj_dev_group_*) */
+#define HJ_JOIN_KERNEL_GROUP 8
 int hj_ctx_join_kernel(hj_ctx *ctx);
 
 /* ------------------------------------------------------------ device phases
@@ -265,6 +267,73 @@ int hj_dev_lookup_i64(hj_ctx *ctx, const int64_t *skey, int64_t n, int64_t null_
                       int64_t *out_r, int32_t *out_cnt, uint64_t *d_count, void *stream);
 int hj_dev_lookup_i32(hj_ctx *ctx, const int32_t *skey, int64_t n, int32_t null_row,
                       int32_t *out_r, int32_t *out_cnt, uint64_t *d_count, void *stream);
+
+/* Group probe (the group join of a query engine: join, then aggregate per
+ * build row -- SELECT r.id, count(*), sum(s.v), min(s.v), max(s.v) ... GROUP
+ * BY r.id, TPC-H Q13's shape, a segment reduction) over the table an ordinary
+ * hj_dev_build_* left.  For the built relation R and the probe relation S with
+ * a value column, let G(i) = {j : S.key[j] == R.key[i]}; then for R row i
+ *   cnt(i) = |G(i)|,
+ *   sum(i) = the sum of S.val[j] over G(i) in two's-complement int64 (it wraps),
+ *   min(i) / max(i) = the signed extremes of S.val over G(i).
+ * The result holds one row (R.pay[i], cnt, sum, min, max) per R row, every
+ * column aligned at the same index:
+ *   HJ_GROUP_MATCHED: only the R rows with cnt > 0;
+ *   HJ_GROUP_ALL:     every R row; an empty group gives cnt = 0, sum = 0 and
+ *                     min = max = null_val (i32: null_row) written verbatim.
+ * Every copy of a repeated build key is a row of its own and carries the whole
+ * group's aggregates (what join-then-group-by-R-row gives); two S rows with
+ * equal keys are two contributions.  Row order is unspecified; the result is
+ * otherwise a function of the data alone -- integer add, min and max commute --
+ * and bit-equal across strategies, kernels and runs.  INT64_MIN is a key like
+ * any other, INT64_MIN and INT64_MAX are values like any other: validity comes
+ * from cnt, never from a sentinel.  R empty: M = 0.  S empty: MATCHED gives
+ * M = 0, ALL every R row as an empty group.
+ * i32: the S value is the row id row_base + row, as in every i32 entry point,
+ * so out_min / out_max are the first and last partner's row and out_sum is an
+ * int64 sum of row ids (defined, rarely wanted); n > INT32_MAX is HJ_ERR_ARG.
+ * Any output column may be NULL and is then neither computed nor stored; sval
+ * may be NULL when none of sum / min / max is asked for.  out_cap == 0 with all
+ * five outputs NULL is the count-only form; out_cap > 0 with all five NULL is
+ * HJ_ERR_ARG, and so is out_cap == 0 with any of them non-NULL.  d_count = M,
+ * the exact number of result rows, even when M > out_cap: rows past out_cap
+ * are dropped and nothing is written at or past index out_cap in any column;
+ * bit 63 as above.
+ * Errors in hj_dev_probe_full_*'s order: a null context (HJ_ERR_ARG); a kind
+ * other than the two (HJ_ERR_ARG); no build of that layout (HJ_ERR_STATE); a
+ * null count pointer, a bad relation, bad outputs (HJ_ERR_ARG).  GLOBAL keeps
+ * per-slot accumulators beside the table (at most 32 B per slot, allocated by
+ * the call, grow-only, or ahead by hj_ctx_reserve_group): HJ_ERR_NOMEM when
+ * they do not fit.
+ * Asynchronous on the stream, kernels (and the counter's one-word memset) only
+ * once hj_ctx_reserve / hj_ctx_reserve_probe / hj_ctx_reserve_group sized the
+ * workspace (graph-capturable).  The strategy is chosen exactly as for
+ * hj_dev_probe_* (the AUTO dual build included) and hj_ctx_strategy_used
+ * reports it; the probe timing works as for hj_dev_exists_* (RADIX: [4] S's
+ * partition, [5] the rest) and hj_ctx_join_kernel returns HJ_JOIN_KERNEL_GROUP
+ * after a radix one.  Nothing the build left is written -- not the table, R's
+ * partition, the side list, the "build keys repeat" flag or the mark bitmap:
+ * group, lookup, inner, semi, anti, outer, build and full probes of one build
+ * may follow each other in any order and each returns what it returned before.
+ * Valid after hj_dev_build_routed_i64 over unrouted rows, as
+ * hj_dev_probe_full_i64 is; there is no routed bin-range form (a bin range
+ * sees part of S). */
+#define HJ_GROUP_MATCHED 0
+#define HJ_GROUP_ALL 1
+int hj_dev_group_i64(hj_ctx *ctx, int kind, const int64_t *skey, const int64_t *sval, int64_t n, int64_t null_val,
+                     int64_t *out_r, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                     int64_t out_cap, uint64_t *d_count, void *stream);
+/* rows as packed 16-B {key, value} tuples */
+int hj_dev_group_tuples_i64(hj_ctx *ctx, int kind, const int64_t *tuples, int64_t n, int64_t null_val,
+                            int64_t *out_r, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                            int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_group_i32(hj_ctx *ctx, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t null_row,
+                     int32_t *out_r, int32_t *out_cnt, int64_t *out_sum, int32_t *out_min, int32_t *out_max,
+                     int64_t out_cap, uint64_t *d_count, void *stream);
+/* Sizes the GLOBAL group probe's accumulators for builds of up to
+ * max_build_rows rows of key_bits (32 / 64) keys, so that hj_dev_group_*
+ * allocates nothing (a no-op where such a build would take the radix join). */
+int hj_ctx_reserve_group(hj_ctx *ctx, int64_t max_build_rows, int key_bits);
 
 /* Probe-side outer join (LEFT OUTER with the probe relation on the left) over
  * the table an ordinary hj_dev_build_* left: one build serves inner, semi,

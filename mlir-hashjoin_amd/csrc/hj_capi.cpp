@@ -148,6 +148,7 @@ struct hj_ctx {
     SetBufs rset, sset, tset;   // R and S final partitions, ping set of multi-pass plans
     Buf nb, pcur, rcur, tile_start, tile_owner, tdesc, wstart, work_start, work_desc, scan_sums, scan_state, raw_cnt;
     Buf slow;   // global-table probe: tiles for the general path
+    Buf acc_cnt, acc_sum, acc_min, acc_max;   // global-table group probe: per-slot accumulators (hj::GroupAcc)
     Buf rows_kx, rows_ky, rows_px, rows_py;   // row materialisation: key columns, pair row ids
     Buf sel_tiles, sel_sums;                  // selection: per-tile counts (then offsets), scan sums
     Buf route_hist, route_sums;               // folded routing: (bin, workgroup) slot bases, scan sums
@@ -219,6 +220,7 @@ struct hj_ctx {
     bool join_ran = false, join_wide = false, join_stream = false;
     bool exists_ran = false;   // the last probe was a radix semi- / anti-join (HJ_JOIN_KERNEL_EXISTS)
     bool lookup_ran = false;   // the last probe was a radix lookup (HJ_JOIN_KERNEL_LOOKUP)
+    bool group_ran = false;    // the last probe was a radix group probe (HJ_JOIN_KERNEL_GROUP)
     bool routed = false;   // the current build came from hj_dev_build_routed_i64 (plan.skip owner bits)
     bool dup_checked = false;   // hj_ctx_build_has_duplicates ran its DETECT build for this build
     bool host_building = false;  // host_join's build is running (do_build keeps the memo's input copies)
@@ -582,7 +584,7 @@ int begin_build(hj_ctx *c, int layout, int64_t n, int used, bool dual, bool rout
     c->routed = routed;
     c->plan = plan;
     c->probe_used = -1;
-    c->join_ran = c->exists_ran = c->lookup_ran = c->dup_checked = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = c->dup_checked = false;
     // (hj_count_*'s kept table is gone; a host join's own build keeps the
     // EXACT copies it has just taken of its inputs)
     if (c->host_building) c->memo.valid = false;
@@ -642,7 +644,8 @@ int do_build(hj_ctx *c, int layout, const hj::SrcDev &src, hipStream_t st) {
 }
 
 // One probe of the current build, after the entry point's argument checks.
-enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter, kProbeBuild, kProbeFull, kProbeLookup };
+enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter, kProbeBuild, kProbeFull, kProbeLookup,
+                 kProbeGroup };
 struct ProbeReq {
     RadixSrc in;       // S; routed: bins [bin0, bin0 + in.nbins) of the build's first pass
     int bin0 = 0;
@@ -652,7 +655,19 @@ struct ProbeReq {
     ProbeKind kind = kProbeInner;
     unsigned long long null_pay = 0;   // outer, full, lookup: the R payload of an S row without a partner (outer, full: out.cap == 0 counts only)
     unsigned long long null_s = 0;     // build, full: the S payload of an R row without a partner
+    hj::GroupOut grp{};                // group: the result columns, the kind and the null value (its counter is out.counter)
 };
+
+// The global-table group probe's accumulators for a table of 2^bits slots (and
+// the side list's entry): the count always, the others when asked for.
+int ensure_group_acc(hj_ctx *c, int bits, int layout, bool sum, bool mn, bool mx) {
+    const size_t entries = (size_t(1) << bits) + 1, small = layout == kWide ? 8 : 4;
+    HJ_TRY(ensure_buf(c->acc_cnt, entries * small));
+    if (sum) HJ_TRY(ensure_buf(c->acc_sum, entries * 8));
+    if (mn) HJ_TRY(ensure_buf(c->acc_min, entries * small));
+    if (mx) HJ_TRY(ensure_buf(c->acc_max, entries * small));
+    return HJ_OK;
+}
 
 int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
     HJ_TRY(set_device(c));
@@ -663,7 +678,7 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
     const bool r_nulls = q.kind == kProbeBuild || q.kind == kProbeFull;
     const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
     c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
-    c->join_ran = c->exists_ran = c->lookup_ran = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = false;
     if (!radix) {
         HJ_HIP(hipMemsetAsync(q.out.counter, 0, sizeof(uint64_t), st));
         record(c, kEvProbe0, st);
@@ -671,6 +686,11 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
             HJ_HIP(hj::launch_probe_exists(table_dev(c), c->layout, src, q.out, q.kind == kProbeAnti, st));
         } else if (q.kind == kProbeLookup) {
             HJ_HIP(hj::launch_probe_lookup(table_dev(c), c->layout, src, q.out, q.out_cnt, q.null_pay, st));
+        } else if (q.kind == kProbeGroup) {
+            HJ_TRY(ensure_group_acc(c, c->bits, c->layout, q.grp.sum, q.grp.mn, q.grp.mx));
+            const hj::GroupAcc acc{c->acc_cnt.p, q.grp.sum ? (unsigned long long *)c->acc_sum.p : nullptr,
+                                   q.grp.mn ? c->acc_min.p : nullptr, q.grp.mx ? c->acc_max.p : nullptr};
+            HJ_HIP(hj::launch_group(table_dev(c), c->layout, src, acc, q.grp, st));
         } else {
             const size_t slow_cap = hj::probe_tiles(src.n);
             HJ_TRY(ensure_buf(c->slow, slow_cap * sizeof(unsigned)));
@@ -696,8 +716,9 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
         HJ_TRY(ensure_radix_scratch(c, c->sset, src.n, wide, c->plan, q.in.nsrc));
         trace("probe: workspace", st, (long long)c->sset.max_buckets);
         record(c, kEvProbe0, st);
-        if (q.kind == kProbeLookup && wide) {
+        if ((q.kind == kProbeLookup || (q.kind == kProbeGroup && !src.pay && src.form == hj::kCols64)) && wide) {
             // S's rows carry their index through the passes: the key column alone is read
+            // (a group probe without a value column: no aggregate reads the payload)
             RadixSrc in = q.in;
             in.src.form = hj::kKeyRow64;
             in.src.pay = nullptr;
@@ -722,6 +743,9 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
             HJ_RADIX(c, st, hj::radix_lookup(wide, q.null_pay, src.n, c->plan, radix_work(c), r, bucket_set(c->sset),
                                              q.out, q.out_cnt, st));
             c->lookup_ran = true;
+        } else if (q.kind == kProbeGroup) {
+            HJ_RADIX(c, st, hj::radix_group(wide, c->plan, radix_work(c), r, bucket_set(c->sset), q.grp, st));
+            c->group_ran = true;
         } else {
             // the kernel: a function of (row width, size ratio, build-time sample)
             o.dup_flag = c->meta + 1;
@@ -800,6 +824,31 @@ int do_lookup(hj_ctx *c, int layout, const hj::SrcDev &src, unsigned long long n
     q.out_cnt = out_cnt;
     q.kind = kProbeLookup;
     q.null_pay = null_pay;
+    return run_probe(c, q, st);
+}
+
+// Group probe (hj_dev_group_*): one row per R row with the aggregates of the S
+// rows of its key.  do_probe_full's order of checks; rel_err: the entry point
+// found its relation bad.  Any column may be null; out_cap == 0 with all five
+// null is the count-only form.  Reads what an inner probe reads.
+int do_group(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, const char *rel_err, unsigned long long null_val,
+             void *out_r, void *out_cnt, void *out_sum, void *out_min, void *out_max, int64_t cap, uint64_t *d_count,
+             hipStream_t st) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (kind != HJ_GROUP_MATCHED && kind != HJ_GROUP_ALL)
+        HJ_FAIL(HJ_ERR_ARG, "kind must be HJ_GROUP_MATCHED or HJ_GROUP_ALL");
+    if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, "probe without a matching build");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (rel_err) HJ_FAIL(HJ_ERR_ARG, rel_err);
+    if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
+    const bool any = out_r || out_cnt || out_sum || out_min || out_max;
+    if (cap < 0 || (cap > 0 && !any) || (cap == 0 && any)) HJ_FAIL(HJ_ERR_ARG, "bad output");
+    ProbeReq q;
+    q.in.src = src;
+    q.out = hj::OutDev{nullptr, nullptr, cap, (unsigned long long *)d_count};
+    q.kind = kProbeGroup;
+    q.grp = hj::GroupOut{out_r, out_cnt, out_sum, out_min, out_max, cap, (unsigned long long *)d_count, null_val,
+                         kind == HJ_GROUP_ALL ? 1 : 0};
     return run_probe(c, q, st);
 }
 
@@ -1604,7 +1653,7 @@ void hj_ctx_destroy(hj_ctx *c) {
     for (SetBufs *sb : {&c->rset, &c->sset, &c->tset})
         for (Buf *b : {&sb->rows, &sb->bbin, &sb->bfill, &sb->runs, &sb->rstart}) free_buf(*b);
     for (Buf *b : {&c->nb, &c->pcur, &c->rcur, &c->tile_start, &c->tile_owner, &c->tdesc, &c->wstart, &c->work_start, &c->work_desc, &c->scan_sums, &c->scan_state, &c->raw_cnt,
-                   &c->slow, &c->rows_kx, &c->rows_ky, &c->rows_px, &c->rows_py, &c->sel_tiles, &c->sel_sums,
+                   &c->slow, &c->acc_cnt, &c->acc_sum, &c->acc_min, &c->acc_max, &c->rows_kx, &c->rows_ky, &c->rows_px, &c->rows_py, &c->sel_tiles, &c->sel_sums,
                    &c->route_hist, &c->route_sums})
         free_buf(*b);
     for (int k = 0; k < c->ev_made; ++k)
@@ -1664,6 +1713,7 @@ int hj_ctx_join_kernel(hj_ctx *c) {
     if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
     if (c->exists_ran && c->layout >= 0) return HJ_JOIN_KERNEL_EXISTS;
     if (c->lookup_ran && c->layout >= 0) return HJ_JOIN_KERNEL_LOOKUP;
+    if (c->group_ran && c->layout >= 0) return HJ_JOIN_KERNEL_GROUP;
     if (!c->join_ran || c->layout < 0) return 0;
     HJ_TRY(set_device(c));
     unsigned long long v[2] = {0, 0};
@@ -1768,6 +1818,15 @@ int hj_ctx_reserve_probe(hj_ctx *c, int64_t max_probe_rows, int key_bits) {
     return ensure_radix_scratch(c, c->sset, max_probe_rows, key_bits == 64, c->plan);
 }
 
+int hj_ctx_reserve_group(hj_ctx *c, int64_t max_build_rows, int key_bits) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (max_build_rows < 0 || (key_bits != 32 && key_bits != 64)) HJ_FAIL(HJ_ERR_ARG, "bad reserve arguments");
+    // (the radix group probe works in the build's and hj_ctx_reserve_probe's workspace)
+    if (choose_strategy(c, max_build_rows) != HJ_STRATEGY_GLOBAL) return HJ_OK;
+    HJ_TRY(set_device(c));
+    return ensure_group_acc(c, table_bits(max_build_rows), key_bits == 64 ? kWide : kNarrow, true, true, true);
+}
+
 // ------------------------------------------------------------ device phases
 int hj_dev_build_i64(hj_ctx *c, const int64_t *rkey, const int64_t *rpay, int64_t n, void *stream) {
     return do_build(c, kWide, src_cols64(rkey, rpay, n), (hipStream_t)stream);
@@ -1831,6 +1890,30 @@ int hj_dev_lookup_i32(hj_ctx *c, const int32_t *skey, int64_t n, int32_t null_ro
                       uint64_t *d_count, void *stream) {
     return do_lookup(c, kNarrow, src_col32(skey, n, 0), (unsigned long long)(long long)null_row, out_r, out_cnt,
                      d_count, (hipStream_t)stream);
+}
+
+int hj_dev_group_i64(hj_ctx *c, int kind, const int64_t *skey, const int64_t *sval, int64_t n, int64_t null_val,
+                     int64_t *out_r, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                     int64_t out_cap, uint64_t *d_count, void *stream) {
+    // (a null value column is kept null: no kernel reads it when no aggregate of it is asked for)
+    const bool no_val = n > 0 && !sval && (out_sum || out_min || out_max);
+    return do_group(c, kWide, kind, src_cols64(skey, sval, n), no_val ? "null probe value column" : nullptr,
+                    (unsigned long long)null_val, out_r, out_cnt, out_sum, out_min, out_max, out_cap, d_count,
+                    (hipStream_t)stream);
+}
+int hj_dev_group_tuples_i64(hj_ctx *c, int kind, const int64_t *tuples, int64_t n, int64_t null_val, int64_t *out_r,
+                            int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap,
+                            uint64_t *d_count, void *stream) {
+    return do_group(c, kWide, kind, src_packed(tuples, n), nullptr, (unsigned long long)null_val, out_r, out_cnt,
+                    out_sum, out_min, out_max, out_cap, d_count, (hipStream_t)stream);
+}
+int hj_dev_group_i32(hj_ctx *c, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t null_row,
+                     int32_t *out_r, int32_t *out_cnt, int64_t *out_sum, int32_t *out_min, int32_t *out_max,
+                     int64_t out_cap, uint64_t *d_count, void *stream) {
+    const bool bad_ids = n > 0x7fffffffll || row_base < 0 || row_base + n > 0x7fffffffll;
+    return do_group(c, kNarrow, kind, src_col32(skey, n, bad_ids ? 0 : row_base),
+                    bad_ids ? "i32 row ids out of range" : nullptr, (unsigned long long)(uint32_t)null_row, out_r,
+                    out_cnt, out_sum, out_min, out_max, out_cap, d_count, (hipStream_t)stream);
 }
 
 // (the null context is reported before any other argument, as the header says)

@@ -134,6 +134,29 @@ hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src,
 // One launch; reads meta[0..1], writes no build state.
 hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, int *cnt,
                                unsigned long long null_pay, hipStream_t st);
+// The group probe's result columns (any may be null: neither computed nor
+// stored) and its per-slot accumulators of the global table.  Element types by
+// layout: wide -- every column int64; narrow -- r, cnt, mn, mx int32 and sum
+// int64 (the S value is the row id).
+struct GroupOut {
+    void *r, *cnt, *sum, *mn, *mx;
+    long long cap;                // rows the caller allocated (0: count only)
+    unsigned long long *counter;  // device u64: result rows (all of them, even past cap)
+    unsigned long long null_val;  // min / max of an empty group
+    int all;                      // 0: only the groups with a partner, 1: every R row
+};
+struct GroupAcc {                 // slots + 1 entries each (the last: the wide INT64_MIN side list's)
+    void *cnt;                    // u64 (wide) / u32 (narrow); always present
+    unsigned long long *sum;      // null: not asked for
+    void *mn, *mx;                // i64 (wide) / i32 (narrow); null: not asked for
+};
+// group probe over the global table: k_group_init (the accumulators' fill, a
+// kernel), k_probe_group (S's rows add into the accumulators of the first slot
+// holding their key; src.pay may be null when sum, mn and mx all are) and
+// k_emit_groups (one row per R row, compacted through out.counter, which the
+// caller zeroed).  Reads the table, the side list and meta[0..1]; writes none.
+hipError_t launch_group(const TableDev &t, int layout, const SrcDev &src, const GroupAcc &acc, const GroupOut &out,
+                        hipStream_t st);
 // probe-side outer join over the global table: launch_probe's pairs plus
 // (null_pay, S payload) for every S row without a partner; out.cap == 0
 // counts only; slow / slow_cap as launch_probe's
@@ -263,6 +286,15 @@ hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWo
 // r, writes neither it nor the repeat flag.
 hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, const RadixPlan &pl, const RadixWork &ws,
                         const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt, hipStream_t st);
+// Group probe over the partitioned relations (k_join_group): one row per R row
+// with the count, wrapping sum and signed extremes of the S payloads of its
+// key.  The two bucket sets exchanged as in radix_unmatched_build: S's rows are
+// aggregated per key in the LDS table, R's rows look their key up and are
+// compacted through out.counter (zeroed by the work map).  The map cuts R's
+// runs (ws must cover r.max_runs: every build sizes it so); out.all keeps the
+// R partitions without S rows.  Reads r and s, writes neither nor the repeat flag.
+hipError_t radix_group(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
+                       const GroupOut &out, hipStream_t st);
 // The outer join's second stage, after radix_join over the same r and s (and
 // out): the S rows without a partner in r are appended behind the pairs as
 // (null_pay, S payload) -- radix_exists' anti probe whose work map leaves

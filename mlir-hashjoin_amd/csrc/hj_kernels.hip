@@ -11,6 +11,7 @@
 // plus the exists probes (k_probe_exists), the positional lookup probe
 // (k_probe_lookup), the outer probe (k_probe_outer),
 // the build-side outer stages (k_probe_mark, k_emit_unmatched),
+// the group probe (k_group_init, k_probe_group, k_emit_groups),
 // the radix partition used by the
 // multi-GPU exchange, the selection, the counter-based generators of the
 // benchmark inputs and the copy floors.
@@ -1134,6 +1135,214 @@ __global__ __launch_bounds__(kBlock) void k_emit_unmatched(TableDev t, OutDev ou
     }
 }
 
+// ------------------------------------------------------------------ group probe
+// Join, then aggregate per build row: per-slot accumulators beside the slot
+// array (GroupAcc: separate arrays of slots + 1 entries, so an aggregate nobody
+// asked for does not exist; the last entry is the wide side list's), three
+// launches and no scratch.
+//   k_group_init   the fill: count and sum 0, min the largest and max the
+//                  smallest value of the type.
+//   k_probe_group  k_probe_exists' shape over S's keys and values: each row
+//                  walks to the FIRST slot of its chain holding its key and
+//                  issues its atomics there (results unused: non-returning),
+//                  only for the aggregates asked for.  A row without a partner
+//                  does nothing.  A wide INT64_MIN key adds into the last
+//                  entry when the side list holds a row.
+//   k_emit_groups  k_emit_unmatched's shape over the slots: an occupied slot
+//                  finds the accumulators of its key's first copy -- itself
+//                  when the repeat flag meta[1] is clear, else the first equal
+//                  key on the walk from the key's home slot -- applies the
+//                  kind and writes the columns passed; workgroup 0 appends the
+//                  side list's rows with the last entry's aggregates.
+// Element types: Lay<L>::out_t for r, count, min and max, int64 for the sum.
+template <int L>
+struct GroupTypes;
+template <>
+struct GroupTypes<kWide> {
+    using cnt_t = unsigned long long;
+    using ext_t = long long;
+    static constexpr ext_t kMin = (ext_t)0x8000000000000000ull, kMax = 0x7fffffffffffffffll;
+};
+template <>
+struct GroupTypes<kNarrow> {
+    using cnt_t = unsigned;
+    using ext_t = int;
+    static constexpr ext_t kMin = (ext_t)0x80000000u, kMax = 0x7fffffff;
+};
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_group_init(GroupAcc acc, unsigned long long n) {
+    using GT = GroupTypes<L>;
+    typename GT::cnt_t *cnt = (typename GT::cnt_t *)acc.cnt;
+    typename GT::ext_t *mn = (typename GT::ext_t *)acc.mn, *mx = (typename GT::ext_t *)acc.mx;
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+    for (unsigned long long j = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride) {
+        cnt[j] = 0;
+        if (acc.sum) acc.sum[j] = 0ull;
+        if (mn) mn[j] = GT::kMax;
+        if (mx) mx[j] = GT::kMin;
+    }
+}
+
+template <int L, int FORM>
+__global__ __launch_bounds__(kBlock) void k_probe_group(TableDev t, SrcDev src, GroupAcc acc) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using GT = GroupTypes<L>;
+    typename GT::cnt_t *cnt = (typename GT::cnt_t *)acc.cnt;
+    typename GT::ext_t *mn = (typename GT::ext_t *)acc.mn, *mx = (typename GT::ext_t *)acc.mx;
+    const slot_t *sl = (const slot_t *)t.slots;
+    const bool vals = acc.sum || mn || mx;   // (uniform) else only the key is read
+    const bool side_rows = L == kWide && t.meta[0] != 0ull;   // the build side holds an INT64_MIN key
+    const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long K[kProbeItems], V[kProbeItems], H[kProbeItems];
+        unsigned walk = 0, found = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const long long row = (long long)q * kProbeTile + (long long)i * kBlock + threadIdx.x;
+            K[i] = V[i] = 0ull;
+            if (row < src.n) {
+                if (vals) {
+                    const Tuple tp = load_src<FORM>(src, row);
+                    K[i] = tp.k;
+                    V[i] = tp.p;
+                } else {
+                    K[i] = load_key<FORM>(src, row);
+                }
+                if (LY::null_key(K[i])) found |= side_rows ? 1u << i : 0u;
+                else walk |= 1u << i;
+            }
+        }
+        slot_t S[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            H[i] = LY::null_key(K[i]) ? t.mask + 1ull : slot_of(K[i], t.shift);
+            if ((walk >> i) & 1u) S[i] = sl[H[i]];
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((walk >> i) & 1u)) continue;
+            slot_t sv = S[i];
+            unsigned long long hh = H[i];
+            while (!LY::empty(sv) && LY::key(sv) != K[i]) {
+                hh = (hh + 1) & t.mask;
+                sv = sl[hh];
+            }
+            H[i] = hh;
+            if (!LY::empty(sv)) found |= 1u << i;
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((found >> i) & 1u)) continue;
+            atomicAdd(cnt + H[i], (typename GT::cnt_t)1);
+            if (acc.sum) atomicAdd(acc.sum + H[i], V[i]);
+            if (mn) atomicMin(mn + H[i], (typename GT::ext_t)V[i]);
+            if (mx) atomicMax(mx + H[i], (typename GT::ext_t)V[i]);
+        }
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_emit_groups(TableDev t, GroupAcc acc, GroupOut out) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    using GT = GroupTypes<L>;
+    constexpr int NW = kBlock / 64;
+    __shared__ unsigned long long st_base;
+    __shared__ unsigned s_cw[kProbeItems * NW];
+    const typename GT::cnt_t *cnt = (const typename GT::cnt_t *)acc.cnt;
+    const typename GT::ext_t *mn = (const typename GT::ext_t *)acc.mn, *mx = (const typename GT::ext_t *)acc.mx;
+    const slot_t *sl = (const slot_t *)t.slots;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long cap = t.mask + 1ull;
+    const unsigned long long nt = (cap + kProbeTile - 1) / kProbeTile;
+    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+    const bool unique = (__hip_atomic_load(&t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull);
+    out_t *orr = (out_t *)out.r, *ocnt = (out_t *)out.cnt, *omin = (out_t *)out.mn, *omax = (out_t *)out.mx;
+    long long *osum = (long long *)out.sum;
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long P[kProbeItems], F[kProbeItems];
+        typename GT::cnt_t C[kProbeItems];
+        unsigned found = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const unsigned long long j = q * kProbeTile + (unsigned long long)(i * kBlock) + threadIdx.x;
+            P[i] = 0ull;
+            F[i] = 0ull;
+            C[i] = 0;
+            if (j < cap) {
+                const slot_t sv = sl[j];
+                if (!LY::empty(sv)) {
+                    P[i] = LY::pay(sv);
+                    unsigned long long f = j;
+                    if (!unique) {   // the first copy of the key: the walk from its home slot
+                        const unsigned long long k = LY::key(sv);
+                        f = slot_of(k, t.shift);
+                        while (f != j && LY::key(sl[f]) != k) f = (f + 1) & t.mask;
+                    }
+                    F[i] = f;
+                    C[i] = cnt[f];
+                    if (out.all || C[i] != 0) found |= 1u << i;
+                }
+            }
+        }
+        unsigned lpre[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const unsigned long long bal = __ballot((found >> i) & 1u);
+            lpre[i] = (unsigned)__popcll(bal & lt);
+            if (lane == 0) s_cw[i * NW + wv] = (unsigned)__popcll(bal);
+        }
+        __syncthreads();
+        if (wv == 0) {   // exclusive scan of the kProbeItems * NW runs (<= 64)
+            static_assert(kProbeItems * NW <= 64, "one lane per run");
+            const unsigned v = lane < kProbeItems * NW ? s_cw[lane] : 0u;
+            const unsigned x = wave_incl_add(v);
+            if (lane < kProbeItems * NW) s_cw[lane] = x - v;
+            if (lane == 63) st_base = x ? atomicAdd(out.counter, (unsigned long long)x) : 0ull;
+        }
+        __syncthreads();
+        if (out.cap != 0) {   // (uniform)
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i) {
+                if (!((found >> i) & 1u)) continue;
+                const unsigned long long gi = st_base + s_cw[i * NW + wv] + lpre[i];
+                if (gi < (unsigned long long)out.cap) {
+                    const bool some = C[i] != 0;
+                    if (orr) orr[gi] = (out_t)P[i];
+                    if (ocnt) ocnt[gi] = (out_t)C[i];
+                    if (osum) osum[gi] = (long long)acc.sum[F[i]];
+                    if (omin) omin[gi] = some ? (out_t)mn[F[i]] : (out_t)out.null_val;
+                    if (omax) omax[gi] = some ? (out_t)mx[F[i]] : (out_t)out.null_val;
+                }
+            }
+        }
+        __syncthreads();   // s_cw / st_base reused by the next tile
+    }
+    if constexpr (L == kWide) {
+        if (blockIdx.x != 0) return;
+        const unsigned long long ns = t.meta[0];
+        if (ns == 0ull) return;   // (uniform)
+        const typename GT::cnt_t c = cnt[cap];
+        if (!out.all && c == 0) return;
+        if (threadIdx.x == 0) st_base = atomicAdd(out.counter, ns);
+        __syncthreads();
+        if (out.cap == 0) return;
+        for (unsigned long long j = threadIdx.x; j < ns; j += kBlock) {
+            const unsigned long long gi = st_base + j;
+            if (gi < (unsigned long long)out.cap) {
+                if (orr) orr[gi] = (out_t)t.side[j];
+                if (ocnt) ocnt[gi] = (out_t)c;
+                if (osum) osum[gi] = (long long)acc.sum[cap];
+                if (omin) omin[gi] = c ? (out_t)mn[cap] : (out_t)out.null_val;
+                if (omax) omax[gi] = c ? (out_t)mx[cap] : (out_t)out.null_val;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ partition
 // Radix partition by a hash independent of the slot hash (fmix64 top word,
 // multiply-shift onto [0, P)), so a partition's keys still spread over its
@@ -1745,6 +1954,30 @@ hipError_t launch_unmatched_build(const TableDev &t, int layout, const SrcDev &s
         hipLaunchKernelGGL(k_emit_unmatched<kNarrow>, dim3(g), dim3(kBlock), 0, st, t, out, (const unsigned *)marks,
                            words, null_s);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_group(const TableDev &t, int layout, const SrcDev &src, const GroupAcc &acc, const GroupOut &out,
+                        hipStream_t st) {
+    if (layout != kWide && layout != kNarrow) return hipErrorInvalidValue;
+    const unsigned long long cap = t.mask + 1ull, entries = cap + 1ull;
+    // the fill's and the scan's persistent workgroups: eight per CU at most
+    const unsigned most = (unsigned)(cu_count() * 8);
+    const unsigned fl = grid_for((long long)entries, kBlock), gi = fl < most ? fl : most;
+    if (layout == kWide) hipLaunchKernelGGL(k_group_init<kWide>, dim3(gi), dim3(kBlock), 0, st, acc, entries);
+    else hipLaunchKernelGGL(k_group_init<kNarrow>, dim3(gi), dim3(kBlock), 0, st, acc, entries);
+    if (src.n > 0) {
+        const unsigned tiles = grid_for(src.n, kProbeTile);
+        const hipError_t e = with_layout_form(layout, src.form, [&](auto l, auto f) {
+            hipLaunchKernelGGL((k_probe_group<decltype(l)::value, decltype(f)::value>), dim3(tiles), dim3(kBlock), 0, st,
+                               t, src, acc);
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return e;
+    }
+    const unsigned tl = grid_for((long long)cap, kProbeTile), g = tl < most ? tl : most;
+    if (layout == kWide) hipLaunchKernelGGL(k_emit_groups<kWide>, dim3(g), dim3(kBlock), 0, st, t, acc, out);
+    else hipLaunchKernelGGL(k_emit_groups<kNarrow>, dim3(g), dim3(kBlock), 0, st, t, acc, out);
     return hipGetLastError();
 }
 

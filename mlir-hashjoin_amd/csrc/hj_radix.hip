@@ -3434,6 +3434,256 @@ __global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cn
     if (off == 63 && x) atomicAdd(a.counter, (u64)x);
 }
 
+// --------------------------------------------------------------- group join
+// Join, then aggregate per build row (radix_group): for each R row the count,
+// the wrapping sum and the signed extremes of the payloads of the S rows with
+// its key.  k_join_lookup's structure with the two bucket sets exchanged, the
+// way radix_unmatched_build exchanges them for k_join_exists: the kernel's "r"
+// side -- the rows whose keys go into the LDS table -- is S's partition, its
+// "s" side -- the rows kept in registers and emitted -- is R's.  An insert ends
+// at EMPTY or at its own key (each S key takes one slot per round), then adds 1
+// to the slot's 16-bit round count (two slots to a word: a round holds at most
+// 2560 rows, no carry reaches the neighbour), adds the payload to the slot's
+// sum and applies atomicMin / atomicMax to its extremes (64-bit signed for
+// int64 rows; 32-bit for i32 rows, whose payloads are row ids below 2^31).
+// Wide INT64_MIN S keys are aggregated in LDS words of their own beside the
+// table.  2^12 slots: 32 (keys) + 32 + 32 + 32 + 8 (counts) = 136 KiB for
+// int64 rows, 32 + 32 + 16 + 16 + 8 = 104 KiB for i32 rows: one 1024-thread
+// workgroup per CU, rounds of RCAP = 2560 rows (40 runs; load <= 0.625).
+// An R lane adds the round's count, sum and extremes of its key to the running
+// ones in its registers (the count 64-bit for int64 rows); after the last
+// round the sub-chunk is compacted as k_join_exists compacts (ballots, one scan,
+// ONE add on the output cursor per sub-chunk): kind MATCHED drops the rows
+// whose count is 0, ALL keeps every row (an item without S rows builds nothing
+// and emits empty groups: its map keeps such partitions).  Every column passed
+// is stored under cap per element; a column not passed is not aggregated
+// either.  Kind, cap and the columns are wave-uniform runtime branches.
+// S's partition is read once per R sub-chunk when it is more than one round.
+constexpr int kGroupTableLog = 12;
+constexpr int kGroupNT = 1024, kGroupSI = 3, kGroupWPS = 4;
+struct GroupCols {
+    void *cnt, *sum, *mn, *mx;   // out_r is JoinArgs' out_r
+    u64 null_val;
+    unsigned all;
+};
+template <bool WIDE, int NT, int SI, int WPS>
+__global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g) {
+    typedef Row<WIDE> R;
+    typedef typename R::T T;
+    typedef typename std::conditional<WIDE, u64, unsigned>::type PT;          // output element (r, cnt, min, max)
+    typedef typename std::conditional<WIDE, long long, unsigned>::type MT;    // the extremes' order
+    typedef typename std::conditional<WIDE, u64, unsigned>::type CT;          // running count
+    constexpr int TS = 1 << kGroupTableLog;
+    constexpr unsigned kMask = TS - 1;
+    constexpr int RCAP = TS * 5 / 8;          // table rows per round
+    constexpr int NW = NT / 64;
+    constexpr unsigned rb = (unsigned)RCAP >> kRunLog;         // runs per round
+    constexpr int RI = (int)((rb + NW - 1) / NW);              // row slots per thread per round (the last partly used)
+    constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;  // runs per sub-chunk
+    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
+    static_assert(RCAP < 65536, "a round's count of one key must fit 16 bits");
+    static_assert(SI * NW <= 64, "one lane per (row slot, wave) run");
+    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    constexpr MT kMinInit = WIDE ? (MT)0x7fffffffffffffffll : (MT)0xffffffffu;
+    constexpr MT kMaxInit = WIDE ? (MT)0x8000000000000000ull : (MT)0u;
+    __shared__ u64 tkey[TS];
+    __shared__ u64 tsum[TS];
+    __shared__ MT tmin[TS];
+    __shared__ MT tmax[TS];
+    __shared__ unsigned tcnt[TS / 2];
+    __shared__ unsigned s_cw[SI * NW];
+    __shared__ u64 s_base;
+    __shared__ unsigned s_nullc;
+    __shared__ u64 s_nullsum;
+    __shared__ MT s_nullmin, s_nullmax;
+
+    const unsigned total = a.work_start[a.P];
+    if (blockIdx.x >= total) return;
+    const T *trows = (const T *)a.r;   // S's partition: aggregated in the table
+    const T *erows = (const T *)a.s;   // R's partition: looked up and emitted
+    PT *orr = (PT *)a.out_r;
+    PT *ocnt = (PT *)g.cnt;
+    u64 *osum = (u64 *)g.sum;
+    PT *omin = (PT *)g.mn;
+    PT *omax = (PT *)g.mx;
+    const bool w_sum = osum != nullptr, w_min = omin != nullptr, w_max = omax != nullptr;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
+    const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
+    const u64 lt = off ? (~0ull >> (64 - off)) : 0ull;
+
+    for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
+        const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
+        const bool rounds = it.r_hi - it.r_lo > (u64)rb;   // more than one round of S rows
+        bool built = false;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += subb) {
+            const u64 shi = sb + subb < it.s_hi ? sb + subb : it.s_hi;
+            T sv[SI];
+            unsigned sok = 0;
+            CT cnt[SI];
+            u64 sum[SI];
+            MT lo[SI], hi[SI];
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                const u64 li = sb + (u64)i * NW + wave;
+                const u64 e = li < shi ? sload(a.s_runs + li) : 0ull;
+                cnt[i] = 0;
+                sum[i] = 0ull;
+                lo[i] = kMinInit;
+                hi[i] = kMaxInit;
+                if (off < (unsigned)(e & 127u)) {
+                    sv[i] = ld_s<kNtJoinLd>(erows + (e >> 7) + off);
+                    sok |= 1u << i;
+                } else {
+                    sv[i] = R::zero();
+                }
+            }
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += rb) {
+                if (rounds || !built) {
+                    // ---- aggregate S's rows of runs [r0, rhi): each key once
+                    const u64 rhi = r0 + rb < it.r_hi ? r0 + rb : it.r_hi;
+                    T br[RI];
+                    unsigned rok = 0;
+#pragma unroll
+                    for (int i = 0; i < RI; ++i) {
+                        const u64 li = r0 + (u64)i * NW + wave;
+                        const u64 e = li < rhi ? sload(a.r_runs + li) : 0ull;
+                        br[i] = R::zero();
+                        if (off < (unsigned)(e & 127u)) {
+                            br[i] = trows[(e >> 7) + off];
+                            rok |= 1u << i;
+                        }
+                    }
+                    __syncthreads();   // the previous table's lookups are done
+                    for (int j = threadIdx.x; j < TS / 2; j += NT)
+                        ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+                    for (int j = threadIdx.x; j < TS / 2; j += NT) tcnt[j] = 0u;
+                    if (w_sum)
+                        for (int j = threadIdx.x; j < TS; j += NT) tsum[j] = 0ull;
+                    if (w_min)
+                        for (int j = threadIdx.x; j < TS; j += NT) tmin[j] = kMinInit;
+                    if (w_max)
+                        for (int j = threadIdx.x; j < TS; j += NT) tmax[j] = kMaxInit;
+                    if (threadIdx.x == 0) {
+                        s_nullc = 0u;
+                        s_nullsum = 0ull;
+                        s_nullmin = kMinInit;
+                        s_nullmax = kMaxInit;
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int i = 0; i < RI; ++i) {
+                        if (!((rok >> i) & 1u)) continue;
+                        const u64 key = R::key(br[i]);
+                        const u64 val = R::pay(br[i]);
+                        if (WIDE && key == kEmptyKey64) {
+                            atomicAdd(&s_nullc, 1u);
+                            if (w_sum) atomicAdd(&s_nullsum, val);
+                            if (w_min) atomicMin(&s_nullmin, (MT)val);
+                            if (w_max) atomicMax(&s_nullmax, (MT)val);
+                            continue;
+                        }
+                        unsigned h = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                        while (true) {   // ends at EMPTY (claimed) or at the key itself
+                            const u64 old = atomicCAS(&tkey[h], kEmpty, key);
+                            if (old == kEmpty || old == key) break;
+                            h = (h + 1) & kMask;
+                        }
+                        atomicAdd(&tcnt[h >> 1], 1u << ((h & 1u) * 16u));
+                        if (w_sum) atomicAdd(&tsum[h], val);
+                        if (w_min) atomicMin(&tmin[h], (MT)val);
+                        if (w_max) atomicMax(&tmax[h], (MT)val);
+                    }
+                    __syncthreads();
+                    built = true;
+                }
+                // ---- every row of the sub-chunk looks its key up: first slots read before any is resolved
+                unsigned hp[SI];
+                u64 e0[SI];
+                unsigned open = sok;
+                const unsigned nullc = s_nullc;
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    const u64 key = R::key(sv[i]);
+                    if (WIDE && key == kEmptyKey64) {
+                        if (((open >> i) & 1u) && nullc) {
+                            cnt[i] += nullc;
+                            if (w_sum) sum[i] += s_nullsum;
+                            if (w_min) {
+                                const MT m = s_nullmin;
+                                lo[i] = m < lo[i] ? m : lo[i];
+                            }
+                            if (w_max) {
+                                const MT m = s_nullmax;
+                                hi[i] = m > hi[i] ? m : hi[i];
+                            }
+                        }
+                        open &= ~(1u << i);
+                    }
+                    hp[i] = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                    e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
+                }
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    if (!((open >> i) & 1u)) continue;
+                    const u64 key = R::key(sv[i]);
+                    unsigned h = hp[i];
+                    u64 e = e0[i];
+                    while (e != kEmpty && e != key) {
+                        h = (h + 1) & kMask;
+                        e = tkey[h];
+                    }
+                    if (e == key) {
+                        cnt[i] += (tcnt[h >> 1] >> ((h & 1u) * 16u)) & 0xffffu;
+                        if (w_sum) sum[i] += tsum[h];
+                        if (w_min) {
+                            const MT m = tmin[h];
+                            lo[i] = m < lo[i] ? m : lo[i];
+                        }
+                        if (w_max) {
+                            const MT m = tmax[h];
+                            hi[i] = m > hi[i] ? m : hi[i];
+                        }
+                    }
+                }
+            }
+            // ---- emit this sub-chunk's rows
+            unsigned keep = 0;
+#pragma unroll
+            for (int i = 0; i < SI; ++i)
+                if (((sok >> i) & 1u) && (g.all || cnt[i] != 0)) keep |= 1u << i;
+            unsigned lpre[SI];
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                const u64 bal = __ballot((keep >> i) & 1u);
+                lpre[i] = (unsigned)__popcll(bal & lt);
+                if (off == 0) s_cw[i * NW + wave] = (unsigned)__popcll(bal);
+            }
+            __syncthreads();
+            if (wave == 0) {   // exclusive scan of the SI * NW runs
+                const unsigned v = off < (unsigned)(SI * NW) ? s_cw[off] : 0u;
+                const unsigned x = wave_incl_add(v);
+                if (off < (unsigned)(SI * NW)) s_cw[off] = x - v;
+                if (off == 63) s_base = x ? atomicAdd(a.counter, (u64)x) : 0ull;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                if (!((keep >> i) & 1u)) continue;
+                const u64 gi = s_base + s_cw[i * NW + wave] + lpre[i];
+                if (gi < (u64)a.cap) {
+                    const bool some = cnt[i] != 0;
+                    if (orr) st_s<kNtJoinSt>(orr + gi, (PT)R::pay(sv[i]));
+                    if (ocnt) st_s<kNtJoinSt>(ocnt + gi, (PT)cnt[i]);
+                    if (w_sum) st_s<kNtJoinSt>(osum + gi, sum[i]);
+                    if (w_min) st_s<kNtJoinSt>(omin + gi, some ? (PT)lo[i] : (PT)g.null_val);
+                    if (w_max) st_s<kNtJoinSt>(omax + gi, some ? (PT)hi[i] : (PT)g.null_val);
+                }
+            }
+            __syncthreads();   // s_cw / s_base reused by the next sub-chunk
+        }
+    }
+}
+
 // --------------------------------------------------------------- join shapes
 // One product kernel per (row width, shape), chosen from facts known when
 // the join is launched -- never from an earlier join's statistics:
@@ -3652,7 +3902,8 @@ unsigned long long radix_join_items(const RadixPlan &pl, unsigned long long s_ru
     // the smallest item of any shape (work_map sizes items by its kernel's sub-chunk)
     constexpr u64 sub = (u64)kFastNT * kFastSI;
     static_assert(sub <= (u64)kNarrowNT * kNarrowSI && sub <= (u64)kStreamNT * kStreamSI &&
-                      sub <= (u64)kExistsNT * kExistsSI, "no kernel's sub-chunk is below the one the items are counted with");
+                      sub <= (u64)kExistsNT * kExistsSI && sub <= (u64)kGroupNT * kGroupSI,
+                  "no kernel's sub-chunk is below the one the items are counted with");
     const u64 chr = (u64)kJoinSub * (sub >> kRunLog);
     return s_runs / chr + (1ull << pl.total_bits) + 2;
 }
@@ -4188,6 +4439,34 @@ hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, con
     else
         hipLaunchKernelGGL((k_join_lookup<false, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, a,
                            cnt, (u64)null_pay, rows);
+    return hipGetLastError();
+}
+
+// k_join_group over radix_unmatched_build's work map: the two bucket sets are
+// exchanged, so the map cuts R's runs into items (the work area covers them:
+// every build sizes it for R's run list) and each item names S's partition as
+// its table side.  MATCHED gates on S: an R partition without S rows has
+// nothing to emit; ALL keeps it -- its rows are the empty groups.  One
+// workgroup per CU (its table).
+hipError_t radix_group(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
+                       const GroupOut &out, hipStream_t st) {
+    const int P = 1 << pl.total_bits;
+    const unsigned pg = (unsigned)cu_count();
+    WorkMapSpec m;
+    m.subb = (unsigned)((kGroupNT * kGroupSI) >> kRunLog);
+    m.grid = pg;
+    m.r_gates = !out.all;
+    m.counter = out.counter;
+    const WorkMap w = work_map(pl, P, ws, s, &r, m, st);
+    if (!w.items) return hipErrorInvalidValue;
+    JoinArgs a = join_args(wide, pl, s, r, P, ws, OutDev{out.r, nullptr, out.cap, out.counter}, nullptr, nullptr);
+    a.tshift = 64 - pl.skip - pl.total_bits - kGroupTableLog;
+    const GroupCols g{out.cnt, out.sum, out.mn, out.mx, (u64)out.null_val, out.all ? 1u : 0u};
+    const unsigned grid = w.items < pg ? w.items : pg;
+    if (wide)
+        hipLaunchKernelGGL((k_join_group<true, kGroupNT, kGroupSI, kGroupWPS>), dim3(grid), dim3(kGroupNT), 0, st, a, g);
+    else
+        hipLaunchKernelGGL((k_join_group<false, kGroupNT, kGroupSI, kGroupWPS>), dim3(grid), dim3(kGroupNT), 0, st, a, g);
     return hipGetLastError();
 }
 

@@ -21,12 +21,14 @@ import os
 
 import torch
 
-from ._lib import (HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
+from ._lib import (HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
                    HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, check, lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
 EXISTS_KINDS = {"semi": HJ_EXISTS_SEMI, "anti": HJ_EXISTS_ANTI}
 FULL_KINDS = {"build": HJ_OUTER_BUILD, "full": HJ_OUTER_FULL}
+GROUP_KINDS = {"matched": HJ_GROUP_MATCHED, "all": HJ_GROUP_ALL}
+GROUP_AGGS = ("count", "sum", "min", "max")
 
 
 def _ptr(t):
@@ -78,6 +80,11 @@ class HashJoin:
     def reserve_probe(self, num_tuples, key_bits=64):
         check(lib.hj_ctx_reserve_probe(self._ctx, int(num_tuples), int(key_bits)), "hj_ctx_reserve_probe")
 
+    def reserve_group(self, num_tuples, key_bits=64):
+        """Size the global-table group probe's accumulators for builds of up to
+        num_tuples rows (hj_ctx_reserve_group), so probe_group allocates nothing."""
+        check(lib.hj_ctx_reserve_group(self._ctx, int(num_tuples), int(key_bits)), "hj_ctx_reserve_group")
+
     def probe_hint(self, num_tuples):
         """The probe side's expected rows, given before the build (None or < 0:
         unknown).  AUTO spares a mid-size build the radix partition it keeps
@@ -118,14 +125,14 @@ class HashJoin:
         return bool(r)
 
     JOIN_KERNELS = {1: "k_join_b", 2: "k_join_u", 3: "k_join_u_stream", 4: "k_join_grp", 5: "k_join",
-                    6: "k_join_exists", 7: "k_join_lookup"}
+                    6: "k_join_exists", 7: "k_join_lookup", 8: "k_join_group"}
 
     @property
     def join_kernel(self):
         """Kernel of the last radix join (hj_ctx_join_kernel): 'k_join_b',
         'k_join_u_stream', 'k_join_grp', 'k_join', 'k_join_exists' (a radix
-        semi- / anti-join), 'k_join_lookup' (a radix lookup), or None (no radix
-        join)."""
+        semi- / anti-join), 'k_join_lookup' (a radix lookup), 'k_join_group' (a
+        radix group probe), or None (no radix join)."""
         r = lib.hj_ctx_join_kernel(self._ctx)
         if r < 0:
             check(r, "hj_ctx_join_kernel")
@@ -348,6 +355,99 @@ class HashJoin:
         if m < 0:   # bit 63 (hj.h)
             raise RuntimeError("hash join: internal work list overflow (count flagged)")
         return (out_r, out_cnt) if with_counts else out_r
+
+    # ---- group probe (hj.h "Group probe"): join, then aggregate per build row
+    def _group_outputs(self, dt, out_r, out_cnt, out_sum, out_min, out_max):
+        cols = (out_r, out_cnt, out_sum, out_min, out_max)
+        passed = [o for o in cols if o is not None]
+        cap = passed[0].numel() if passed else 0
+        if any(o.numel() != cap for o in passed):
+            raise ValueError("output columns differ in length")
+        for o in (out_r, out_cnt, out_min, out_max):
+            if o is not None and o.dtype != dt:
+                raise ValueError("out_r, out_cnt, out_min and out_max carry the probe key's dtype")
+        if out_sum is not None and out_sum.dtype != torch.int64:
+            raise ValueError("out_sum is an int64 column")
+        return cap
+
+    def probe_group(self, skey, sval=None, how="matched", out_r=None, out_cnt=None, out_sum=None, out_min=None,
+                    out_max=None, null=0, count=None, row_base=0, stream=None):
+        """Group probe of the built table: one row per R row (how="all") or per
+        R row with a partner (how="matched"), holding the R payload, and the
+        count, wrapping int64 sum, signed min and max of sval over the S rows
+        with its key, aligned at the same index of each column passed.  Any
+        column may be None (not computed); all None counts only.  An empty
+        group has count 0, sum 0 and min = max = `null` written verbatim.
+        int32 keys: sval is the S row id row_base + row, out_sum stays int64.
+        `count` (int64 device tensor) receives M.  Returns count."""
+        _need_cuda(skey, sval, out_r, out_cnt, out_sum, out_min, out_max)
+        st = _stream(self.device, stream)
+        k = GROUP_KINDS[how]
+        count = self._count if count is None else count
+        if skey.dtype not in (torch.int64, torch.int32):
+            raise TypeError("keys must be int32 or int64")
+        cap = self._group_outputs(skey.dtype, out_r, out_cnt, out_sum, out_min, out_max)
+        outs = (_ptr(out_r), _ptr(out_cnt), _ptr(out_sum), _ptr(out_min), _ptr(out_max))
+        if skey.dtype == torch.int64:
+            if sval is None and any(o is not None for o in (out_sum, out_min, out_max)):
+                raise ValueError("sum / min / max need an int64 value column")
+            if sval is not None and (sval.dtype != torch.int64 or sval.numel() != skey.numel()):
+                raise ValueError("int64 probe needs an int64 value column of the same length")
+            check(lib.hj_dev_group_i64(self._ctx, k, _ptr(skey), _ptr(sval), skey.numel(), int(null), *outs, cap,
+                                       _ptr(count), st), "hj_dev_group_i64")
+        else:
+            if sval is not None:
+                raise ValueError("i32 joins carry row ids, not values (reference types)")
+            check(lib.hj_dev_group_i32(self._ctx, k, _ptr(skey), skey.numel(), int(row_base), int(null), *outs, cap,
+                                       _ptr(count), st), "hj_dev_group_i32")
+        return count
+
+    def probe_group_tuples(self, tuples, how="matched", out_r=None, out_cnt=None, out_sum=None, out_min=None,
+                           out_max=None, null=0, count=None, stream=None):
+        """probe_group over packed (n, 2) int64 {key, value} rows."""
+        _need_cuda(tuples, out_r, out_cnt, out_sum, out_min, out_max)
+        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
+            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        count = self._count if count is None else count
+        cap = self._group_outputs(torch.int64, out_r, out_cnt, out_sum, out_min, out_max)
+        check(lib.hj_dev_group_tuples_i64(self._ctx, GROUP_KINDS[how], _ptr(tuples), tuples.shape[0], int(null),
+                                          _ptr(out_r), _ptr(out_cnt), _ptr(out_sum), _ptr(out_min), _ptr(out_max),
+                                          cap, _ptr(count), _stream(self.device, stream)), "hj_dev_group_tuples_i64")
+        return count
+
+    def count_group(self, skey, how="matched", stream=None, sync=True):
+        """M of the group probe: the R rows with a partner ("matched") or all of them."""
+        cnt = self.probe_group(skey, how=how, stream=stream)
+        return int(cnt.item()) if sync else cnt
+
+    def group_join(self, rkey, rpay, skey, sval, how="matched", aggs=("count", "sum"), null=0, capacity=None,
+                   stream=None):
+        """Build R, then probe_group into outputs of |R| rows (the most the
+        result can hold) or `capacity`: returns (rpay, {agg: tensor}) trimmed
+        to M, for aggs among "count", "sum", "min", "max".  int32 keys: rpay
+        and sval are None (row ids)."""
+        if how not in GROUP_KINDS:
+            raise ValueError("how must be 'matched' or 'all'")
+        if any(a not in GROUP_AGGS for a in aggs):
+            raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
+        self.probe_hint(skey.numel())
+        try:
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+        dt = torch.int64 if rkey.dtype == torch.int64 else torch.int32
+        cap = max(1, rkey.numel() if capacity is None else int(capacity))
+        for _ in range(2):
+            out_r = torch.empty(cap, dtype=dt, device=self.device)
+            cols = {a: torch.empty(cap, dtype=torch.int64 if a == "sum" else dt, device=self.device) for a in aggs}
+            m = int(self.probe_group(skey, sval, how, out_r, cols.get("count"), cols.get("sum"), cols.get("min"),
+                                     cols.get("max"), null=null, stream=stream).item())
+            if m < 0:   # bit 63 (hj.h)
+                raise RuntimeError("hash join: internal work list overflow (count flagged)")
+            if m <= cap:
+                return out_r[:m], {a: c[:m] for a, c in cols.items()}
+            cap = m
+        raise RuntimeError("group join output did not fit after resizing")
 
     # ---- probe-side outer join (hj.h "Probe-side outer join")
     def probe_outer(self, skey, spay=None, out_r=None, out_s=None, null=-1, count=None, row_base=0, stream=None):
