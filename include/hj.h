@@ -153,6 +153,8 @@ int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 #define HJ_JOIN_KERNEL_LOOKUP 7
 /* k_join_group: the last probe was a radix group probe (hj_dev_group_*) */
 #define HJ_JOIN_KERNEL_GROUP 8
+/* k_join_aggregate: the last call was a radix hash aggregate (hj_dev_aggregate_*) */
+#define HJ_JOIN_KERNEL_AGGREGATE 9
 int hj_ctx_join_kernel(hj_ctx *ctx);
 
 /* ------------------------------------------------------------ device phases
@@ -334,6 +336,80 @@ int hj_dev_group_i32(hj_ctx *ctx, int kind, const int32_t *skey, int64_t n, int6
  * max_build_rows rows of key_bits (32 / 64) keys, so that hj_dev_group_*
  * allocates nothing (a no-op where such a build would take the radix join). */
 int hj_ctx_reserve_group(hj_ctx *ctx, int64_t max_build_rows, int key_bits);
+
+/* Hash aggregate (GROUP BY key over ONE relation, and DISTINCT):
+ *   SELECT key, count(*), sum(v), min(v), max(v) FROM S GROUP BY key
+ * For the relation S with a value column, let G(k) = {j : S.key[j] == k}; the
+ * result holds one row (key, cnt, sum, min, max) per DISTINCT key k of S, every
+ * column aligned at the same index:
+ *   cnt = |G(k)|,
+ *   sum = the sum of S.val[j] over G(k) in two's-complement int64 (it wraps),
+ *   min / max = the signed extremes of S.val over G(k).
+ * M is the number of distinct keys.  Row order is unspecified; the result is
+ * otherwise a function of the data alone -- integer add, min and max commute --
+ * and bit-equal across strategies, kernels and runs.  INT64_MIN is a key like
+ * any other (the wide table's empty word, and whatever word a layout uses as
+ * "empty", never shows), INT64_MIN and INT64_MAX are values like any other;
+ * i32 keys -1, INT32_MIN and 0 are ordinary keys.
+ * i32: the value is the row id row_base + row, as in every i32 entry point, so
+ * out_min / out_max are the key's first and last row, out_cnt its multiplicity
+ * and out_sum an int64 sum of row ids; n > INT32_MAX (or row ids past it) is
+ * HJ_ERR_ARG.
+ * Any output column may be NULL and is then neither computed nor stored; val
+ * may be NULL when none of sum / min / max is asked for (only the key column
+ * is read then), and val == NULL with one of them passed is HJ_ERR_ARG (n == 0
+ * reads nothing and takes a null column).  With
+ * only out_key passed the call is DISTINCT.  out_cap == 0 with all five outputs
+ * NULL is the count-only form (d_count = the number of distinct keys); out_cap
+ * > 0 with all five NULL is HJ_ERR_ARG, and so is out_cap == 0 with any of them
+ * non-NULL.  d_count = M exactly, even when M > out_cap: rows past out_cap are
+ * dropped (which ones is unspecified) and nothing is written at or past index
+ * out_cap in any column; bit 63 as above (no aggregate path sets it).  n == 0:
+ * M = 0 and nothing is written.
+ * Errors, in this order: a null context (HJ_ERR_ARG); a null count pointer, a
+ * bad relation, bad outputs (HJ_ERR_ARG); HJ_ERR_NOMEM when the workspace does
+ * not fit.
+ * The call needs NO prior build.  It takes the context's workspace the way a
+ * build does -- a new timing step, the host memo dropped -- and leaves NO build
+ * behind: every hj_dev_probe_* / _count_* / _exists_* / _lookup_* / _group_*
+ * after it returns HJ_ERR_STATE until the next hj_dev_build_*, and so does
+ * hj_ctx_build_has_duplicates; a build and its probes after an aggregate work
+ * exactly as on a fresh context.  Until that build hj_ctx_strategy_used,
+ * hj_ctx_radix_plan and hj_ctx_table_capacity describe the aggregate, and
+ * hj_ctx_join_kernel returns HJ_JOIN_KERNEL_AGGREGATE after a radix one, 0
+ * after a global one.  Timing follows the probes: the whole call is the probe
+ * phase ([2]); RADIX: [4] the input's partition, [5] the rest.
+ * Strategy: hj_ctx_set_strategy and hj_ctx_set_radix_bits are honoured; AUTO
+ * goes by n alone -- RADIX from 2^21 rows on, else GLOBAL (it does not know
+ * the number of distinct keys).  GLOBAL: a table of >= 2n slots with per-slot
+ * accumulators; each 2048-row tile is collapsed in LDS before it touches the
+ * table, so a hot key costs one global atomic per tile.  RADIX: the input is
+ * partitioned once (i32 rows one bit finer than a join's plan) and each
+ * partition aggregated in one LDS table that persists over the partition's
+ * rows; a partition with more distinct keys than the table admits is re-run
+ * in sub-splits and is exact all the same.
+ * Asynchronous on the stream: kernels only (the counter is zeroed by one of
+ * them, not by a memset) -- no allocation, no synchronisation -- once
+ * hj_ctx_reserve_aggregate sized the workspace (graph-capturable as a linear
+ * graph). */
+int hj_dev_aggregate_i64(hj_ctx *ctx, const int64_t *key, const int64_t *val, int64_t n,
+                         int64_t *out_key, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                         int64_t out_cap, uint64_t *d_count, void *stream);
+/* rows as packed 16-B {key, value} tuples */
+int hj_dev_aggregate_tuples_i64(hj_ctx *ctx, const int64_t *tuples, int64_t n,
+                                int64_t *out_key, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                                int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_aggregate_i32(hj_ctx *ctx, const int32_t *key, int64_t n, int64_t row_base,
+                         int32_t *out_key, int32_t *out_cnt, int64_t *out_sum, int32_t *out_min, int32_t *out_max,
+                         int64_t out_cap, uint64_t *d_count, void *stream);
+/* Sizes the workspace for hj_dev_aggregate_* calls of up to max_rows rows of
+ * key_bits (32 / 64) keys under the context's strategy and radix bits, every
+ * column asked for, so that those calls allocate nothing.  AUTO: both the
+ * radix workspace for max_rows and the global table for the inputs below 2^21
+ * rows.  Where it has to replace the global table, a current build in that
+ * table is dropped (probes answer HJ_ERR_STATE until the next build): reserve
+ * before building, as with hj_ctx_reserve. */
+int hj_ctx_reserve_aggregate(hj_ctx *ctx, int64_t max_rows, int key_bits);
 
 /* Probe-side outer join (LEFT OUTER with the probe relation on the left) over
  * the table an ordinary hj_dev_build_* left: one build serves inner, semi,

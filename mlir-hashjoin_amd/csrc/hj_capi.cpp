@@ -221,6 +221,8 @@ struct hj_ctx {
     bool exists_ran = false;   // the last probe was a radix semi- / anti-join (HJ_JOIN_KERNEL_EXISTS)
     bool lookup_ran = false;   // the last probe was a radix lookup (HJ_JOIN_KERNEL_LOOKUP)
     bool group_ran = false;    // the last probe was a radix group probe (HJ_JOIN_KERNEL_GROUP)
+    bool agg_ran = false;      // an aggregate (hj_dev_aggregate_*) ran since the last build: layout < 0, and used,
+                               // plan, bits and n_build describe it
     bool routed = false;   // the current build came from hj_dev_build_routed_i64 (plan.skip owner bits)
     bool dup_checked = false;   // hj_ctx_build_has_duplicates ran its DETECT build for this build
     bool host_building = false;  // host_join's build is running (do_build keeps the memo's input copies)
@@ -244,7 +246,8 @@ int ensure_meta(hj_ctx *c, size_t words) {
     return HJ_OK;
 }
 
-int ensure_table(hj_ctx *c, int64_t n, int layout) {
+// with_build = false: the slots alone (an aggregate reads neither the side list nor the mark bitmap)
+int ensure_table(hj_ctx *c, int64_t n, int layout, bool with_build = true) {
     const int bits = table_bits(n);
     const size_t need = (size_t(1) << bits) * (layout == kWide ? 16 : 8);
     if (c->table_bytes < need) {
@@ -254,6 +257,7 @@ int ensure_table(hj_ctx *c, int64_t n, int layout) {
         if (hipMalloc(&c->table, need) != hipSuccess) HJ_FAIL(HJ_ERR_NOMEM, "hipMalloc table " + std::to_string(need));
         c->table_bytes = need;
     }
+    if (!with_build) return ensure_meta(c, 64);
     if (layout == kWide && c->side_rows < (size_t)(n > 0 ? n : 1)) {
         if (c->side) HJ_HIP(hipFree(c->side));
         c->side = nullptr;
@@ -584,7 +588,7 @@ int begin_build(hj_ctx *c, int layout, int64_t n, int used, bool dual, bool rout
     c->routed = routed;
     c->plan = plan;
     c->probe_used = -1;
-    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = c->dup_checked = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = c->agg_ran = c->dup_checked = false;
     // (hj_count_*'s kept table is gone; a host join's own build keeps the
     // EXACT copies it has just taken of its inputs)
     if (c->host_building) c->memo.valid = false;
@@ -850,6 +854,75 @@ int do_group(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, const char 
     q.grp = hj::GroupOut{out_r, out_cnt, out_sum, out_min, out_max, cap, (unsigned long long *)d_count, null_val,
                          kind == HJ_GROUP_ALL ? 1 : 0};
     return run_probe(c, q, st);
+}
+
+// Hash aggregate (hj_dev_aggregate_*): GROUP BY key over one relation.  It
+// takes the workspace as a build does (begin_build: a new timing step, the host
+// memo dropped) and leaves no build: layout stays -1, so every probe answers
+// HJ_ERR_STATE until the next build, while used / plan / bits describe the
+// aggregate.  AUTO goes by n alone.  The radix plan is made for n rows; i32
+// rows are planned as if there were twice as many, one bit finer than a join's
+// plan: k_join_aggregate's table admits 2400 keys per partition whatever the
+// row width, the narrow join plan averages 4096 rows.
+int aggregate_strategy(const hj_ctx *c, int64_t n) {
+    if (c->strategy == HJ_STRATEGY_GLOBAL || c->strategy == HJ_STRATEGY_RADIX) return c->strategy;
+    return n >= kRadixMinRows ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
+}
+hj::RadixPlan aggregate_plan(const hj_ctx *c, int64_t n, bool wide) {
+    return hj::radix_plan(wide ? n : 2 * n, c->radix_bits, wide);
+}
+int ensure_aggregate(hj_ctx *c, int64_t n, int layout, int used, bool sum, bool mn, bool mx) {
+    if (used == HJ_STRATEGY_RADIX)
+        return ensure_radix_scratch(c, c->sset, n, layout == kWide, aggregate_plan(c, n, layout == kWide));
+    HJ_TRY(ensure_table(c, n, layout, false));
+    return ensure_group_acc(c, table_bits(n), layout, sum, mn, mx);
+}
+
+int do_aggregate(hj_ctx *c, int layout, const hj::SrcDev &src, const char *rel_err, void *out_key, void *out_cnt,
+                 void *out_sum, void *out_min, void *out_max, int64_t cap, uint64_t *d_count, hipStream_t st) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (rel_err) HJ_FAIL(HJ_ERR_ARG, rel_err);
+    if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad relation");
+    const bool any = out_key || out_cnt || out_sum || out_min || out_max;
+    if (cap < 0 || (cap > 0 && !any) || (cap == 0 && any)) HJ_FAIL(HJ_ERR_ARG, "bad output");
+    HJ_TRY(set_device(c));
+    const bool wide = layout == kWide;
+    const int used = aggregate_strategy(c, src.n);
+    // (the build is dropped before the workspace is touched: sizing it may free
+    // the table a global build lives in, and may then fail)
+    HJ_TRY(begin_build(c, -1, src.n, used, false, false,
+                       used == HJ_STRATEGY_RADIX ? aggregate_plan(c, src.n, wide) : c->plan));
+    c->evs().rec[0] = c->evs().rec[1] = c->evs().rec[3] = false;   // (no init, build or routing phase in this step)
+    c->evs().rec[2] = c->evs().rec_mid = false;
+    HJ_TRY(ensure_aggregate(c, src.n, layout, used, out_sum, out_min, out_max));
+    c->agg_ran = true;
+    const hj::GroupOut grp{out_key, out_cnt, out_sum, out_min, out_max, cap, (unsigned long long *)d_count, 0ull, 0};
+    if (used != HJ_STRATEGY_RADIX) {
+        c->bits = table_bits(src.n);
+        // (the accumulators' fill zeroes the counter: no memset launch)
+        record(c, kEvProbe0, st);
+        const hj::GroupAcc acc{c->acc_cnt.p, out_sum ? (unsigned long long *)c->acc_sum.p : nullptr,
+                               out_min ? c->acc_min.p : nullptr, out_max ? c->acc_max.p : nullptr};
+        HJ_HIP(hj::launch_aggregate(table_dev(c), layout, src, acc, grp, st));
+    } else {
+        // (the work-map kernel zeroes the counter: no memset launch)
+        record(c, kEvProbe0, st);
+        hj::SrcDev in = src;
+        if (wide && !src.pay && src.form == hj::kCols64) {
+            // no aggregate reads the payload: the key column alone is read (the rows carry their index)
+            in.form = hj::kKeyRow64;
+        }
+        HJ_RADIX(c, st, hj::radix_partition(in, wide, c->plan, radix_work(c), bucket_set(c->sset), st));
+        trace("aggregate: partitioned", st, src.n);
+        record(c, kEvProbeMid, st);
+        HJ_RADIX(c, st, hj::radix_aggregate(wide, c->plan, radix_work(c), bucket_set(c->sset), grp, st));
+        trace("aggregate: done", st, cap);
+    }
+    record(c, kEvProbe1, st);
+    c->evs().rec[2] = c->timing;
+    c->evs().rec_mid = used == HJ_STRATEGY_RADIX && c->timing;
+    return HJ_OK;
 }
 
 // Probe-side outer join (hj_dev_probe_outer_*): do_probe's checks; out_cap == 0
@@ -1675,14 +1748,14 @@ int hj_ctx_reserve(hj_ctx *c, int64_t max_build_rows, int key_bits) {
 }
 
 int64_t hj_ctx_table_capacity(const hj_ctx *c) {
-    if (!c || c->layout < 0) return 0;
+    if (!c || (c->layout < 0 && !c->agg_ran)) return 0;
     if (c->used == HJ_STRATEGY_RADIX) return (int64_t)(1ll << c->plan.total_bits);   // partitions
     return (int64_t)(1ll << c->bits);
 }
 
 int hj_ctx_radix_plan(const hj_ctx *c, int *passes, int bits[3]) {
     if (!c || !passes || !bits) HJ_FAIL(HJ_ERR_ARG, "null argument");
-    const bool radix = c->layout >= 0 && (c->used == HJ_STRATEGY_RADIX || c->dual);
+    const bool radix = (c->layout >= 0 || c->agg_ran) && (c->used == HJ_STRATEGY_RADIX || c->dual);
     *passes = radix ? c->plan.passes : 0;
     for (int i = 0; i < 3; ++i) bits[i] = radix ? c->plan.bits[i] : 0;
     return HJ_OK;
@@ -1711,6 +1784,7 @@ int hj_ctx_build_has_duplicates(hj_ctx *c) {
 
 int hj_ctx_join_kernel(hj_ctx *c) {
     if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (c->agg_ran) return c->used == HJ_STRATEGY_RADIX ? HJ_JOIN_KERNEL_AGGREGATE : 0;
     if (c->exists_ran && c->layout >= 0) return HJ_JOIN_KERNEL_EXISTS;
     if (c->lookup_ran && c->layout >= 0) return HJ_JOIN_KERNEL_LOOKUP;
     if (c->group_ran && c->layout >= 0) return HJ_JOIN_KERNEL_GROUP;
@@ -1800,6 +1874,7 @@ int hj_ctx_set_radix_bits(hj_ctx *c, int bits) {
 
 
 int hj_ctx_strategy_used(const hj_ctx *c) {
+    if (c && c->agg_ran) return c->used;
     if (!c || c->layout < 0) return 0;
     return c->probe_used >= 0 ? c->probe_used : c->used;
 }
@@ -1825,6 +1900,24 @@ int hj_ctx_reserve_group(hj_ctx *c, int64_t max_build_rows, int key_bits) {
     if (choose_strategy(c, max_build_rows) != HJ_STRATEGY_GLOBAL) return HJ_OK;
     HJ_TRY(set_device(c));
     return ensure_group_acc(c, table_bits(max_build_rows), key_bits == 64 ? kWide : kNarrow, true, true, true);
+}
+
+int hj_ctx_reserve_aggregate(hj_ctx *c, int64_t max_rows, int key_bits) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (max_rows < 0 || (key_bits != 32 && key_bits != 64)) HJ_FAIL(HJ_ERR_ARG, "bad reserve arguments");
+    if (key_bits == 32 && max_rows > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids: at most 2^31 - 1 rows");
+    HJ_TRY(set_device(c));
+    HJ_TRY(ensure_meta(c, 64));
+    const int layout = key_bits == 64 ? kWide : kNarrow;
+    const int used = aggregate_strategy(c, max_rows);
+    // (a current build that lives in the global table is dropped when the table is replaced or lost)
+    const size_t table_bytes = c->table_bytes;
+    int rc = ensure_aggregate(c, max_rows, layout, used, true, true, true);
+    // AUTO sends the inputs below kRadixMinRows rows to the global table: size that too
+    if (rc == HJ_OK && c->strategy == HJ_STRATEGY_AUTO && used == HJ_STRATEGY_RADIX)
+        rc = ensure_aggregate(c, kRadixMinRows - 1, layout, HJ_STRATEGY_GLOBAL, true, true, true);
+    if (c->table_bytes != table_bytes && (c->used == HJ_STRATEGY_GLOBAL || c->dual)) c->layout = -1;
+    return rc;
 }
 
 // ------------------------------------------------------------ device phases
@@ -1914,6 +2007,30 @@ int hj_dev_group_i32(hj_ctx *c, int kind, const int32_t *skey, int64_t n, int64_
     return do_group(c, kNarrow, kind, src_col32(skey, n, bad_ids ? 0 : row_base),
                     bad_ids ? "i32 row ids out of range" : nullptr, (unsigned long long)(uint32_t)null_row, out_r,
                     out_cnt, out_sum, out_min, out_max, out_cap, d_count, (hipStream_t)stream);
+}
+
+int hj_dev_aggregate_i64(hj_ctx *c, const int64_t *key, const int64_t *val, int64_t n, int64_t *out_key,
+                         int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap,
+                         uint64_t *d_count, void *stream) {
+    // (a null value column is kept null: no kernel reads it when no aggregate of it is asked for)
+    // (n == 0 reads nothing: an empty column may be null)
+    const bool no_val = n > 0 && !val && (out_sum || out_min || out_max);
+    return do_aggregate(c, kWide, src_cols64(key, val, n), no_val ? "null value column" : nullptr, out_key, out_cnt,
+                        out_sum, out_min, out_max, out_cap, d_count, (hipStream_t)stream);
+}
+int hj_dev_aggregate_tuples_i64(hj_ctx *c, const int64_t *tuples, int64_t n, int64_t *out_key, int64_t *out_cnt,
+                                int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap,
+                                uint64_t *d_count, void *stream) {
+    return do_aggregate(c, kWide, src_packed(tuples, n), nullptr, out_key, out_cnt, out_sum, out_min, out_max, out_cap,
+                        d_count, (hipStream_t)stream);
+}
+int hj_dev_aggregate_i32(hj_ctx *c, const int32_t *key, int64_t n, int64_t row_base, int32_t *out_key,
+                         int32_t *out_cnt, int64_t *out_sum, int32_t *out_min, int32_t *out_max, int64_t out_cap,
+                         uint64_t *d_count, void *stream) {
+    const bool bad_ids = n > 0x7fffffffll || row_base < 0 || row_base + n > 0x7fffffffll;
+    return do_aggregate(c, kNarrow, src_col32(key, n, bad_ids ? 0 : row_base),
+                        bad_ids ? "i32 row ids out of range" : nullptr, out_key, out_cnt, out_sum, out_min, out_max,
+                        out_cap, d_count, (hipStream_t)stream);
 }
 
 // (the null context is reported before any other argument, as the header says)

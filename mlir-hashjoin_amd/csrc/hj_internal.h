@@ -157,6 +157,18 @@ struct GroupAcc {                 // slots + 1 entries each (the last: the wide 
 // caller zeroed).  Reads the table, the side list and meta[0..1]; writes none.
 hipError_t launch_group(const TableDev &t, int layout, const SrcDev &src, const GroupAcc &acc, const GroupOut &out,
                         hipStream_t st);
+// Hash aggregate (GROUP BY key) of src over the global table, which the call
+// fills itself: launch_init, k_aggregate_init (the accumulators' fill; it also
+// zeroes out.counter), k_aggregate (each 2048-row tile
+// collapsed in LDS, then one insert-or-find and one atomic per accumulator and
+// distinct key of the tile) and k_emit_aggregate (one row per occupied slot,
+// compacted through out.counter).  t: 2^bits >= 2 *
+// src.n slots; acc as launch_group's (slots + 1 entries; the last is the wide
+// INT64_MIN key's).  out.r receives the KEY; out.all and out.null_val are not
+// read.  src.pay may be null when acc.sum, acc.mn and acc.mx all are.  The
+// table is left holding the keys, not a build: meta[0..1] are zeroed.
+hipError_t launch_aggregate(const TableDev &t, int layout, const SrcDev &src, const GroupAcc &acc, const GroupOut &out,
+                            hipStream_t st);
 // probe-side outer join over the global table: launch_probe's pairs plus
 // (null_pay, S payload) for every S row without a partner; out.cap == 0
 // counts only; slow / slow_cap as launch_probe's
@@ -295,6 +307,14 @@ hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, con
 // R partitions without S rows.  Reads r and s, writes neither nor the repeat flag.
 hipError_t radix_group(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
                        const GroupOut &out, hipStream_t st);
+// Hash aggregate over ONE partitioned relation s (k_join_aggregate): one row
+// (key in out.r, count, wrapping sum, signed extremes of the payloads) per
+// distinct key, compacted through out.counter (zeroed by the work map); one
+// item per non-empty partition, exact whatever a partition holds (an item with
+// more distinct keys than its LDS table admits is re-run in sub-splits).
+// out.all and out.null_val are not read.  Reads s, writes nothing of it.
+hipError_t radix_aggregate(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &s, const GroupOut &out,
+                           hipStream_t st);
 // The outer join's second stage, after radix_join over the same r and s (and
 // out): the S rows without a partner in r are appended behind the pairs as
 // (null_pay, S payload) -- radix_exists' anti probe whose work map leaves

@@ -12,6 +12,7 @@
 // (k_probe_lookup), the outer probe (k_probe_outer),
 // the build-side outer stages (k_probe_mark, k_emit_unmatched),
 // the group probe (k_group_init, k_probe_group, k_emit_groups),
+// the hash aggregate (k_aggregate, k_emit_aggregate),
 // the radix partition used by the
 // multi-GPU exchange, the selection, the counter-based generators of the
 // benchmark inputs and the copy floors.
@@ -1171,7 +1172,7 @@ struct GroupTypes<kNarrow> {
 };
 
 template <int L>
-__global__ __launch_bounds__(kBlock) void k_group_init(GroupAcc acc, unsigned long long n) {
+__device__ __forceinline__ void group_fill(const GroupAcc &acc, unsigned long long n) {
     using GT = GroupTypes<L>;
     typename GT::cnt_t *cnt = (typename GT::cnt_t *)acc.cnt;
     typename GT::ext_t *mn = (typename GT::ext_t *)acc.mn, *mx = (typename GT::ext_t *)acc.mx;
@@ -1182,6 +1183,10 @@ __global__ __launch_bounds__(kBlock) void k_group_init(GroupAcc acc, unsigned lo
         if (mn) mn[j] = GT::kMax;
         if (mx) mx[j] = GT::kMin;
     }
+}
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_group_init(GroupAcc acc, unsigned long long n) {
+    group_fill<L>(acc, n);
 }
 
 template <int L, int FORM>
@@ -1339,6 +1344,254 @@ __global__ __launch_bounds__(kBlock) void k_emit_groups(TableDev t, GroupAcc acc
                 if (omin) omin[gi] = c ? (out_t)mn[cap] : (out_t)out.null_val;
                 if (omax) omax[gi] = c ? (out_t)mx[cap] : (out_t)out.null_val;
             }
+        }
+    }
+}
+
+// ------------------------------------------------------------------ hash aggregate
+// GROUP BY key over one relation (launch_aggregate): the table holds each
+// distinct key once and the group probe's accumulators (GroupAcc) sit beside
+// it.  The table's fill and k_aggregate_init (k_group_init's fill, and the
+// output counter's zero: a captured one-word memset node in front of these
+// launches was replayed with a stale byte pattern at 70 000 rows; the cause is
+// not known; a kernel's arguments travel in its node), then
+//   k_aggregate       persistent workgroups over 2048-row tiles.  A tile is
+//                     first collapsed in a kAggSlots-slot LDS table (key,
+//                     count and the partials asked for: LDS atomics behind a
+//                     CAS that ends at EMPTY or at the key itself, at most
+//                     kAggWalk steps from the key's home slot -- slots are
+//                     never freed inside a tile, so every row of a key takes
+//                     the same way).  A row whose walk ends on neither goes to
+//                     the global table itself.  Every occupied LDS slot is
+//                     then flushed once: insert-or-find in the global table (a
+//                     CAS on the slot's key word; narrow: key << 32, which is
+//                     never the all-ones EMPTY word, so -1 is a key like any
+//                     other) and one non-returning atomic per accumulator that
+//                     carries the tile's partial.  A hot key costs one global
+//                     atomic per tile instead of one per row.  Wide INT64_MIN
+//                     keys (the table's EMPTY word) are collapsed in LDS words
+//                     of their own and flushed into the last entry.
+//   k_emit_aggregate  k_emit_groups' scan over the slots, emitting the slot's
+//                     key and its own accumulators (no first-copy walk: the
+//                     table holds each key once); workgroup 0 appends the
+//                     INT64_MIN entry when its count is non-zero.
+// 18 KiB of LDS (int64 rows) per workgroup: eight workgroups fit a CU.
+constexpr int kAggSlotsLog = 9, kAggSlots = 1 << kAggSlotsLog, kAggWalk = 8;
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_aggregate_init(GroupAcc acc, unsigned long long n,
+                                                           unsigned long long *counter) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *counter = 0ull;
+    group_fill<L>(acc, n);
+}
+
+// the slot of key K in the global table, claimed if the key is new
+template <int L>
+__device__ __forceinline__ unsigned long long agg_slot(typename Lay<L>::slot_t *sl, const TableDev &t,
+                                                       unsigned long long K) {
+    using LY = Lay<L>;
+    const unsigned long long w = L == kWide ? K : K << 32;
+    unsigned long long h = slot_of(K, t.shift);
+    while (true) {
+        // (read first: a repeated key finds itself without an atomic)
+        unsigned long long old = __hip_atomic_load(LY::word(sl, h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == LY::kEmptyWord) old = atomicCAS(LY::word(sl, h), LY::kEmptyWord, w);
+        if (old == LY::kEmptyWord || old == w) return h;
+        h = (h + 1) & t.mask;
+    }
+}
+
+template <int L>
+__device__ __forceinline__ void acc_add(const GroupAcc &acc, unsigned long long h, typename GroupTypes<L>::cnt_t c,
+                                        unsigned long long s, typename GroupTypes<L>::ext_t lo,
+                                        typename GroupTypes<L>::ext_t hi) {
+    using GT = GroupTypes<L>;
+    atomicAdd((typename GT::cnt_t *)acc.cnt + h, c);
+    if (acc.sum) atomicAdd(acc.sum + h, s);
+    if (acc.mn) atomicMin((typename GT::ext_t *)acc.mn + h, lo);
+    if (acc.mx) atomicMax((typename GT::ext_t *)acc.mx + h, hi);
+}
+
+template <int L, int FORM>
+__global__ __launch_bounds__(kBlock) void k_aggregate(TableDev t, SrcDev src, GroupAcc acc) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using GT = GroupTypes<L>;
+    using ext_t = typename GT::ext_t;
+    using cnt_t = typename GT::cnt_t;
+    constexpr unsigned long long kE = L == kWide ? kEmptyKey64 : ~0ull;   // (a zero-extended i32 key is never all ones)
+    __shared__ unsigned long long lkey[kAggSlots];
+    __shared__ unsigned long long lsum[kAggSlots];
+    __shared__ ext_t lmin[kAggSlots], lmax[kAggSlots];
+    __shared__ unsigned lcnt[kAggSlots];
+    __shared__ unsigned long long n_sum;
+    __shared__ ext_t n_min, n_max;
+    __shared__ unsigned n_cnt;
+    slot_t *sl = (slot_t *)t.slots;
+    const bool w_sum = acc.sum != nullptr, w_min = acc.mn != nullptr, w_max = acc.mx != nullptr;
+    const bool vals = w_sum || w_min || w_max;   // (uniform) else only the key is read
+    const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long K[kProbeItems], V[kProbeItems];
+        unsigned ok = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const long long row = (long long)q * kProbeTile + (long long)i * kBlock + threadIdx.x;
+            K[i] = V[i] = 0ull;
+            if (row < src.n) {
+                if (vals) {
+                    const Tuple tp = load_src<FORM>(src, row);
+                    K[i] = tp.k;
+                    V[i] = tp.p;
+                } else {
+                    K[i] = load_key<FORM>(src, row);
+                }
+                ok |= 1u << i;
+            }
+        }
+        for (int j = threadIdx.x; j < kAggSlots; j += kBlock) {
+            lkey[j] = kE;
+            lcnt[j] = 0u;
+            if (w_sum) lsum[j] = 0ull;
+            if (w_min) lmin[j] = GT::kMax;
+            if (w_max) lmax[j] = GT::kMin;
+        }
+        if (threadIdx.x == 0) {
+            n_cnt = 0u;
+            n_sum = 0ull;
+            n_min = GT::kMax;
+            n_max = GT::kMin;
+        }
+        __syncthreads();
+        // ---- the tile's rows into the LDS table
+        unsigned direct = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((ok >> i) & 1u)) continue;
+            if (LY::null_key(K[i])) {
+                atomicAdd(&n_cnt, 1u);
+                if (w_sum) atomicAdd(&n_sum, V[i]);
+                if (w_min) atomicMin(&n_min, (ext_t)V[i]);
+                if (w_max) atomicMax(&n_max, (ext_t)V[i]);
+                continue;
+            }
+            unsigned h = (unsigned)slot_of(K[i], 64 - kAggSlotsLog);
+            bool in = false;
+            for (int step = 0; step < kAggWalk; ++step) {
+                unsigned long long e = __hip_atomic_load(&lkey[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (e == kE) e = atomicCAS(&lkey[h], kE, K[i]);
+                if (e == kE || e == K[i]) {
+                    in = true;
+                    break;
+                }
+                h = (h + 1u) & (unsigned)(kAggSlots - 1);
+            }
+            if (in) {
+                atomicAdd(&lcnt[h], 1u);
+                if (w_sum) atomicAdd(&lsum[h], V[i]);
+                if (w_min) atomicMin(&lmin[h], (ext_t)V[i]);
+                if (w_max) atomicMax(&lmax[h], (ext_t)V[i]);
+            } else {
+                direct |= 1u << i;
+            }
+        }
+        // ---- the rows the LDS table did not admit: the global table, one by one
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((direct >> i) & 1u)) continue;
+            acc_add<L>(acc, agg_slot<L>(sl, t, K[i]), (cnt_t)1, V[i], (ext_t)V[i], (ext_t)V[i]);
+        }
+        __syncthreads();
+        // ---- one flush per occupied LDS slot
+        for (int j = threadIdx.x; j < kAggSlots; j += kBlock) {
+            const unsigned long long k = lkey[j];
+            if (k == kE) continue;
+            acc_add<L>(acc, agg_slot<L>(sl, t, k), (cnt_t)lcnt[j], w_sum ? lsum[j] : 0ull, w_min ? lmin[j] : GT::kMax,
+                       w_max ? lmax[j] : GT::kMin);
+        }
+        if (L == kWide && threadIdx.x == 0 && n_cnt != 0u)
+            acc_add<L>(acc, t.mask + 1ull, (cnt_t)n_cnt, n_sum, n_min, n_max);
+        __syncthreads();   // the LDS table is cleared for the next tile
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_emit_aggregate(TableDev t, GroupAcc acc, GroupOut out) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    using GT = GroupTypes<L>;
+    constexpr int NW = kBlock / 64;
+    __shared__ unsigned long long st_base;
+    __shared__ unsigned s_cw[kProbeItems * NW];
+    const typename GT::cnt_t *cnt = (const typename GT::cnt_t *)acc.cnt;
+    const typename GT::ext_t *mn = (const typename GT::ext_t *)acc.mn, *mx = (const typename GT::ext_t *)acc.mx;
+    const slot_t *sl = (const slot_t *)t.slots;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long cap = t.mask + 1ull;
+    const unsigned long long nt = (cap + kProbeTile - 1) / kProbeTile;
+    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+    out_t *okey = (out_t *)out.r, *ocnt = (out_t *)out.cnt, *omin = (out_t *)out.mn, *omax = (out_t *)out.mx;
+    long long *osum = (long long *)out.sum;
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long KY[kProbeItems];
+        unsigned found = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const unsigned long long j = q * kProbeTile + (unsigned long long)(i * kBlock) + threadIdx.x;
+            KY[i] = 0ull;
+            if (j < cap) {
+                const slot_t sv = sl[j];
+                if (!LY::empty(sv)) {
+                    KY[i] = LY::key(sv);
+                    found |= 1u << i;
+                }
+            }
+        }
+        unsigned lpre[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const unsigned long long bal = __ballot((found >> i) & 1u);
+            lpre[i] = (unsigned)__popcll(bal & lt);
+            if (lane == 0) s_cw[i * NW + wv] = (unsigned)__popcll(bal);
+        }
+        __syncthreads();
+        if (wv == 0) {   // exclusive scan of the kProbeItems * NW runs (<= 64)
+            static_assert(kProbeItems * NW <= 64, "one lane per run");
+            const unsigned v = lane < kProbeItems * NW ? s_cw[lane] : 0u;
+            const unsigned x = wave_incl_add(v);
+            if (lane < kProbeItems * NW) s_cw[lane] = x - v;
+            if (lane == 63) st_base = x ? atomicAdd(out.counter, (unsigned long long)x) : 0ull;
+        }
+        __syncthreads();
+        if (out.cap != 0) {   // (uniform)
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i) {
+                if (!((found >> i) & 1u)) continue;
+                const unsigned long long gi = st_base + s_cw[i * NW + wv] + lpre[i];
+                if (gi < (unsigned long long)out.cap) {
+                    const unsigned long long j = q * kProbeTile + (unsigned long long)(i * kBlock) + threadIdx.x;
+                    if (okey) okey[gi] = (out_t)KY[i];
+                    if (ocnt) ocnt[gi] = (out_t)cnt[j];
+                    if (osum) osum[gi] = (long long)acc.sum[j];
+                    if (omin) omin[gi] = (out_t)mn[j];
+                    if (omax) omax[gi] = (out_t)mx[j];
+                }
+            }
+        }
+        __syncthreads();   // s_cw / st_base reused by the next tile
+    }
+    if constexpr (L == kWide) {
+        if (blockIdx.x != 0 || threadIdx.x != 0) return;
+        const typename GT::cnt_t c = cnt[cap];
+        if (c == 0) return;
+        const unsigned long long gi = atomicAdd(out.counter, 1ull);
+        if (gi < (unsigned long long)out.cap) {
+            if (okey) okey[gi] = (out_t)kEmptyKey64;
+            if (ocnt) ocnt[gi] = (out_t)c;
+            if (osum) osum[gi] = (long long)acc.sum[cap];
+            if (omin) omin[gi] = (out_t)mn[cap];
+            if (omax) omax[gi] = (out_t)mx[cap];
         }
     }
 }
@@ -1978,6 +2231,33 @@ hipError_t launch_group(const TableDev &t, int layout, const SrcDev &src, const 
     const unsigned tl = grid_for((long long)cap, kProbeTile), g = tl < most ? tl : most;
     if (layout == kWide) hipLaunchKernelGGL(k_emit_groups<kWide>, dim3(g), dim3(kBlock), 0, st, t, acc, out);
     else hipLaunchKernelGGL(k_emit_groups<kNarrow>, dim3(g), dim3(kBlock), 0, st, t, acc, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_aggregate(const TableDev &t, int layout, const SrcDev &src, const GroupAcc &acc, const GroupOut &out,
+                            hipStream_t st) {
+    if (layout != kWide && layout != kNarrow) return hipErrorInvalidValue;
+    const unsigned long long cap = t.mask + 1ull, entries = cap + 1ull;
+    hipError_t e = launch_init(t, layout, cap, st);
+    if (e != hipSuccess) return e;
+    // the fill's, the tiles' and the scan's persistent workgroups: eight per CU at most (their LDS)
+    const unsigned most = (unsigned)(cu_count() * 8);
+    const unsigned fl = grid_for((long long)entries, kBlock), gi = fl < most ? fl : most;
+    if (layout == kWide)
+        hipLaunchKernelGGL(k_aggregate_init<kWide>, dim3(gi), dim3(kBlock), 0, st, acc, entries, out.counter);
+    else hipLaunchKernelGGL(k_aggregate_init<kNarrow>, dim3(gi), dim3(kBlock), 0, st, acc, entries, out.counter);
+    if (src.n > 0) {
+        const unsigned tiles = grid_for(src.n, kProbeTile), ga = tiles < most ? tiles : most;
+        e = with_layout_form(layout, src.form, [&](auto l, auto f) {
+            hipLaunchKernelGGL((k_aggregate<decltype(l)::value, decltype(f)::value>), dim3(ga), dim3(kBlock), 0, st, t,
+                               src, acc);
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return e;
+    }
+    const unsigned tl = grid_for((long long)cap, kProbeTile), g = tl < most ? tl : most;
+    if (layout == kWide) hipLaunchKernelGGL(k_emit_aggregate<kWide>, dim3(g), dim3(kBlock), 0, st, t, acc, out);
+    else hipLaunchKernelGGL(k_emit_aggregate<kNarrow>, dim3(g), dim3(kBlock), 0, st, t, acc, out);
     return hipGetLastError();
 }
 

@@ -3684,6 +3684,237 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
     }
 }
 
+// --------------------------------------------------------------- hash aggregate
+// GROUP BY key over ONE partitioned relation (radix_aggregate): one row (key,
+// count, wrapping sum, signed min, max of the payloads) per distinct key.  One
+// item per non-empty partition (radix_detect's work map), one 1024-thread
+// workgroup per CU.  k_join_group's LDS layout and insert -- a CAS that ends at
+// EMPTY or at the key itself, then LDS atomics on the slot's accumulators --
+// with three differences:
+//  * The table persists over the whole item: it is never cleared between the
+//    partition's rows, so it bounds the item's DISTINCT KEYS, not its rows.  A
+//    partition that is one hot key streams through one slot; the slot's count
+//    is 64-bit for int64 rows (32-bit for i32 rows: n < 2^31).
+//  * Overflow is exact.  A workgroup-wide count of claimed slots is read before
+//    every insert; a row that reads more than kAggLimit raises the item's
+//    overflow flag instead of inserting (at most one insert per thread is in
+//    flight behind a passed check, so claims stay <= kAggLimit + kAggNT <
+//    kAggTable and every walk ends).  An overflowed table is dropped and the
+//    item re-run in sub-splits: split (k, p) takes only the keys whose split
+//    hash -- a bijection of the key independent of the partition and slot bits
+//    -- has the top k bits p; an overflow of (k, p) descends to (k + 1, 2p),
+//    a split that fits is emitted and followed by its right sibling, or its
+//    nearest ancestor's (depth-first, a few registers of state).  Nothing of a
+//    dropped table was emitted, each key belongs to exactly one leaf, and a
+//    leaf of one key (k = 64) always fits: no row is dropped, no key emitted
+//    twice, bit 63 never set.  The partition is re-read per split.
+//  * The emit.  After the split's last row the occupied slots are compacted as
+//    k_join_exists compacts (ballots, one scan, ONE add on the output cursor
+//    per split) and stored under cap per element, non-temporally; cap == 0
+//    adds the claimed-slot count alone.  Wide INT64_MIN keys (the EMPTY word)
+//    use LDS words beside the table and are the row behind the split's others.
+// kAggTable = 3840 slots (not a power of two: slot = a multiply-shift of the
+// hash bits below the partition bits): 5 x 8 B x 3840 = 150 KiB for int64 rows
+// with the 64-bit count, 105 KiB for i32 rows; a power of two would be 2^12
+// (160 KiB + the words beside it: over the limit) or 2^11 (1280 keys admitted,
+// below the planner's 2048 rows per partition).  Columns, cap == 0 and the
+// split are wave-uniform runtime branches.
+constexpr int kAggTable = 3840, kAggLimit = 2400;
+constexpr int kAggNT = 1024, kAggRI = 2;
+struct AggCols {
+    void *key, *cnt, *sum, *mn, *mx;
+};
+__device__ __forceinline__ u64 agg_split_hash(u64 k) {
+    u64 x = k * 0xD6E8FEB86659FD93ull;
+    x ^= x >> 32;
+    return x * 0xFF51AFD7ED558CCDull;
+}
+template <bool WIDE>
+__global__ __launch_bounds__(kAggNT, 4) void k_join_aggregate(JoinArgs a, AggCols g) {
+    typedef Row<WIDE> R;
+    typedef typename R::T T;
+    typedef typename std::conditional<WIDE, u64, unsigned>::type PT;          // output element (key, cnt, min, max)
+    typedef typename std::conditional<WIDE, long long, unsigned>::type MT;    // the extremes' order (i32: row ids < 2^31)
+    typedef typename std::conditional<WIDE, u64, unsigned>::type CT;          // a key's count
+    constexpr int TS = kAggTable, NT = kAggNT, NW = NT / 64, RI = kAggRI;
+    constexpr int SI = (TS + NT - 1) / NT;   // slots per thread of the emit
+    static_assert(SI * NW <= 64, "one lane per (slot row, wave) run");
+    static_assert(kAggLimit + NT < TS, "claims behind a passed check must leave an empty slot");
+    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    constexpr MT kMinInit = WIDE ? (MT)0x7fffffffffffffffll : (MT)0xffffffffu;
+    constexpr MT kMaxInit = WIDE ? (MT)0x8000000000000000ull : (MT)0u;
+    __shared__ u64 tkey[TS];
+    __shared__ u64 tsum[TS];
+    __shared__ MT tmin[TS];
+    __shared__ MT tmax[TS];
+    __shared__ CT tcnt[TS];
+    __shared__ unsigned s_cw[SI * NW];
+    __shared__ u64 s_base;
+    __shared__ unsigned s_tot, s_claimed, s_over;
+    __shared__ CT s_nullc;
+    __shared__ u64 s_nullsum;
+    __shared__ MT s_nullmin, s_nullmax;
+
+    const unsigned total = a.work_start[a.P];
+    if (blockIdx.x >= total) return;
+    const T *rows = (const T *)a.r;
+    PT *okey = (PT *)g.key;
+    PT *ocnt = (PT *)g.cnt;
+    u64 *osum = (u64 *)g.sum;
+    PT *omin = (PT *)g.mn;
+    PT *omax = (PT *)g.mx;
+    const bool w_cnt = ocnt != nullptr, w_sum = osum != nullptr, w_min = omin != nullptr, w_max = omax != nullptr;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
+    const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
+    const u64 lt = off ? (~0ull >> (64 - off)) : 0ull;
+
+    for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
+        const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
+        unsigned k = 0;   // the split: the keys whose split hash has the top k bits pre
+        u64 pre = 0ull;
+        while (true) {
+            __syncthreads();   // the previous table's emit is done
+            for (int j = threadIdx.x; j < TS; j += NT) tkey[j] = kEmpty;
+            if (w_cnt)
+                for (int j = threadIdx.x; j < TS; j += NT) tcnt[j] = 0;
+            if (w_sum)
+                for (int j = threadIdx.x; j < TS; j += NT) tsum[j] = 0ull;
+            if (w_min)
+                for (int j = threadIdx.x; j < TS; j += NT) tmin[j] = kMinInit;
+            if (w_max)
+                for (int j = threadIdx.x; j < TS; j += NT) tmax[j] = kMaxInit;
+            if (threadIdx.x == 0) {
+                s_claimed = 0u;
+                s_over = 0u;
+                s_nullc = 0;
+                s_nullsum = 0ull;
+                s_nullmin = kMinInit;
+                s_nullmax = kMaxInit;
+            }
+            __syncthreads();
+            // ---- the partition's rows of this split, RI runs per wave at a time
+            for (u64 r0 = it.r_lo + wave; r0 < it.r_hi; r0 += (u64)RI * NW) {
+                if (__hip_atomic_load(&s_over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+                T br[RI];
+                unsigned rok = 0;
+#pragma unroll
+                for (int i = 0; i < RI; ++i) {
+                    const u64 li = r0 + (u64)i * NW;
+                    const u64 e = li < it.r_hi ? sload(a.r_runs + li) : 0ull;
+                    br[i] = R::zero();
+                    if (off < (unsigned)(e & 127u)) {
+                        br[i] = ld_s<kNtJoinLd>(rows + (e >> 7) + off);
+                        rok |= 1u << i;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < RI; ++i) {
+                    if (!((rok >> i) & 1u)) continue;
+                    const u64 key = R::key(br[i]);
+                    const u64 val = R::pay(br[i]);
+                    if (k != 0u && (agg_split_hash(key) >> (64u - k)) != pre) continue;
+                    if (WIDE && key == kEmptyKey64) {
+                        atomicAdd(&s_nullc, (CT)1);
+                        if (w_sum) atomicAdd(&s_nullsum, val);
+                        if (w_min) atomicMin(&s_nullmin, (MT)val);
+                        if (w_max) atomicMax(&s_nullmax, (MT)val);
+                        continue;
+                    }
+                    if (__hip_atomic_load(&s_claimed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >
+                        (unsigned)kAggLimit) {
+                        __hip_atomic_store(&s_over, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        continue;
+                    }
+                    unsigned h = (unsigned)(((u64)(unsigned)((rhash(key) << a.tshift) >> 32) * (u64)TS) >> 32);
+                    while (true) {   // ends at EMPTY (claimed) or at the key itself
+                        u64 e = __hip_atomic_load(&tkey[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (e == kEmpty) {
+                            e = atomicCAS(&tkey[h], kEmpty, key);
+                            if (e == kEmpty) atomicAdd(&s_claimed, 1u);
+                        }
+                        if (e == kEmpty || e == key) break;
+                        h = h + 1u == (unsigned)TS ? 0u : h + 1u;
+                    }
+                    if (w_cnt) atomicAdd(&tcnt[h], (CT)1);
+                    if (w_sum) atomicAdd(&tsum[h], val);
+                    if (w_min) atomicMin(&tmin[h], (MT)val);
+                    if (w_max) atomicMax(&tmax[h], (MT)val);
+                }
+            }
+            __syncthreads();
+            if (s_over != 0u) {   // (uniform) more distinct keys than the table admits: the left half of this split
+                ++k;
+                pre <<= 1;
+                continue;
+            }
+            // ---- emit this split's keys
+            const CT nullc = WIDE ? s_nullc : (CT)0;
+            if (a.cap == 0) {   // (uniform) count only
+                const u64 x = (u64)s_claimed + (nullc ? 1ull : 0ull);
+                if (threadIdx.x == 0 && x) atomicAdd(a.counter, x);
+            } else {
+                u64 ek[SI];
+                unsigned keep = 0;
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    const int j = i * NT + (int)threadIdx.x;
+                    ek[i] = j < TS ? tkey[j] : kEmpty;
+                    if (ek[i] != kEmpty) keep |= 1u << i;
+                }
+                unsigned lpre[SI];
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    const u64 bal = __ballot((keep >> i) & 1u);
+                    lpre[i] = (unsigned)__popcll(bal & lt);
+                    if (off == 0) s_cw[i * NW + wave] = (unsigned)__popcll(bal);
+                }
+                __syncthreads();
+                if (wave == 0) {   // exclusive scan of the SI * NW runs
+                    const unsigned v = off < (unsigned)(SI * NW) ? s_cw[off] : 0u;
+                    const unsigned x = wave_incl_add(v);
+                    if (off < (unsigned)(SI * NW)) s_cw[off] = x - v;
+                    if (off == 63) {
+                        const u64 tot = (u64)x + (nullc ? 1ull : 0ull);
+                        s_tot = x;
+                        s_base = tot ? atomicAdd(a.counter, tot) : 0ull;
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    if (!((keep >> i) & 1u)) continue;
+                    const int j = i * NT + (int)threadIdx.x;
+                    const u64 gi = s_base + s_cw[i * NW + wave] + lpre[i];
+                    if (gi < (u64)a.cap) {
+                        if (okey) st_s<kNtJoinSt>(okey + gi, (PT)ek[i]);
+                        if (w_cnt) st_s<kNtJoinSt>(ocnt + gi, (PT)tcnt[j]);
+                        if (w_sum) st_s<kNtJoinSt>(osum + gi, tsum[j]);
+                        if (w_min) st_s<kNtJoinSt>(omin + gi, (PT)tmin[j]);
+                        if (w_max) st_s<kNtJoinSt>(omax + gi, (PT)tmax[j]);
+                    }
+                }
+                if (threadIdx.x == 0 && nullc) {
+                    const u64 gi = s_base + s_tot;
+                    if (gi < (u64)a.cap) {
+                        if (okey) st_s<kNtJoinSt>(okey + gi, (PT)kEmptyKey64);
+                        if (w_cnt) st_s<kNtJoinSt>(ocnt + gi, (PT)nullc);
+                        if (w_sum) st_s<kNtJoinSt>(osum + gi, s_nullsum);
+                        if (w_min) st_s<kNtJoinSt>(omin + gi, (PT)s_nullmin);
+                        if (w_max) st_s<kNtJoinSt>(omax + gi, (PT)s_nullmax);
+                    }
+                }
+            }
+            // ---- the next split: the right sibling, or the nearest ancestor's
+            while (k != 0u && (pre & 1ull)) {
+                pre >>= 1;
+                --k;
+            }
+            if (k == 0u) break;
+            pre |= 1ull;
+        }
+    }
+}
+
 // --------------------------------------------------------------- join shapes
 // One product kernel per (row width, shape), chosen from facts known when
 // the join is launched -- never from an earlier join's statistics:
@@ -4467,6 +4698,27 @@ hipError_t radix_group(bool wide, const RadixPlan &pl, const RadixWork &ws, cons
         hipLaunchKernelGGL((k_join_group<true, kGroupNT, kGroupSI, kGroupWPS>), dim3(grid), dim3(kGroupNT), 0, st, a, g);
     else
         hipLaunchKernelGGL((k_join_group<false, kGroupNT, kGroupSI, kGroupWPS>), dim3(grid), dim3(kGroupNT), 0, st, a, g);
+    return hipGetLastError();
+}
+
+// k_join_aggregate over radix_detect's work map: one item per non-empty
+// partition of s (a map from s.rstart alone: P + 1 items at most, which the
+// work area of any bucket set covers); an empty partition is no item and emits
+// nothing.  One workgroup per CU (its table).
+hipError_t radix_aggregate(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &s, const GroupOut &out,
+                           hipStream_t st) {
+    const int P = 1 << pl.total_bits;
+    const unsigned pg = (unsigned)cu_count();
+    WorkMapSpec m;
+    m.counter = out.counter;
+    const WorkMap w = work_map(pl, P, ws, s, nullptr, m, st);
+    if (!w.items) return hipErrorInvalidValue;
+    JoinArgs a = join_args(wide, pl, s, s, P, ws, OutDev{out.r, nullptr, out.cap, out.counter}, nullptr, nullptr);
+    a.tshift = pl.skip + pl.total_bits;   // the hash bits above the LDS slot's (k_join_aggregate shifts them out)
+    const AggCols g{out.r, out.cnt, out.sum, out.mn, out.mx};
+    const unsigned grid = w.items < pg ? w.items : pg;
+    if (wide) hipLaunchKernelGGL((k_join_aggregate<true>), dim3(grid), dim3(kAggNT), 0, st, a, g);
+    else hipLaunchKernelGGL((k_join_aggregate<false>), dim3(grid), dim3(kAggNT), 0, st, a, g);
     return hipGetLastError();
 }
 

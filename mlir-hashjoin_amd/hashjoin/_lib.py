@@ -29,6 +29,7 @@ HJ_EXISTS_ANTI = 1
 HJ_JOIN_KERNEL_EXISTS = 6
 HJ_JOIN_KERNEL_LOOKUP = 7
 HJ_JOIN_KERNEL_GROUP = 8
+HJ_JOIN_KERNEL_AGGREGATE = 9
 HJ_GROUP_MATCHED = 0
 HJ_GROUP_ALL = 1
 HJ_OUTER_BUILD = 1
@@ -95,6 +96,10 @@ def _load():
         "hj_dev_group_tuples_i64": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_group_i32": (_int, [_vp, _int, _vp, _i64, _i64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
         "hj_ctx_reserve_group": (_int, [_vp, _i64, _int]),
+        "hj_dev_aggregate_i64": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_aggregate_tuples_i64": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_aggregate_i32": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+        "hj_ctx_reserve_aggregate": (_int, [_vp, _i64, _int]),
         "hj_dev_probe_outer_i64": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_probe_outer_tuples_i64": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_probe_outer_i32": (_int, [_vp, _vp, _i64, _i64, C.c_int32, _vp, _vp, _i64, _vp, _vp]),

@@ -85,6 +85,11 @@ class HashJoin:
         num_tuples rows (hj_ctx_reserve_group), so probe_group allocates nothing."""
         check(lib.hj_ctx_reserve_group(self._ctx, int(num_tuples), int(key_bits)), "hj_ctx_reserve_group")
 
+    def reserve_aggregate(self, num_tuples, key_bits=64):
+        """Size the workspace for aggregates of up to num_tuples rows under the
+        current strategy (hj_ctx_reserve_aggregate), so aggregate_into allocates nothing."""
+        check(lib.hj_ctx_reserve_aggregate(self._ctx, int(num_tuples), int(key_bits)), "hj_ctx_reserve_aggregate")
+
     def probe_hint(self, num_tuples):
         """The probe side's expected rows, given before the build (None or < 0:
         unknown).  AUTO spares a mid-size build the radix partition it keeps
@@ -125,14 +130,15 @@ class HashJoin:
         return bool(r)
 
     JOIN_KERNELS = {1: "k_join_b", 2: "k_join_u", 3: "k_join_u_stream", 4: "k_join_grp", 5: "k_join",
-                    6: "k_join_exists", 7: "k_join_lookup", 8: "k_join_group"}
+                    6: "k_join_exists", 7: "k_join_lookup", 8: "k_join_group", 9: "aggregate"}
 
     @property
     def join_kernel(self):
         """Kernel of the last radix join (hj_ctx_join_kernel): 'k_join_b',
         'k_join_u_stream', 'k_join_grp', 'k_join', 'k_join_exists' (a radix
         semi- / anti-join), 'k_join_lookup' (a radix lookup), 'k_join_group' (a
-        radix group probe), or None (no radix join)."""
+        radix group probe), 'aggregate' (a radix hash aggregate: k_join_aggregate),
+        or None (no radix join)."""
         r = lib.hj_ctx_join_kernel(self._ctx)
         if r < 0:
             check(r, "hj_ctx_join_kernel")
@@ -448,6 +454,80 @@ class HashJoin:
                 return out_r[:m], {a: c[:m] for a, c in cols.items()}
             cap = m
         raise RuntimeError("group join output did not fit after resizing")
+
+    # ---- hash aggregate (hj.h "Hash aggregate"): GROUP BY key over one relation, no build
+    def aggregate_into(self, key, val=None, out_key=None, out_cnt=None, out_sum=None, out_min=None, out_max=None,
+                       count=None, row_base=0, stream=None):
+        """GROUP BY key over one relation: one row per distinct key holding the
+        key and the count, wrapping int64 sum, signed min and max of val over
+        the rows with it, aligned at the same index of each column passed.  Any
+        column may be None (not computed); out_key alone is DISTINCT, all None
+        counts the distinct keys.  int32 keys: the value is the row id row_base
+        + row (val stays None), out_sum stays int64.  Needs no build and leaves
+        none: the context's table is taken, probes need a new build_table.
+        `count` (int64 device tensor) receives M.  Returns count."""
+        _need_cuda(key, val, out_key, out_cnt, out_sum, out_min, out_max)
+        st = _stream(self.device, stream)
+        count = self._count if count is None else count
+        if key.dtype not in (torch.int64, torch.int32):
+            raise TypeError("keys must be int32 or int64")
+        cap = self._group_outputs(key.dtype, out_key, out_cnt, out_sum, out_min, out_max)
+        outs = (_ptr(out_key), _ptr(out_cnt), _ptr(out_sum), _ptr(out_min), _ptr(out_max))
+        if key.dtype == torch.int64:
+            if val is not None and (val.dtype != torch.int64 or val.numel() != key.numel()):
+                raise ValueError("int64 keys need an int64 value column of the same length")
+            check(lib.hj_dev_aggregate_i64(self._ctx, _ptr(key), _ptr(val), key.numel(), *outs, cap, _ptr(count), st),
+                  "hj_dev_aggregate_i64")
+        else:
+            if val is not None:
+                raise ValueError("i32 rows carry row ids, not values (reference types)")
+            check(lib.hj_dev_aggregate_i32(self._ctx, _ptr(key), key.numel(), int(row_base), *outs, cap, _ptr(count),
+                                           st), "hj_dev_aggregate_i32")
+        return count
+
+    def aggregate_tuples_into(self, tuples, out_key=None, out_cnt=None, out_sum=None, out_min=None, out_max=None,
+                              count=None, stream=None):
+        """aggregate_into over packed (n, 2) int64 {key, value} rows."""
+        _need_cuda(tuples, out_key, out_cnt, out_sum, out_min, out_max)
+        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
+            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        count = self._count if count is None else count
+        cap = self._group_outputs(torch.int64, out_key, out_cnt, out_sum, out_min, out_max)
+        check(lib.hj_dev_aggregate_tuples_i64(self._ctx, _ptr(tuples), tuples.shape[0], _ptr(out_key), _ptr(out_cnt),
+                                              _ptr(out_sum), _ptr(out_min), _ptr(out_max), cap, _ptr(count),
+                                              _stream(self.device, stream)), "hj_dev_aggregate_tuples_i64")
+        return count
+
+    def count_distinct(self, key, stream=None, sync=True):
+        """The number of distinct keys (the aggregate's count-only form)."""
+        cnt = self.aggregate_into(key, stream=stream)
+        return int(cnt.item()) if sync else cnt
+
+    def aggregate(self, key, val=None, aggs=("count", "sum"), capacity=None, stream=None):
+        """GROUP BY key: returns {"key": tensor, agg: tensor, ...} trimmed to M,
+        for aggs among "count", "sum", "min", "max".  capacity=None counts the
+        distinct keys first and allocates exactly; a capacity below M is grown
+        to M and the call repeated.  int32 keys: val is None (row ids)."""
+        if any(a not in GROUP_AGGS for a in aggs):
+            raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
+        dt = key.dtype
+        cap = self.count_distinct(key, stream=stream) if capacity is None else int(capacity)
+        for _ in range(2):
+            cap = max(1, cap)
+            out_key = torch.empty(cap, dtype=dt, device=self.device)
+            cols = {a: torch.empty(cap, dtype=torch.int64 if a == "sum" else dt, device=self.device) for a in aggs}
+            m = int(self.aggregate_into(key, val, out_key, cols.get("count"), cols.get("sum"), cols.get("min"),
+                                        cols.get("max"), stream=stream).item())
+            if m < 0:   # bit 63 (hj.h)
+                raise RuntimeError("hash join: internal work list overflow (count flagged)")
+            if m <= cap:
+                return {"key": out_key[:m], **{a: c[:m] for a, c in cols.items()}}
+            cap = m
+        raise RuntimeError("aggregate output did not fit after resizing")
+
+    def distinct(self, key, capacity=None, stream=None):
+        """SELECT DISTINCT key: the distinct keys, in no particular order."""
+        return self.aggregate(key, aggs=(), capacity=capacity, stream=stream)["key"]
 
     # ---- probe-side outer join (hj.h "Probe-side outer join")
     def probe_outer(self, skey, spay=None, out_r=None, out_s=None, null=-1, count=None, row_base=0, stream=None):
