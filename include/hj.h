@@ -131,7 +131,7 @@ int hj_ctx_last_timing_ex(hj_ctx *ctx, float ms[8]);
 int hj_ctx_timing_accumulate(hj_ctx *ctx, int enable);
 int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 /* RADIX: the join kernel of the last probe, whichever entry point ran it
- * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_probe_full_*, hj_dev_count_*, hj_dev_exists_*, hj_dev_lookup_*, and after a routed build
+ * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_probe_full_*, hj_dev_count_*, hj_dev_exists_*, hj_dev_lookup_*, hj_dev_expand_*, and after a routed build
  * hj_dev_probe_routed_i64 too).  A pure function of the row
  * width, the probe / build size ratio (>= 8: the probe-heavy shape) and the
  * build side's repeated keys, sampled at build time over up to 64 partitions
@@ -155,6 +155,8 @@ int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 #define HJ_JOIN_KERNEL_GROUP 8
 /* k_join_aggregate: the last call was a radix hash aggregate (hj_dev_aggregate_*) */
 #define HJ_JOIN_KERNEL_AGGREGATE 9
+/* k_join_expand: the last probe was a radix expand (hj_dev_expand_*) */
+#define HJ_JOIN_KERNEL_EXPAND 10
 int hj_ctx_join_kernel(hj_ctx *ctx);
 
 /* ------------------------------------------------------------ device phases
@@ -269,6 +271,78 @@ int hj_dev_lookup_i64(hj_ctx *ctx, const int64_t *skey, int64_t n, int64_t null_
                       int64_t *out_r, int32_t *out_cnt, uint64_t *d_count, void *stream);
 int hj_dev_lookup_i32(hj_ctx *ctx, const int32_t *skey, int64_t n, int32_t null_row,
                       int32_t *out_r, int32_t *out_cnt, uint64_t *d_count, void *stream);
+
+/* Expand probe (the join as a CSR: merge(how="inner" | "left") in the left
+ * frame's order, a ragged id -> rows lookup, neighbour lists, an inverted
+ * index, explode) over the table an ordinary hj_dev_build_* left: EVERY
+ * partner of every probe row, at a place known from the row's position.  For
+ * the built relation R and the probe relation S of n rows, with j the row's
+ * position in S as passed in, let c(j) = the number of R rows i with
+ * R.key[i] == S.key[j] and
+ *   HJ_EXPAND_INNER: w(j) = c(j);
+ *   HJ_EXPAND_OUTER: w(j) = max(1, c(j)) -- a row without a partner gets one
+ *                    null entry.
+ * out_off (required, n + 1 int64 words): out_off[j] = the sum of w(i) over
+ * i < j, out_off[n] = M.  Exactly these n + 1 words are written; n == 0 writes
+ * out_off[0] = 0.
+ * out_r[out_off[j] .. out_off[j + 1]) holds the R payloads of row j's partners
+ * (i32: R's row ids, hj_dev_build_i32's row_base + row), each partner exactly
+ * once, a repeated build key one entry per copy; OUTER with c(j) == 0 gives
+ * the single entry null_pay (i32: null_row), written verbatim.
+ * The order INSIDE one segment is unspecified (compare after sorting within
+ * segments); everything else is a function of the data alone and bit-equal
+ * across strategies, kernels and runs -- with a build side that repeats no key
+ * the whole of out_r is.
+ * d_count = M exactly, even when M > out_cap: entries at positions >= out_cap
+ * are dropped, nothing is written at or past out_cap, every position < out_cap
+ * holds its defined value, and the offsets are always complete; bit 63 as
+ * above (no expand path sets it).  out_cap == 0 with out_r NULL is the count
+ * form (offsets and M only); out_cap > 0 with out_r NULL is HJ_ERR_ARG, and so
+ * is out_cap == 0 with out_r non-NULL.
+ * INT64_MIN is a key like any other, on both sides.  R empty: INNER gives
+ * M = 0 and all offsets 0, OUTER n null entries with out_off[j] = j.
+ * Errors in hj_dev_lookup_*'s order: a null context (HJ_ERR_ARG); a kind other
+ * than the two (HJ_ERR_ARG); no build of that layout (HJ_ERR_STATE); a null
+ * count pointer, a bad relation, a null out_off, bad outputs (HJ_ERR_ARG); a
+ * current build of more than INT32_MAX rows (HJ_ERR_ARG: the per-row counts
+ * are int32); for i32, n > INT32_MAX (HJ_ERR_ARG); HJ_ERR_NOMEM when the
+ * workspace does not fit.  The workspace -- one int32 count per probe row and
+ * one uint64 per 2048 of them -- lives in the context, grow-only, allocated by
+ * the call or ahead by hj_ctx_reserve_expand.
+ * Asynchronous on the stream, kernels ONLY once hj_ctx_reserve /
+ * hj_ctx_reserve_probe / hj_ctx_reserve_expand sized the workspace (the
+ * counter is written by a kernel, not by a memset): capturable as a linear
+ * graph.  Three stages: the per-row counts (the lookup's kernels without their
+ * payload column), a scan of them in three launches in which no workgroup
+ * waits on another, and a fill that walks each row's partners again and stores
+ * them at out_off[j] + k; RADIX partitions S ONCE and both stages share that
+ * partition and its work map.  The strategy is chosen exactly as for
+ * hj_dev_probe_* (the AUTO dual build included) and hj_ctx_strategy_used
+ * reports it; the probe timing works as for hj_dev_lookup_* (RADIX: [4] S's
+ * one partition, [5] everything after) and hj_ctx_join_kernel returns
+ * HJ_JOIN_KERNEL_EXPAND after a radix expand.  Nothing the build left is
+ * written -- not the table, R's partition, the side list, the "build keys
+ * repeat" flag or the mark bitmap: expand, lookup, group, inner, semi, anti,
+ * outer, build and full probes of one build may follow each other in any order
+ * and each returns what it returned before.  Valid after
+ * hj_dev_build_routed_i64 too, over unrouted rows.
+ * Cost: a probe row with c partners issues its c stores
+ * one after the other from one lane, and RADIX keeps every copy of a build key
+ * in a slot of its own of one probe chain -- fine at PK-FK fan-out, far from
+ * the grouped inner join's cooperative write path on a build side with ~100
+ * copies per key.
+ * There is no tuples form and no routed bin-range form, for the reasons the
+ * lookup gives. */
+#define HJ_EXPAND_INNER 0   /* w(j) = c(j) */
+#define HJ_EXPAND_OUTER 1   /* w(j) = max(1, c(j)): a row without a partner gets one null entry */
+int hj_dev_expand_i64(hj_ctx *ctx, int kind, const int64_t *skey, int64_t n, int64_t null_pay,
+                      int64_t *out_off, int64_t *out_r, int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_expand_i32(hj_ctx *ctx, int kind, const int32_t *skey, int64_t n, int32_t null_row,
+                      int64_t *out_off, int32_t *out_r, int64_t out_cap, uint64_t *d_count, void *stream);
+/* Sizes the expand probe's count column and scan sums for probe sides of up to
+ * max_probe_rows rows (key_bits 32 / 64), so that hj_dev_expand_* allocates
+ * nothing. */
+int hj_ctx_reserve_expand(hj_ctx *ctx, int64_t max_probe_rows, int key_bits);
 
 /* Group probe (the group join of a query engine: join, then aggregate per
  * build row -- SELECT r.id, count(*), sum(s.v), min(s.v), max(s.v) ... GROUP

@@ -149,6 +149,7 @@ struct hj_ctx {
     Buf nb, pcur, rcur, tile_start, tile_owner, tdesc, wstart, work_start, work_desc, scan_sums, scan_state, raw_cnt;
     Buf slow;   // global-table probe: tiles for the general path
     Buf acc_cnt, acc_sum, acc_min, acc_max;   // global-table group probe: per-slot accumulators (hj::GroupAcc)
+    Buf exp_cnt, exp_sums;                    // expand probe: per-row int32 partner counts, the scan's tile sums
     Buf rows_kx, rows_ky, rows_px, rows_py;   // row materialisation: key columns, pair row ids
     Buf sel_tiles, sel_sums;                  // selection: per-tile counts (then offsets), scan sums
     Buf route_hist, route_sums;               // folded routing: (bin, workgroup) slot bases, scan sums
@@ -221,6 +222,7 @@ struct hj_ctx {
     bool exists_ran = false;   // the last probe was a radix semi- / anti-join (HJ_JOIN_KERNEL_EXISTS)
     bool lookup_ran = false;   // the last probe was a radix lookup (HJ_JOIN_KERNEL_LOOKUP)
     bool group_ran = false;    // the last probe was a radix group probe (HJ_JOIN_KERNEL_GROUP)
+    bool expand_ran = false;   // the last probe was a radix expand (HJ_JOIN_KERNEL_EXPAND)
     bool agg_ran = false;      // an aggregate (hj_dev_aggregate_*) ran since the last build: layout < 0, and used,
                                // plan, bits and n_build describe it
     bool routed = false;   // the current build came from hj_dev_build_routed_i64 (plan.skip owner bits)
@@ -588,7 +590,7 @@ int begin_build(hj_ctx *c, int layout, int64_t n, int used, bool dual, bool rout
     c->routed = routed;
     c->plan = plan;
     c->probe_used = -1;
-    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = c->agg_ran = c->dup_checked = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = c->expand_ran = c->agg_ran = c->dup_checked = false;
     // (hj_count_*'s kept table is gone; a host join's own build keeps the
     // EXACT copies it has just taken of its inputs)
     if (c->host_building) c->memo.valid = false;
@@ -649,7 +651,7 @@ int do_build(hj_ctx *c, int layout, const hj::SrcDev &src, hipStream_t st) {
 
 // One probe of the current build, after the entry point's argument checks.
 enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter, kProbeBuild, kProbeFull, kProbeLookup,
-                 kProbeGroup };
+                 kProbeGroup, kProbeExpand };
 struct ProbeReq {
     RadixSrc in;       // S; routed: bins [bin0, bin0 + in.nbins) of the build's first pass
     int bin0 = 0;
@@ -660,6 +662,8 @@ struct ProbeReq {
     unsigned long long null_pay = 0;   // outer, full, lookup: the R payload of an S row without a partner (outer, full: out.cap == 0 counts only)
     unsigned long long null_s = 0;     // build, full: the S payload of an R row without a partner
     hj::GroupOut grp{};                // group: the result columns, the kind and the null value (its counter is out.counter)
+    long long *out_off = nullptr;      // expand: the n + 1 offsets (out.r the values, may be null with out.cap == 0)
+    bool expand_outer = false;         // expand: a row without a partner gets one null_pay entry
 };
 
 // The global-table group probe's accumulators for a table of 2^bits slots (and
@@ -673,6 +677,12 @@ int ensure_group_acc(hj_ctx *c, int bits, int layout, bool sum, bool mn, bool mx
     return HJ_OK;
 }
 
+// The expand probe's workspace for n probe rows: the count column and the scan's tile sums.
+int ensure_expand(hj_ctx *c, int64_t n) {
+    HJ_TRY(ensure_buf(c->exp_cnt, (size_t)(n > 0 ? n : 0) * sizeof(int)));
+    return ensure_buf(c->exp_sums, hj::expand_scan_tiles(n) * sizeof(unsigned long long));
+}
+
 int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
     HJ_TRY(set_device(c));
     const hj::SrcDev &src = q.in.src;
@@ -682,11 +692,21 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
     const bool r_nulls = q.kind == kProbeBuild || q.kind == kProbeFull;
     const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
     c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
-    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = c->expand_ran = false;
+    if (q.kind == kProbeExpand) HJ_TRY(ensure_expand(c, src.n));
     if (!radix) {
-        HJ_HIP(hipMemsetAsync(q.out.counter, 0, sizeof(uint64_t), st));
+        // (expand: the scan's last launch stores the counter, nothing reads it before)
+        if (q.kind != kProbeExpand) HJ_HIP(hipMemsetAsync(q.out.counter, 0, sizeof(uint64_t), st));
         record(c, kEvProbe0, st);
-        if (exists) {
+        if (q.kind == kProbeExpand) {
+            // counts (the lookup's kernel without its payload column), their scan, the fill
+            const hj::OutDev cnt_out{nullptr, nullptr, src.n, q.out.counter};
+            HJ_HIP(hj::launch_probe_lookup(table_dev(c), c->layout, src, cnt_out, (int *)c->exp_cnt.p, 0ull, st));
+            HJ_HIP(hj::launch_expand_scan((const int *)c->exp_cnt.p, src.n, q.expand_outer,
+                                          (unsigned long long *)c->exp_sums.p, q.out_off, q.out.counter, st));
+            HJ_HIP(hj::launch_probe_expand(table_dev(c), c->layout, src, q.out_off, q.out.r, q.out.cap, q.expand_outer,
+                                           q.null_pay, st));
+        } else if (exists) {
             HJ_HIP(hj::launch_probe_exists(table_dev(c), c->layout, src, q.out, q.kind == kProbeAnti, st));
         } else if (q.kind == kProbeLookup) {
             HJ_HIP(hj::launch_probe_lookup(table_dev(c), c->layout, src, q.out, q.out_cnt, q.null_pay, st));
@@ -720,7 +740,7 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
         HJ_TRY(ensure_radix_scratch(c, c->sset, src.n, wide, c->plan, q.in.nsrc));
         trace("probe: workspace", st, (long long)c->sset.max_buckets);
         record(c, kEvProbe0, st);
-        if ((q.kind == kProbeLookup || (q.kind == kProbeGroup && !src.pay && src.form == hj::kCols64)) && wide) {
+        if ((q.kind == kProbeLookup || q.kind == kProbeExpand || (q.kind == kProbeGroup && !src.pay && src.form == hj::kCols64)) && wide) {
             // S's rows carry their index through the passes: the key column alone is read
             // (a group probe without a value column: no aggregate reads the payload)
             RadixSrc in = q.in;
@@ -747,6 +767,11 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
             HJ_RADIX(c, st, hj::radix_lookup(wide, q.null_pay, src.n, c->plan, radix_work(c), r, bucket_set(c->sset),
                                              q.out, q.out_cnt, st));
             c->lookup_ran = true;
+        } else if (q.kind == kProbeExpand) {
+            HJ_RADIX(c, st, hj::radix_expand(wide, q.expand_outer, q.null_pay, src.n, c->plan, radix_work(c), r,
+                                             bucket_set(c->sset), q.out, (int *)c->exp_cnt.p, q.out_off,
+                                             (unsigned long long *)c->exp_sums.p, st));
+            c->expand_ran = true;
         } else if (q.kind == kProbeGroup) {
             HJ_RADIX(c, st, hj::radix_group(wide, c->plan, radix_work(c), r, bucket_set(c->sset), q.grp, st));
             c->group_ran = true;
@@ -827,6 +852,31 @@ int do_lookup(hj_ctx *c, int layout, const hj::SrcDev &src, unsigned long long n
     q.out = hj::OutDev{out_r, nullptr, src.n, (unsigned long long *)d_count};
     q.out_cnt = out_cnt;
     q.kind = kProbeLookup;
+    q.null_pay = null_pay;
+    return run_probe(c, q, st);
+}
+
+// Expand probe (hj_dev_expand_*): every partner of S row j at out_r[out_off[j] ..
+// out_off[j + 1]).  do_lookup's order of checks behind the kind's.  Reads what
+// do_lookup reads.
+int do_expand(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, unsigned long long null_pay, int64_t *out_off,
+              void *out_r, int64_t cap, uint64_t *d_count, hipStream_t st) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (kind != HJ_EXPAND_INNER && kind != HJ_EXPAND_OUTER)
+        HJ_FAIL(HJ_ERR_ARG, "kind must be HJ_EXPAND_INNER or HJ_EXPAND_OUTER");
+    if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, "probe without a matching build");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
+    if (!out_off) HJ_FAIL(HJ_ERR_ARG, "null offsets (n + 1 int64 words)");
+    if (cap < 0 || (cap > 0 && !out_r) || (cap == 0 && out_r)) HJ_FAIL(HJ_ERR_ARG, "bad output");
+    if (c->n_build > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "int32 counts: the build side must have < 2^31 rows");
+    if (layout == kNarrow && src.n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids: probe side must have < 2^31 rows");
+    ProbeReq q;
+    q.in.src = src;
+    q.out = hj::OutDev{out_r, nullptr, cap, (unsigned long long *)d_count};
+    q.out_off = (long long *)out_off;
+    q.expand_outer = kind == HJ_EXPAND_OUTER;
+    q.kind = kProbeExpand;
     q.null_pay = null_pay;
     return run_probe(c, q, st);
 }
@@ -1726,7 +1776,7 @@ void hj_ctx_destroy(hj_ctx *c) {
     for (SetBufs *sb : {&c->rset, &c->sset, &c->tset})
         for (Buf *b : {&sb->rows, &sb->bbin, &sb->bfill, &sb->runs, &sb->rstart}) free_buf(*b);
     for (Buf *b : {&c->nb, &c->pcur, &c->rcur, &c->tile_start, &c->tile_owner, &c->tdesc, &c->wstart, &c->work_start, &c->work_desc, &c->scan_sums, &c->scan_state, &c->raw_cnt,
-                   &c->slow, &c->acc_cnt, &c->acc_sum, &c->acc_min, &c->acc_max, &c->rows_kx, &c->rows_ky, &c->rows_px, &c->rows_py, &c->sel_tiles, &c->sel_sums,
+                   &c->slow, &c->acc_cnt, &c->acc_sum, &c->acc_min, &c->acc_max, &c->exp_cnt, &c->exp_sums, &c->rows_kx, &c->rows_ky, &c->rows_px, &c->rows_py, &c->sel_tiles, &c->sel_sums,
                    &c->route_hist, &c->route_sums})
         free_buf(*b);
     for (int k = 0; k < c->ev_made; ++k)
@@ -1788,6 +1838,7 @@ int hj_ctx_join_kernel(hj_ctx *c) {
     if (c->exists_ran && c->layout >= 0) return HJ_JOIN_KERNEL_EXISTS;
     if (c->lookup_ran && c->layout >= 0) return HJ_JOIN_KERNEL_LOOKUP;
     if (c->group_ran && c->layout >= 0) return HJ_JOIN_KERNEL_GROUP;
+    if (c->expand_ran && c->layout >= 0) return HJ_JOIN_KERNEL_EXPAND;
     if (!c->join_ran || c->layout < 0) return 0;
     HJ_TRY(set_device(c));
     unsigned long long v[2] = {0, 0};
@@ -1902,6 +1953,14 @@ int hj_ctx_reserve_group(hj_ctx *c, int64_t max_build_rows, int key_bits) {
     return ensure_group_acc(c, table_bits(max_build_rows), key_bits == 64 ? kWide : kNarrow, true, true, true);
 }
 
+int hj_ctx_reserve_expand(hj_ctx *c, int64_t max_probe_rows, int key_bits) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (max_probe_rows < 0 || (key_bits != 32 && key_bits != 64)) HJ_FAIL(HJ_ERR_ARG, "bad reserve arguments");
+    // (the counts are int32 and the tile sums u64 whatever the key width; both strategies use them)
+    HJ_TRY(set_device(c));
+    return ensure_expand(c, max_probe_rows);
+}
+
 int hj_ctx_reserve_aggregate(hj_ctx *c, int64_t max_rows, int key_bits) {
     if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
     if (max_rows < 0 || (key_bits != 32 && key_bits != 64)) HJ_FAIL(HJ_ERR_ARG, "bad reserve arguments");
@@ -1983,6 +2042,18 @@ int hj_dev_lookup_i32(hj_ctx *c, const int32_t *skey, int64_t n, int32_t null_ro
                       uint64_t *d_count, void *stream) {
     return do_lookup(c, kNarrow, src_col32(skey, n, 0), (unsigned long long)(long long)null_row, out_r, out_cnt,
                      d_count, (hipStream_t)stream);
+}
+
+int hj_dev_expand_i64(hj_ctx *c, int kind, const int64_t *skey, int64_t n, int64_t null_pay, int64_t *out_off,
+                      int64_t *out_r, int64_t out_cap, uint64_t *d_count, void *stream) {
+    // (the key column stands in for the payload column, which no expand kernel reads)
+    return do_expand(c, kWide, kind, src_cols64(skey, skey, n), (unsigned long long)null_pay, out_off, out_r, out_cap,
+                     d_count, (hipStream_t)stream);
+}
+int hj_dev_expand_i32(hj_ctx *c, int kind, const int32_t *skey, int64_t n, int32_t null_row, int64_t *out_off,
+                      int32_t *out_r, int64_t out_cap, uint64_t *d_count, void *stream) {
+    return do_expand(c, kNarrow, kind, src_col32(skey, n, 0), (unsigned long long)(long long)null_row, out_off, out_r,
+                     out_cap, d_count, (hipStream_t)stream);
 }
 
 int hj_dev_group_i64(hj_ctx *c, int kind, const int64_t *skey, const int64_t *sval, int64_t n, int64_t null_val,

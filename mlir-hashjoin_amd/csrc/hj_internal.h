@@ -134,6 +134,21 @@ hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src,
 // One launch; reads meta[0..1], writes no build state.
 hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, int *cnt,
                                unsigned long long null_pay, hipStream_t st);
+// The expand probe's scan (hj_kernels.hip; both strategies): cnt[0..n) are the
+// per-row partner counts (launch_probe_lookup's / radix_lookup's cnt column),
+// width = cnt, or max(1, cnt) when outer.  off[j] = the widths before row j,
+// off[n] = *count = M: exactly n + 1 words, for n == 0 too.  Three launches
+// (tile sums, one workgroup over the tile sums, per-tile scan + prefix), no
+// workgroup waits on another.  sums: expand_scan_tiles(n) u64.
+size_t expand_scan_tiles(long long n);
+hipError_t launch_expand_scan(const int *cnt, long long n, bool outer, unsigned long long *sums, long long *off,
+                              unsigned long long *count, hipStream_t st);
+// The expand probe's fill over the global table (k_probe_expand): the payloads
+// of S row j's partners at out_r[off[j] ..), in chain order, null_pay where an
+// outer row has none; only positions < cap are written (cap <= 0: no launch).
+// src as launch_probe_lookup's.  Reads meta[0..1], writes no build state.
+hipError_t launch_probe_expand(const TableDev &t, int layout, const SrcDev &src, const long long *off, void *out_r,
+                               long long cap, bool outer, unsigned long long null_pay, hipStream_t st);
 // The group probe's result columns (any may be null: neither computed nor
 // stored) and its per-slot accumulators of the global table.  Element types by
 // layout: wide -- every column int64; narrow -- r, cnt, mn, mx int32 and sum
@@ -298,6 +313,17 @@ hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWo
 // r, writes neither it nor the repeat flag.
 hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, const RadixPlan &pl, const RadixWork &ws,
                         const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt, hipStream_t st);
+// Expand probe over the partitioned relations: s partitioned as for
+// radix_lookup (each row carries its index in S), n = |S|.  One work map
+// (radix_lookup's: every non-empty S partition is an item) serves both
+// stages: k_join_lookup with the count column alone fills cnt[0..n), then
+// launch_expand_scan writes off[0..n] and out.counter = M, then (out.cap > 0)
+// k_join_expand stores the payloads of row j's partners at out.r[off[j] ..)
+// below out.cap, null_pay where an outer row has none.  sums:
+// expand_scan_tiles(n) u64.  Reads r, writes neither it nor the repeat flag.
+hipError_t radix_expand(bool wide, bool outer, unsigned long long null_pay, long long n, const RadixPlan &pl,
+                        const RadixWork &ws, const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt,
+                        long long *off, unsigned long long *sums, hipStream_t st);
 // Group probe over the partitioned relations (k_join_group): one row per R row
 // with the count, wrapping sum and signed extremes of the S payloads of its
 // key.  The two bucket sets exchanged as in radix_unmatched_build: S's rows are

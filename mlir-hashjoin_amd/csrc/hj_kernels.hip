@@ -9,7 +9,9 @@
 //                                          reads, ballot-compacted output,
 //                                          one global cursor add per block
 // plus the exists probes (k_probe_exists), the positional lookup probe
-// (k_probe_lookup), the outer probe (k_probe_outer),
+// (k_probe_lookup), the expand probe's scan and global-table fill
+// (k_expand_sums, k_expand_scan_sums, k_expand_offsets, k_probe_expand),
+// the outer probe (k_probe_outer),
 // the build-side outer stages (k_probe_mark, k_emit_unmatched),
 // the group probe (k_group_init, k_probe_group, k_emit_groups),
 // the hash aggregate (k_aggregate, k_emit_aggregate),
@@ -21,7 +23,7 @@
 // independent, no warp-32 idioms.  Integer/byte work: no MFMA.
 //
 // Written once, used by several kernels / launchers:
-//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists, k_probe_lookup, k_probe_outer)
+//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists, k_probe_lookup, k_probe_expand, k_probe_outer)
 //   wave_incl_add    every wave prefix sum (hj_internal.h: DPP, no LDS round trips)
 //   with_layout_form the (layout, form) -> template-argument dispatch of the launchers
 //   probe_grid       the tile probes' grid and LDS bytes
@@ -833,6 +835,173 @@ __global__ __launch_bounds__(kBlock) void k_probe_lookup(TableDev t, SrcDev src,
 #pragma unroll
         for (int w = 0; w < NW; ++w) sum += s_hits[w];
         if (sum) atomicAdd(out.counter, sum);
+    }
+}
+
+// ------------------------------------------------------------------ expand probe
+// Every partner of S row j at out_r[off[j] .. off[j + 1]): a CSR.  Three
+// stages share one per-row int32 count column (k_probe_lookup without its
+// payload output, or k_join_lookup): the scan below turns the counts into the
+// int64 offsets, then a fill kernel (k_probe_expand here, k_join_expand of the
+// radix join) walks each row's chain again and stores at off[j] + k.
+//
+// The scan is reduce-then-scan in three launches, so that no workgroup ever
+// waits on another: k_expand_sums (one u64 sum per tile of kExpandTile
+// counts), k_expand_scan_sums (ONE workgroup turns the tile sums into their
+// exclusive prefix, kExpandFan of them per step with a running carry) and
+// k_expand_offsets (each tile's own exclusive scan plus its prefix; the last
+// thread of the last tile also writes off[n] = M and the call's counter).
+// width(c) = c for the inner kind, max(1, c) for the outer one (outer = 1).
+constexpr int kExpandItems = 8;
+constexpr int kExpandTile = kBlock * kExpandItems;
+constexpr int kExpandFan = 1024;
+
+__device__ __forceinline__ unsigned long long expand_width(int c, unsigned outer) {
+    return c ? (unsigned long long)(unsigned)c : (unsigned long long)outer;
+}
+// exclusive prefix of v over the workgroup's NT threads and its total (all threads call)
+template <int NT>
+__device__ __forceinline__ unsigned long long block_excl_add64(unsigned long long v, unsigned long long *wsum,
+                                                               unsigned long long &total) {
+    constexpr int NW = NT / 64;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long inc = wave_incl_add64(v);
+    __syncthreads();   // wsum's previous readers are done
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    unsigned long long before = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        const unsigned long long s = wsum[w];
+        before += w < wv ? s : 0ull;
+        tot += s;
+    }
+    total = tot;
+    return before + inc - v;
+}
+// a thread's kExpandItems consecutive widths of tile blockIdx.x (0 past n) and their sum
+__device__ __forceinline__ unsigned long long expand_load(const int *cnt, long long n, unsigned outer,
+                                                          unsigned long long (&w)[kExpandItems]) {
+    const long long base = (long long)blockIdx.x * kExpandTile + (long long)threadIdx.x * kExpandItems;
+    unsigned long long s = 0;
+    if (base + kExpandItems <= n) {   // (cnt is the context's own buffer: 16-B aligned at every tile's thread base)
+        const int4 a = ((const int4 *)(cnt + base))[0], b = ((const int4 *)(cnt + base))[1];
+        const int c[kExpandItems] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int i = 0; i < kExpandItems; ++i) w[i] = expand_width(c[i], outer);
+    } else {
+#pragma unroll
+        for (int i = 0; i < kExpandItems; ++i) w[i] = base + i < n ? expand_width(cnt[base + i], outer) : 0ull;
+    }
+#pragma unroll
+    for (int i = 0; i < kExpandItems; ++i) s += w[i];
+    return s;
+}
+__global__ __launch_bounds__(kBlock) void k_expand_sums(const int *cnt, long long n, unsigned outer,
+                                                        unsigned long long *sums) {
+    __shared__ unsigned long long wsum[kBlock / 64];
+    unsigned long long w[kExpandItems], total;
+    const unsigned long long s = expand_load(cnt, n, outer, w);
+    block_excl_add64<kBlock>(s, wsum, total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(kExpandFan) void k_expand_scan_sums(unsigned long long *sums, unsigned long long nt) {
+    __shared__ unsigned long long wsum[kExpandFan / 64];
+    unsigned long long carry = 0;
+    for (unsigned long long b = 0; b < nt; b += kExpandFan) {
+        const unsigned long long i = b + threadIdx.x;
+        const unsigned long long v = i < nt ? sums[i] : 0ull;
+        unsigned long long total;
+        const unsigned long long ex = block_excl_add64<kExpandFan>(v, wsum, total);
+        if (i < nt) sums[i] = carry + ex;
+        carry += total;
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_expand_offsets(const int *cnt, long long n, unsigned outer,
+                                                           const unsigned long long *sums, long long *off,
+                                                           unsigned long long *count) {
+    __shared__ unsigned long long wsum[kBlock / 64];
+    unsigned long long w[kExpandItems], total;
+    const unsigned long long s = expand_load(cnt, n, outer, w);
+    unsigned long long run = sums[blockIdx.x] + block_excl_add64<kBlock>(s, wsum, total);
+    const long long base = (long long)blockIdx.x * kExpandTile + (long long)threadIdx.x * kExpandItems;
+#pragma unroll
+    for (int i = 0; i < kExpandItems; ++i) {
+        if (base + i < n) off[base + i] = (long long)run;
+        run += w[i];
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kBlock - 1) {   // (rows past n added 0: run is M)
+        off[n] = (long long)run;
+        *count = run;
+    }
+}
+
+// The global table's fill: k_probe_lookup's tile shape over S's keys alone --
+// 2048-row tiles, every row's first slot load (and its offset) issued before
+// any walk, TableView -- where row j walks its chain to EMPTY (to the first
+// equal key when the build's repeat flag meta[1] is clear) and stores every
+// equal key's payload at pos++, pos starting at off[j], while pos < cap.  A
+// wide INT64_MIN probe key copies the side list's meta[0] payloads.  Outer: a
+// row that stored nothing writes null_pay.  No cursor, no atomics, no counter:
+// every position is a function of the scan.  outer and cap are kernel
+// arguments (wave-uniform); only `pos < cap` is a lane's own.
+template <int L, int FORM, bool LDS>
+__global__ __launch_bounds__(kBlock) void k_probe_expand(TableDev t, SrcDev src, const long long *off, void *out_r,
+                                                         unsigned long long cap, unsigned outer,
+                                                         unsigned long long null_pay) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    extern __shared__ ulonglong2 s_tab[];
+
+    const TableView<L, LDS> tab(t, s_tab);
+    const bool unique = (__hip_atomic_load(&t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull);
+    const unsigned long long side_n = L == kWide ? t.meta[0] : 0ull;   // INT64_MIN build rows
+    out_t *orr = (out_t *)out_r;
+    const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long K[kProbeItems], H[kProbeItems], P[kProbeItems];
+        unsigned valid = 0, walk = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const long long row = (long long)q * kProbeTile + (long long)i * kBlock + threadIdx.x;
+            K[i] = 0ull;
+            P[i] = 0ull;
+            if (row < src.n) {
+                valid |= 1u << i;
+                K[i] = load_key<FORM>(src, row);
+                P[i] = (unsigned long long)off[row];
+                if (!LY::null_key(K[i])) walk |= 1u << i;
+            }
+        }
+        slot_t S[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            H[i] = slot_of(K[i], t.shift);
+            if ((walk >> i) & 1u) S[i] = tab.at(H[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((valid >> i) & 1u)) continue;
+            unsigned long long pos = P[i];
+            if ((walk >> i) & 1u) {
+                slot_t sv = S[i];
+                unsigned long long hh = H[i];
+                while (!LY::empty(sv)) {
+                    if (LY::key(sv) == K[i]) {
+                        if (pos < cap) orr[pos] = (out_t)LY::pay(sv);
+                        ++pos;
+                        if (unique) break;
+                    }
+                    hh = (hh + 1) & t.mask;
+                    sv = tab.at(hh);
+                }
+            } else {
+                for (unsigned long long j = 0; j < side_n; ++j, ++pos)
+                    if (pos < cap) orr[pos] = (out_t)t.side[j];
+            }
+            if (outer && pos == P[i] && pos < cap) orr[pos] = (out_t)null_pay;
+        }
     }
 }
 
@@ -2141,6 +2310,37 @@ hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src,
         constexpr int L = decltype(l)::value, F = decltype(f)::value;
         const auto k = pg.lds ? k_probe_lookup<L, F, true> : k_probe_lookup<L, F, false>;
         hipLaunchKernelGGL(k, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, out, cnt, null_pay);
+        return hipGetLastError();
+    };
+    if (layout == kWide && src.form == kCols64) return launch(int_c<kWide>{}, int_c<kCols64>{});
+    if (layout == kNarrow && src.form == kCol32) return launch(int_c<kNarrow>{}, int_c<kCol32>{});
+    return hipErrorInvalidValue;
+}
+
+size_t expand_scan_tiles(long long n) { return n > 0 ? (size_t)((n + kExpandTile - 1) / kExpandTile) : 1; }
+
+hipError_t launch_expand_scan(const int *cnt, long long n, bool outer, unsigned long long *sums, long long *off,
+                              unsigned long long *count, hipStream_t st) {
+    // (n == 0: one workgroup over no rows writes off[0] = 0 and the counter)
+    const long long rows = n > 0 ? n : 0;
+    const unsigned tiles = (unsigned)expand_scan_tiles(rows);
+    const unsigned o = outer ? 1u : 0u;
+    hipLaunchKernelGGL(k_expand_sums, dim3(tiles), dim3(kBlock), 0, st, cnt, rows, o, sums);
+    hipLaunchKernelGGL(k_expand_scan_sums, dim3(1), dim3(kExpandFan), 0, st, sums, (unsigned long long)tiles);
+    hipLaunchKernelGGL(k_expand_offsets, dim3(tiles), dim3(kBlock), 0, st, cnt, rows, o,
+                       (const unsigned long long *)sums, off, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_probe_expand(const TableDev &t, int layout, const SrcDev &src, const long long *off, void *out_r,
+                               long long cap, bool outer, unsigned long long null_pay, hipStream_t st) {
+    if (src.n <= 0 || cap <= 0) return hipSuccess;
+    const ProbeGrid pg = probe_grid(t, layout, src.n);
+    auto launch = [&](auto l, auto f) {
+        constexpr int L = decltype(l)::value, F = decltype(f)::value;
+        const auto k = pg.lds ? k_probe_expand<L, F, true> : k_probe_expand<L, F, false>;
+        hipLaunchKernelGGL(k, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, off, out_r,
+                           (unsigned long long)cap, outer ? 1u : 0u, null_pay);
         return hipGetLastError();
     };
     if (layout == kWide && src.form == kCols64) return launch(int_c<kWide>{}, int_c<kCols64>{});

@@ -3434,6 +3434,182 @@ __global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cn
     if (off == 63 && x) atomicAdd(a.counter, (u64)x);
 }
 
+// --------------------------------------------------------------- expand join
+// The expand probe's fill (radix_expand): every partner of an S row, stored at
+// offs[row] + k, row being the index the S row carries as its payload.
+// k_join_lookup's structure -- its work map that keeps the items without build
+// rows, its sub-chunks of S rows in registers, its build rounds of RCAP = 5120
+// rows into 2^13 slots, its sub-chunks-outermost path when a partition's build
+// side is more than one round -- over a table of key and payload words alone
+// in which EVERY build row of the round claims a slot of its own (a CAS of
+// EMPTY only, linear probing past equal keys): no minimum, no count.  int64
+// rows 64 + 64 = 128 KiB, i32 rows 64 + 32 = 96 KiB: one workgroup per CU.
+// A probing lane walks from its key's slot to EMPTY and stores the payload of
+// each equal key at its running position pos[i], which is loaded from offs
+// once per sub-chunk and kept in registers across the rounds; only positions
+// below a.cap are written.  A row that has stored nothing after the last round
+// -- the rows of items without build rows among them -- writes null_pay when
+// `outer`, nothing otherwise.  Plain stores (kNtLookupSt).
+// INT64_MIN build keys (wide) cannot sit in a table whose empty word is
+// INT64_MIN, and a round may hold nothing else, so they get a LIST that
+// borrows the payload words: before a round's table is made, the round's
+// INT64_MIN rows append their payloads to tpay[0 .. nn) through an LDS cursor,
+// the sub-chunk's INT64_MIN probe rows copy those nn words out, and only then
+// is the table cleared and filled (tpay[h] is written by the row that claimed
+// tkey[h], so the list needs no clearing).  The list is gone once the table
+// stands, so an item that has shown such a row rebuilds its table for every
+// sub-chunk (renull), as a multi-round item does anyway; all INT64_MIN keys
+// hash to one partition, so at most one partition of a join pays that.
+// Cost: a build key with c copies makes a chain of c slots that every insert
+// of that key and every probe of it walks -- inserts c^2 / 2 LDS steps per
+// round, and a probe row's c stores issue serially from one lane.
+constexpr int kExpandNT = kLookupNT, kExpandSI = kLookupSI, kExpandWPS = kLookupWPS;
+template <bool WIDE, int NT, int SI, int WPS>
+__global__ __launch_bounds__(NT, WPS) void k_join_expand(JoinArgs a, const long long *offs, u64 null_pay,
+                                                          unsigned outer, u64 n) {
+    typedef Row<WIDE> R;
+    typedef typename R::T T;
+    typedef typename std::conditional<WIDE, u64, unsigned>::type PT;   // output element, LDS payload word
+    constexpr int TS = 1 << kExistsTableLog;
+    constexpr unsigned kMask = TS - 1;
+    constexpr int RCAP = TS * 5 / 8;          // build rows per round
+    constexpr int RI = RCAP / NT;             // build rows per thread per round
+    constexpr int NW = NT / 64;
+    constexpr unsigned rb = (unsigned)RCAP >> kRunLog;         // runs per build round
+    constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;  // runs per sub-chunk
+    static_assert(RI * NT == RCAP, "a build round must load exactly RCAP rows");
+    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
+    static_assert(RCAP < TS, "every row of a round has a slot and the walks end at an EMPTY one");
+    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    __shared__ u64 tkey[TS];
+    __shared__ PT tpay[TS];
+    __shared__ unsigned s_nulln;
+
+    const unsigned total = a.work_start[a.P];
+    if (blockIdx.x >= total) return;
+    const T *rrows = (const T *)a.r;
+    const T *srows = (const T *)a.s;
+    PT *orr = (PT *)a.out_r;
+    const u64 cap = (u64)a.cap;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
+    const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
+    if (threadIdx.x == 0) s_nulln = 0u;   // (read behind the first round's barriers)
+
+    for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
+        const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
+        const bool rounds = it.r_hi - it.r_lo > (u64)rb;   // more than one build round
+        bool built = false, renull = false;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += subb) {
+            const u64 shi = sb + subb < it.s_hi ? sb + subb : it.s_hi;
+            T sv[SI];
+            u64 pos[SI];
+            unsigned sok = 0, hit = 0;
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                const u64 li = sb + (u64)i * NW + wave;
+                const u64 e = li < shi ? sload(a.s_runs + li) : 0ull;
+                sv[i] = R::zero();
+                pos[i] = 0ull;
+                if (off < (unsigned)(e & 127u)) {
+                    sv[i] = ld_s<kNtJoinLd>(srows + (e >> 7) + off);
+                    const u64 row = R::pay(sv[i]);
+                    if (row < n) {   // (always: the partition wrote row indices below n)
+                        sok |= 1u << i;
+                        pos[i] = (u64)offs[row];
+                    }
+                }
+            }
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += rb) {
+                if (rounds || !built || renull) {
+                    // ---- build rows of runs [r0, rhi): every row a slot of its own
+                    const u64 rhi = r0 + rb < it.r_hi ? r0 + rb : it.r_hi;
+                    T br[RI];
+                    unsigned rok = 0;
+#pragma unroll
+                    for (int i = 0; i < RI; ++i) {
+                        const u64 li = r0 + (u64)i * NW + wave;
+                        const u64 e = li < rhi ? sload(a.r_runs + li) : 0ull;
+                        br[i] = R::zero();
+                        if (off < (unsigned)(e & 127u)) {
+                            br[i] = rrows[(e >> 7) + off];
+                            rok |= 1u << i;
+                        }
+                    }
+                    __syncthreads();   // the previous table's probes are done
+                    if constexpr (WIDE) {
+                        // ---- the round's INT64_MIN rows, as a list in tpay, copied out before the table is made
+#pragma unroll
+                        for (int i = 0; i < RI; ++i)
+                            if (((rok >> i) & 1u) && R::key(br[i]) == kEmptyKey64)
+                                tpay[atomicAdd(&s_nulln, 1u)] = (PT)R::pay(br[i]);
+                        __syncthreads();
+                        const unsigned nn = s_nulln;
+                        if (nn) {   // (uniform)
+                            renull = true;
+#pragma unroll
+                            for (int i = 0; i < SI; ++i) {
+                                if (!((sok >> i) & 1u) || R::key(sv[i]) != kEmptyKey64) continue;
+                                hit |= 1u << i;
+                                for (unsigned k = 0; k < nn; ++k, ++pos[i])
+                                    if (pos[i] < cap) st_s<kNtLookupSt>(orr + pos[i], tpay[k]);
+                            }
+                        }
+                    }
+                    for (int j = threadIdx.x; j < TS / 2; j += NT)
+                        ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+                    __syncthreads();   // the table is empty, the list has been read
+                    if (WIDE && threadIdx.x == 0) s_nulln = 0u;
+#pragma unroll
+                    for (int i = 0; i < RI; ++i) {
+                        if (!((rok >> i) & 1u)) continue;
+                        const u64 key = R::key(br[i]);
+                        if (WIDE && key == kEmptyKey64) continue;
+                        unsigned h = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                        while (atomicCAS(&tkey[h], kEmpty, key) != kEmpty) h = (h + 1) & kMask;
+                        tpay[h] = (PT)R::pay(br[i]);
+                    }
+                    __syncthreads();
+                    built = true;
+                }
+                // ---- probe every row of the sub-chunk: first slots read before any is resolved
+                unsigned hp[SI];
+                u64 e0[SI];
+                unsigned open = sok;
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    const u64 key = R::key(sv[i]);
+                    if (WIDE && key == kEmptyKey64) open &= ~(1u << i);
+                    hp[i] = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                    e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
+                }
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    if (!((open >> i) & 1u)) continue;
+                    const u64 key = R::key(sv[i]);
+                    unsigned h = hp[i];
+                    u64 e = e0[i];
+                    while (e != kEmpty) {
+                        if (e == key) {
+                            if (pos[i] < cap) st_s<kNtLookupSt>(orr + pos[i], tpay[h]);
+                            ++pos[i];
+                            hit |= 1u << i;
+                        }
+                        h = (h + 1) & kMask;
+                        e = tkey[h];
+                    }
+                }
+            }
+            // ---- outer: the rows that stored nothing write their null entry
+            if (outer) {   // (uniform)
+#pragma unroll
+                for (int i = 0; i < SI; ++i)
+                    if (((sok & ~hit) >> i) & 1u)
+                        if (pos[i] < cap) st_s<kNtLookupSt>(orr + pos[i], (PT)null_pay);
+            }
+        }
+    }
+}
+
 // --------------------------------------------------------------- group join
 // Join, then aggregate per build row (radix_group): for each R row the count,
 // the wrapping sum and the signed extremes of the payloads of the S rows with
@@ -4670,6 +4846,50 @@ hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, con
     else
         hipLaunchKernelGGL((k_join_lookup<false, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, a,
                            cnt, (u64)null_pay, rows);
+    return hipGetLastError();
+}
+
+// The expand probe: ONE work map (radix_lookup's) under both of its join
+// launches -- k_join_lookup with the count column alone, then, behind the scan
+// of those counts, k_join_expand over the same items and descriptors.  The
+// lookup adds its hits into out.counter (zeroed by the map); the scan's last
+// launch then stores M there.
+hipError_t radix_expand(bool wide, bool outer, unsigned long long null_pay, long long n, const RadixPlan &pl,
+                        const RadixWork &ws, const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt,
+                        long long *off, unsigned long long *sums, hipStream_t st) {
+    static_assert(kExpandNT * kExpandSI == kLookupNT * kLookupSI, "the fill's items are the count stage's");
+    const int P = 1 << pl.total_bits;
+    const unsigned pg = (unsigned)cu_count();
+    WorkMapSpec m;
+    m.subb = (unsigned)((kLookupNT * kLookupSI) >> kRunLog);
+    m.grid = pg;
+    m.r_gates = false;
+    m.counter = out.counter;
+    const WorkMap w = work_map(pl, P, ws, r, &s, m, st);
+    if (!w.items) return hipErrorInvalidValue;
+    JoinArgs a = join_args(wide, pl, r, s, P, ws, out, nullptr, nullptr);
+    a.tshift = 64 - pl.skip - pl.total_bits - kExistsTableLog;
+    const unsigned grid = w.items < pg ? w.items : pg;
+    const u64 rows = (u64)(n > 0 ? n : 0);
+    JoinArgs c = a;
+    c.out_r = nullptr;   // the count column alone
+    if (wide)
+        hipLaunchKernelGGL((k_join_lookup<true, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, c,
+                           cnt, 0ull, rows);
+    else
+        hipLaunchKernelGGL((k_join_lookup<false, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, c,
+                           cnt, 0ull, rows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = launch_expand_scan(cnt, n, outer, sums, off, out.counter, st);
+    if (e != hipSuccess || out.cap <= 0) return e;
+    const unsigned o = outer ? 1u : 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_join_expand<true, kExpandNT, kExpandSI, kExpandWPS>), dim3(grid), dim3(kExpandNT), 0, st, a,
+                           (const long long *)off, (u64)null_pay, o, rows);
+    else
+        hipLaunchKernelGGL((k_join_expand<false, kExpandNT, kExpandSI, kExpandWPS>), dim3(grid), dim3(kExpandNT), 0, st,
+                           a, (const long long *)off, (u64)null_pay, o, rows);
     return hipGetLastError();
 }
 

@@ -30,6 +30,13 @@ HJ_JOIN_KERNEL_EXISTS = 6
 HJ_JOIN_KERNEL_LOOKUP = 7
 HJ_JOIN_KERNEL_GROUP = 8
 HJ_JOIN_KERNEL_AGGREGATE = 9
+HJ_JOIN_KERNEL_EXPAND = 10
+HJ_EXPAND_INNER = 0
+HJ_EXPAND_OUTER = 1
+# the expand probe's scan (hj_kernels.hip: kExpandTile counts per tile, kExpandFan tile sums per step of
+# the one workgroup that scans them) -- the sizes at which its paths change, for the tests
+EXPAND_SCAN_TILE = 2048
+EXPAND_SCAN_FAN = 1024
 HJ_GROUP_MATCHED = 0
 HJ_GROUP_ALL = 1
 HJ_OUTER_BUILD = 1
@@ -92,6 +99,9 @@ def _load():
         "hj_dev_exists_i32": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_lookup_i64": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
         "hj_dev_lookup_i32": (_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp, _vp]),
+        "hj_dev_expand_i64": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_expand_i32": (_int, [_vp, _int, _vp, _i64, C.c_int32, _vp, _vp, _i64, _vp, _vp]),
+        "hj_ctx_reserve_expand": (_int, [_vp, _i64, _int]),
         "hj_dev_group_i64": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_group_tuples_i64": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_group_i32": (_int, [_vp, _int, _vp, _i64, _i64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),

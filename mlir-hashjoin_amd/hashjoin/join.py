@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from ._lib import (HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
+from ._lib import (HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
                    HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, check, lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
@@ -29,6 +29,7 @@ EXISTS_KINDS = {"semi": HJ_EXISTS_SEMI, "anti": HJ_EXISTS_ANTI}
 FULL_KINDS = {"build": HJ_OUTER_BUILD, "full": HJ_OUTER_FULL}
 GROUP_KINDS = {"matched": HJ_GROUP_MATCHED, "all": HJ_GROUP_ALL}
 GROUP_AGGS = ("count", "sum", "min", "max")
+EXPAND_KINDS = {"inner": HJ_EXPAND_INNER, "outer": HJ_EXPAND_OUTER}
 
 
 def _ptr(t):
@@ -130,7 +131,8 @@ class HashJoin:
         return bool(r)
 
     JOIN_KERNELS = {1: "k_join_b", 2: "k_join_u", 3: "k_join_u_stream", 4: "k_join_grp", 5: "k_join",
-                    6: "k_join_exists", 7: "k_join_lookup", 8: "k_join_group", 9: "aggregate"}
+                    6: "k_join_exists", 7: "k_join_lookup", 8: "k_join_group", 9: "aggregate",
+                    10: "k_join_expand"}
 
     @property
     def join_kernel(self):
@@ -138,7 +140,7 @@ class HashJoin:
         'k_join_u_stream', 'k_join_grp', 'k_join', 'k_join_exists' (a radix
         semi- / anti-join), 'k_join_lookup' (a radix lookup), 'k_join_group' (a
         radix group probe), 'aggregate' (a radix hash aggregate: k_join_aggregate),
-        or None (no radix join)."""
+        'k_join_expand' (a radix expand), or None (no radix join)."""
         r = lib.hj_ctx_join_kernel(self._ctx)
         if r < 0:
             check(r, "hj_ctx_join_kernel")
@@ -361,6 +363,75 @@ class HashJoin:
         if m < 0:   # bit 63 (hj.h)
             raise RuntimeError("hash join: internal work list overflow (count flagged)")
         return (out_r, out_cnt) if with_counts else out_r
+
+    # ---- expand probe (hj.h "Expand probe"): all partners per probe row, as a CSR in input order
+    def reserve_expand(self, num_tuples, key_bits=64):
+        """Size the expand probe's count column and scan sums for probe sides of
+        up to num_tuples rows (hj_ctx_reserve_expand), so probe_expand allocates nothing."""
+        check(lib.hj_ctx_reserve_expand(self._ctx, int(num_tuples), int(key_bits)), "hj_ctx_reserve_expand")
+
+    def probe_expand(self, skey, out_off, out_r=None, how="inner", null=-1, count=None, stream=None):
+        """Every partner of every probe row, in input order: out_off (int64, at
+        least len(skey) + 1 long; exactly that many are written) receives the
+        segment starts and M, out_r[out_off[j] : out_off[j + 1]] the R payloads
+        (i32: R row ids) of the R rows with key skey[j], in unspecified order
+        inside the segment; how='outer' gives a row without a partner the one
+        entry `null`.  Entries at or past len(out_r) are dropped; out_r None is
+        the count form.  `count` (int64 device tensor) receives M.  Returns count."""
+        _need_cuda(skey, out_off, out_r)
+        st = _stream(self.device, stream)
+        count = self._count if count is None else count
+        n = skey.numel()
+        if skey.dtype not in (torch.int64, torch.int32):
+            raise TypeError("keys must be int32 or int64")
+        if out_off is None or out_off.dtype != torch.int64 or out_off.numel() < n + 1:
+            raise ValueError("out_off is an int64 column of at least len(skey) + 1 elements")
+        if out_r is not None and out_r.dtype != skey.dtype:
+            raise ValueError("out_r carries the probe key's dtype")
+        cap = 0 if out_r is None else out_r.numel()
+        f, name = ((lib.hj_dev_expand_i64, "hj_dev_expand_i64") if skey.dtype == torch.int64
+                   else (lib.hj_dev_expand_i32, "hj_dev_expand_i32"))
+        check(f(self._ctx, EXPAND_KINDS[how], _ptr(skey), n, int(null), _ptr(out_off), _ptr(out_r) if cap else None,
+                cap, _ptr(count), st), name)
+        return count
+
+    def count_expand(self, skey, how="inner", stream=None):
+        """The count form: (offsets, M) of probe_expand, nothing else written."""
+        off = torch.empty(skey.numel() + 1, dtype=torch.int64, device=self.device)
+        m = int(self.probe_expand(skey, off, None, how=how, stream=stream).item())
+        if m < 0:   # bit 63 (hj.h)
+            raise RuntimeError("hash join: internal work list overflow (count flagged)")
+        return off, m
+
+    def expand(self, rkey, rpay, skey, how="inner", null=-1, stream=None):
+        """Build R, then probe_expand sized exactly: (offsets, out_r), a CSR over
+        S's rows in input order.  int64 keys with rpay None: the payload is R's
+        row index; int32 keys always carry R's row ids."""
+        self.probe_hint(skey.numel())
+        try:
+            if rkey.dtype == torch.int64 and rpay is None:
+                rpay = torch.arange(rkey.numel(), dtype=torch.int64, device=self.device)
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+        off, m = self.count_expand(skey, how=how, stream=stream)
+        out_r = torch.empty(m, dtype=skey.dtype, device=self.device)
+        if m:
+            self.probe_expand(skey, off, out_r, how=how, null=null, stream=stream)
+        return off, out_r
+
+    def ordered_join(self, rkey, rpay, skey, spay=None, how="inner", null=-1, stream=None):
+        """The pandas-order merge: (out_r, out_s) with the pairs in S's order --
+        how='inner' | 'left' ('left' keeps the S rows without a partner, with
+        `null` as their R payload).  out_s repeats spay (the row index when
+        None) over the segment lengths."""
+        if how not in ("inner", "left"):
+            raise ValueError("how must be 'inner' or 'left'")
+        off, out_r = self.expand(rkey, rpay, skey, how="outer" if how == "left" else "inner", null=null,
+                                 stream=stream)
+        src = torch.arange(skey.numel(), dtype=torch.int64, device=self.device) if spay is None else spay
+        out_s = torch.repeat_interleave(src, off[1:] - off[:-1], output_size=out_r.numel())
+        return out_r, out_s
 
     # ---- group probe (hj.h "Group probe"): join, then aggregate per build row
     def _group_outputs(self, dt, out_r, out_cnt, out_sum, out_min, out_max):

@@ -4,6 +4,20 @@ line per case (HIP-event timing on the current stream, median of 10 after 2
 warm-ups); algorithmic bytes as stated in DESIGN.md.
 
 usage: python tools/bench_ops.py  [> profiles/r01_ops_bench.jsonl]
+       python tools/bench_ops.py expand [a] [b] [c]  [> profiles/expand_probe.jsonl]
+
+The `expand` op ("Expand probe") times hj_dev_expand_* on
+  a: 2^26 x 2^26 int64 PK-FK, hit fraction 1.0, AUTO (radix);
+  b: 2^20 x 2^24 int64 PK-FK on the global table;
+  c: 10M x 10M i32 keys uniform in [1, 100k] (~1e9 entries, ~100 per row)
+against two yardsticks on the same inputs in the same process: the payload-only
+positional lookup (the one-partner floor) and what a caller composes without
+it -- the inner probe with S.pay = the row index, torch.sort on the S column
+and a gather of the R column.  Rounds alternate the variants; median [min,
+max] of the timed rounds in ms, device events (`wall`) and the library's own
+phase events (`partition`, `rest`: RADIX's [4] and [5]).  The count form
+(partition, counts, scan) is timed as a variant of its own, so the fill is
+full - count form.
 """
 import json
 import os
@@ -31,7 +45,84 @@ def timed(fn, reps=10, warm=2):
     return statistics.median(ts)
 
 
+def expand_op(shape, reps, warm):
+    if shape == "a":
+        nr, ns, strategy, wide = 1 << 26, 1 << 26, "auto", True
+    elif shape == "b":
+        nr, ns, strategy, wide = 1 << 20, 1 << 24, "global", True
+    else:
+        nr, ns, strategy, wide = 10_000_000, 10_000_000, "auto", False
+    if wide:
+        rk, rp, sk, _ = hashjoin.gen_pkfk(0x5EED, nr, ns, 1.0)
+    else:
+        rk, rp = hashjoin.gen_uniform_i32(0x5EED, 1, 1, 100_000, nr), None
+        sk = hashjoin.gen_uniform_i32(0x5EED, 2, 1, 100_000, ns)
+    dt = sk.dtype
+    hj = hashjoin.HashJoin(0)
+    hj.set_strategy(strategy)
+    hj.set_timing(True)
+    hj.probe_hint(ns)
+    hj.build_table(rk, rp)
+    build_ms = hj.last_timing()["build"]
+    off, m = hj.count_expand(sk)
+    hj.reserve_expand(ns, 64 if wide else 32)
+    out_r = torch.empty(m, dtype=dt, device="cuda")
+    look_r = torch.empty(ns, dtype=dt, device="cuda")
+    in_r, in_s = torch.empty(m, dtype=dt, device="cuda"), torch.empty(m, dtype=dt, device="cuda")
+    rows = torch.arange(ns, dtype=torch.int64, device="cuda") if wide else None
+    res, keep = {}, {}
+
+    def one(kind):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        if kind == "expand":
+            hj.probe_expand(sk, off, out_r)
+        elif kind == "expand-count-form":
+            hj.probe_expand(sk, off, None)
+        elif kind == "lookup-payload-only":
+            hj.probe_lookup(sk, look_r)
+        else:   # inner probe carrying the row index, sort by it, gather the R column
+            hj.probe_relation(sk, rows, in_r, in_s)
+            order = torch.sort(in_s, stable=False).indices
+            keep["composed"] = in_r[order]
+        e1.record()
+        e1.synchronize()
+        t = hj.last_timing()
+        if kind == "expand":
+            keep["kernel"] = hj.join_kernel
+        return {"wall": e0.elapsed_time(e1), "partition": t["probe_partition"], "rest": t["probe_join"],
+                "probe": t["probe"]}
+
+    kinds = ("expand", "expand-count-form", "lookup-payload-only", "inner+sort+gather")
+    for it in range(warm + reps):
+        for kind in kinds:
+            t = one(kind)
+            if it >= warm:
+                for k, v in t.items():
+                    res.setdefault(kind + ":" + k, []).append(v)
+    # the composition and the expand hold the same partners per probe row (the same array when the build is unique)
+    seg = torch.repeat_interleave(torch.arange(ns, device="cuda"), off[1:] - off[:-1], output_size=m)
+    same = bool(torch.equal(keep["composed"], out_r)) if wide else None
+    sums = bool(torch.equal(torch.zeros(ns, dtype=torch.int64, device="cuda").index_add_(0, seg, out_r.long()),
+                            torch.zeros(ns, dtype=torch.int64, device="cuda").index_add_(
+                                0, seg, keep["composed"].long())))
+    out = {"op": "expand", "shape": shape, "dtype": str(dt).replace("torch.", ""), "strategy": hj.strategy_used,
+           "join_kernel": keep["kernel"], "build_rows": nr, "probe_rows": ns, "entries": m, "reps": reps, "warm": warm,
+           "build_ms": round(build_ms, 3), "equals_composition": same, "segment_sums_equal": sums,
+           "device": torch.cuda.get_device_name(0)}
+    for k, v in res.items():
+        out[k] = {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+    print(json.dumps(out), flush=True)
+    hj.close()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "expand":
+        reps, warm = int(os.environ.get("REPS", "7")), int(os.environ.get("WARM", "2"))
+        for shape in (sys.argv[2:] or ["a", "b", "c"]):
+            expand_op(shape, reps, warm)
+            torch.cuda.empty_cache()
+        return
     hj = hashjoin.HashJoin(0)
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
