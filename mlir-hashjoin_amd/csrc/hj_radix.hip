@@ -3061,37 +3061,202 @@ __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
     }
 }
 
-// --------------------------------------------------------------- exists join
-// Semi- / anti-join over the work items (EXISTS / NOT EXISTS): each S row of
-// the item's chunk is emitted at most once, so the LDS table holds KEYS only
-// and each key once -- one 8-B slot format for both widths (wide: the key,
-// EMPTY = INT64_MIN, a per-table LDS flag says "the rows built hold an
-// INT64_MIN key"; narrow: the zero-extended 32-bit key, EMPTY = all ones).
-// An insert ends at EMPTY or at its own key, so a hot build key takes one
-// slot.  2^13 slots = 64 KiB, two workgroups per CU; a build round takes
-// RCAP = 5120 rows (80 runs; load <= 0.625 however the keys repeat).
-//
-// Items whose build side is one round (every planner-sized partition) build
-// once and probe their sub-chunks against that table.  Larger build sides
-// (forced small radix_bits, a hot key's partition: rounds are cut by rows)
-// run the sub-chunks OUTERMOST: a sub-chunk's rows stay in registers with
-// their matched bits while every round is built and probed, and are emitted
-// after the last round -- exactly once, matched in some round (semi) or in
-// none (anti).  That re-reads R once per sub-chunk; such items are the
-// exception.  An item without build rows (anti's map keeps them) builds
-// nothing: no row of it matches.
-// Emit: ballot compaction per sub-chunk as k_probe_exists, ONE add on the
-// output cursor per sub-chunk, contiguous per-wave runs.  out_r = S keys
-// (optional), out_s = S payloads; cap == 0 counts only.  kind, count-only
-// and the key output are wave-uniform runtime branches.
+// --------------------------------------------------------------- rounded-table kernels: the shared skeleton
+// k_join_exists, k_join_lookup, k_join_expand and k_join_group share one
+// structure over the work items (work_map); each kernel's header says only
+// what is its own.  An item names a partition's TABLE side (JoinArgs' r and
+// r_runs: the rows whose keys go into an LDS table) and a chunk of its EMIT
+// side (s and s_runs: the rows looked up and written out).  Which relation is
+// which is the launcher's choice: radix_group and radix_unmatched_build pass
+// the two bucket sets exchanged.
+//  * The table is 2^TABLE_LOG 8-B key slots, one format for both widths (wide:
+//    the key, EMPTY = INT64_MIN, so INT64_MIN keys live beside the table, in
+//    each kernel's own way; narrow: the zero-extended 32-bit key, EMPTY = all
+//    ones).  What else a slot holds is in arrays of the kernel's, indexed by
+//    the slot and cleared by the kernel between the same two barriers as the
+//    keys.
+//  * The table side is built a ROUND at a time: RCAP = 5/8 of the slots in
+//    rows, whole runs (load <= 0.625 however the keys repeat), RI row slots per
+//    thread.  The emit side is taken in sub-chunks of NT x SI rows that stay in
+//    registers (row slot i of wave w is run i * NW + w of the sub-chunk).
+//  * Items whose table side is one round (every planner-sized partition) build
+//    once and probe their sub-chunks against that table.  Larger table sides
+//    (forced small radix_bits, a hot key's partition: rounds are cut by rows)
+//    run the sub-chunks OUTERMOST: a sub-chunk's rows stay in registers with
+//    their running results while every round is built and probed, and are
+//    emitted after the last round -- exactly once.  That re-reads the table
+//    side once per sub-chunk; such items are the exception.  An item without
+//    table rows builds nothing: no row of it has a partner.
+//  * A probe reads the first slots of all SI rows before it resolves any, then
+//    walks linearly.
+// The loop nest (item, sub-chunk, round) is written out in each kernel; what is
+// inside it comes from here:
+//   RoundShape        the constants and the asserts that tie them      all four
+//   load_run_rows     a sub-chunk's or a round's rows, one per lane    all four
+//   RoundTable::clear        the key slots to EMPTY                    all four
+//   RoundTable::insert_once  CAS to EMPTY or the key itself            exists, lookup, group
+//   RoundTable::probe_first  first slots, INT64_MIN rows set apart     all four
+//   RoundTable::find_key     the walk to EMPTY or the key              exists, lookup, group
+//   compact_emit      ballots, one scan, ONE add on the output cursor  exists, group
+// (k_join_expand claims a slot per ROW and walks to EMPTY: its own two loops.)
+// All are __forceinline__: the tables reach them as pointers, and only inlined
+// do those stay LDS addresses (ds_* accesses and LDS atomics, not flat ones).
 constexpr int kExistsTableLog = 13;
+
+// EXACT_RI: the threads divide a round, every row slot is whole; otherwise RI
+// is rounded up and the last row slot partly used (k_join_group's 2560 rows).
+template <int TABLE_LOG, int NT_, int SI_, bool EXACT_RI>
+struct RoundShape {
+    static constexpr int NT = NT_, SI = SI_;
+    static constexpr int TS = 1 << TABLE_LOG;
+    static constexpr unsigned kMask = TS - 1;
+    static constexpr int RCAP = TS * 5 / 8;                             // table rows per round
+    static constexpr int NW = NT / 64;
+    static constexpr unsigned rb = (unsigned)RCAP >> kRunLog;           // runs per round
+    static constexpr int RI = EXACT_RI ? RCAP / NT : (int)((rb + NW - 1) / NW);   // row slots per thread per round
+    static constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;    // runs per sub-chunk
+    static_assert(!EXACT_RI || RI * NT == RCAP, "a build round must load exactly RCAP rows");
+    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
+};
+
+// What load_run_rows keeps of a row: all of it (NT_LD: a non-temporal load), or
+// its key alone (k_join_exists' build: the key word of a 16-B row, not the row).
+template <bool NT_LD>
+struct WholeRow {
+    template <typename T>
+    __device__ __forceinline__ T operator()(const T *p) const {
+        return ld_s<NT_LD>(p);
+    }
+};
+template <bool WIDE>
+struct KeyWord {
+    __device__ __forceinline__ u64 operator()(const typename Row<WIDE>::T *p) const {
+        if constexpr (WIDE) return *(const u64 *)p;
+        else return *p >> 32;
+    }
+};
+// Runs [lo, hi) of a run list, N row slots per lane: row slot i of wave `wave`
+// is run lo + i * NW + wave, lane `off` takes its row `off` if the run has one
+// (v[i] = none otherwise).  Returns the mask of the row slots that hold a row.
+template <int NW, int N, typename T, typename V, typename KEEP>
+__device__ __forceinline__ unsigned load_run_rows(const T *rows, const u64 *runs, u64 lo, u64 hi, unsigned wave,
+                                                  unsigned off, V (&v)[N], const V &none, KEEP keep) {
+    unsigned ok = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const u64 li = lo + (u64)i * NW + wave;
+        const u64 e = li < hi ? sload(runs + li) : 0ull;
+        v[i] = none;
+        if (off < (unsigned)(e & 127u)) {
+            v[i] = keep(rows + (e >> 7) + off);
+            ok |= 1u << i;
+        }
+    }
+    return ok;
+}
+
+// The key slots of a table of shape SH.  tkey is the kernel's LDS array.
+template <bool WIDE, typename SH>
+struct RoundTable {
+    typedef Row<WIDE> R;
+    static constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    static constexpr unsigned kMask = SH::kMask;
+
+    static __device__ __forceinline__ unsigned slot(u64 key, int tshift) {
+        return (unsigned)(rhash(key) >> tshift) & kMask;
+    }
+    // (between two barriers of the caller's, with the kernel's other arrays)
+    static __device__ __forceinline__ void clear(u64 *tkey) {
+        for (int j = threadIdx.x; j < SH::TS / 2; j += SH::NT)
+            ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+    }
+    // The slot of `key`, claimed if no row of the round had it yet: a hot key
+    // takes one slot.  Not for wide INT64_MIN.
+    static __device__ __forceinline__ unsigned insert_once(u64 *tkey, u64 key, int tshift) {
+        unsigned h = slot(key, tshift);
+        while (true) {   // ends at EMPTY (claimed) or at the key itself
+            const u64 old = atomicCAS(&tkey[h], kEmpty, key);
+            if (old == kEmpty || old == key) break;
+            h = (h + 1) & kMask;
+        }
+        return h;
+    }
+    // First slots hp[] and their words e0[] of the SI rows sv[], read before
+    // any is resolved (EMPTY for a row not in `open`).  Wide INT64_MIN rows
+    // -- the EMPTY word, never in the table -- leave `open`; for those that
+    // were in it null_row(i) is called: what such a row finds beside the
+    // table is the kernel's.
+    template <typename NULLROW>
+    static __device__ __forceinline__ void probe_first(const u64 *tkey, const typename R::T (&sv)[SH::SI], int tshift,
+                                                       unsigned &open, unsigned (&hp)[SH::SI], u64 (&e0)[SH::SI],
+                                                       NULLROW null_row) {
+#pragma unroll
+        for (int i = 0; i < SH::SI; ++i) {
+            const u64 key = R::key(sv[i]);
+            if (WIDE && key == kEmptyKey64) {
+                if ((open >> i) & 1u) null_row(i);
+                open &= ~(1u << i);
+            }
+            hp[i] = slot(key, tshift);
+            e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
+        }
+    }
+    // From slot h holding word e: the walk to EMPTY or to the key.  True, and h
+    // the key's slot, if the round has it.
+    static __device__ __forceinline__ bool find_key(const u64 *tkey, u64 key, unsigned &h, u64 e) {
+        while (e != kEmpty && e != key) {
+            h = (h + 1) & kMask;
+            e = tkey[h];
+        }
+        return e == key;
+    }
+};
+
+// Compaction of a sub-chunk's kept rows (bit i of keep: this lane's row slot
+// i): ballots, an exclusive scan of the SI * NW (row slot, wave) counts by wave
+// 0 and ONE add on the output cursor.  Behind it, kept row slot i of this lane
+// goes to s_base + s_cw[i * NW + wave] + lpre[i].  Two barriers; the caller puts
+// a third behind its stores, before s_cw and s_base are used again.
+template <int SI, int NW>
+__device__ __forceinline__ void compact_emit(unsigned keep, u64 *counter, unsigned *s_cw, u64 &s_base, unsigned wave,
+                                             unsigned off, unsigned (&lpre)[SI]) {
+    static_assert(SI * NW <= 64, "one lane per (row slot, wave) run");
+    const u64 lt = off ? (~0ull >> (64 - off)) : 0ull;
+#pragma unroll
+    for (int i = 0; i < SI; ++i) {
+        const u64 bal = __ballot((keep >> i) & 1u);
+        lpre[i] = (unsigned)__popcll(bal & lt);
+        if (off == 0) s_cw[i * NW + wave] = (unsigned)__popcll(bal);
+    }
+    __syncthreads();
+    if (wave == 0) {   // exclusive scan of the SI * NW runs
+        const unsigned v = off < (unsigned)(SI * NW) ? s_cw[off] : 0u;
+        const unsigned x = wave_incl_add(v);
+        if (off < (unsigned)(SI * NW)) s_cw[off] = x - v;
+        if (off == 63) s_base = x ? atomicAdd(counter, (u64)x) : 0ull;
+    }
+    __syncthreads();
+}
+
+// --------------------------------------------------------------- exists join
+// Semi- / anti-join over the work items (EXISTS / NOT EXISTS): each emit row is
+// written at most once, so a slot is its KEY alone and each key is inserted
+// once.  2^13 slots = 64 KiB, TWO workgroups per CU; a round takes RCAP = 5120
+// rows (80 runs).  A per-table LDS flag says "the round's rows hold an
+// INT64_MIN key" (wide): such an emit row is matched by the flag.  A sub-chunk
+// carries its rows' matched bits across the rounds and emits the rows matched
+// in some round (semi) or in none (anti: its map keeps the items without table
+// rows).
+// Emit: compact_emit per sub-chunk, contiguous per-wave runs.  out_r = emit
+// keys (optional), out_s = emit payloads; cap == 0 counts only.  kind,
+// count-only and the key output are wave-uniform runtime branches.
 // 1024 threads x 5 build keys + 3 probe rows, 8 waves per SIMD: both
 // workgroups a CU's LDS admits are resident (<= 64 VGPRs)
 constexpr int kExistsNT = 1024, kExistsSI = 3, kExistsWPS = 8;
 // NULLV: empty, or one u64 -- the outer join's unmatched-rows stage (an anti
 // probe behind radix_join's pairs: a.counter is NOT zeroed by its work map,
 // so the cursor goes on behind them): out_r receives that null value instead
-// of the S key.  A pack, so the exists instantiations keep their kernel
+// of the emit key.  A pack, so the exists instantiations keep their kernel
 // arguments and their machine code.
 template <bool WIDE, int NT, int SI, int WPS, typename... NULLV>
 __global__ __launch_bounds__(NT, WPS) void k_join_exists(JoinArgs a, unsigned anti, NULLV... null_pay) {
@@ -3099,140 +3264,72 @@ __global__ __launch_bounds__(NT, WPS) void k_join_exists(JoinArgs a, unsigned an
     typedef Row<WIDE> R;
     typedef typename R::T T;
     typedef typename std::conditional<WIDE, u64, unsigned>::type PT;   // output element
-    constexpr int TS = 1 << kExistsTableLog;
-    constexpr unsigned kMask = TS - 1;
-    constexpr int RCAP = TS * 5 / 8;          // build rows per round
-    constexpr int RI = RCAP / NT;             // build rows per thread per round
-    constexpr int NW = NT / 64;
-    constexpr unsigned rb = (unsigned)RCAP >> kRunLog;         // runs per build round
-    constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;  // runs per sub-chunk
-    static_assert(RI * NT == RCAP, "a build round must load exactly RCAP rows");
-    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
-    static_assert(SI * NW <= 64, "one lane per (row slot, wave) run");
-    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
-    __shared__ u64 tkey[TS];
+    typedef RoundShape<kExistsTableLog, NT, SI, true> SH;
+    typedef RoundTable<WIDE, SH> TB;
+    constexpr int NW = SH::NW;
+    __shared__ u64 tkey[SH::TS];
     __shared__ unsigned s_cw[SI * NW];
     __shared__ u64 s_base;
     __shared__ unsigned s_null;
 
     const unsigned total = a.work_start[a.P];
     if (blockIdx.x >= total) return;
-    const T *rrows = (const T *)a.r;
-    const T *srows = (const T *)a.s;
+    const T *trows = (const T *)a.r;   // the table side
+    const T *erows = (const T *)a.s;   // the emit side
     PT *okk = (PT *)a.out_r;
     PT *oss = (PT *)a.out_s;
     const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
     const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
-    const u64 lt = off ? (~0ull >> (64 - off)) : 0ull;
     const unsigned flip = anti ? (1u << SI) - 1u : 0u;
 
     for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
         const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
-        const bool rounds = it.r_hi - it.r_lo > (u64)rb;   // more than one build round
+        const bool rounds = it.r_hi - it.r_lo > (u64)SH::rb;   // more than one build round
         bool built = false;
-        for (u64 sb = it.s_lo; sb < it.s_hi; sb += subb) {
-            const u64 shi = sb + subb < it.s_hi ? sb + subb : it.s_hi;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += SH::subb) {
+            const u64 shi = sb + SH::subb < it.s_hi ? sb + SH::subb : it.s_hi;
             T sv[SI];
-            unsigned sok = 0, found = 0;
-#pragma unroll
-            for (int i = 0; i < SI; ++i) {
-                const u64 li = sb + (u64)i * NW + wave;
-                const u64 e = li < shi ? sload(a.s_runs + li) : 0ull;
-                if (off < (unsigned)(e & 127u)) {
-                    sv[i] = ld_s<kNtJoinLd>(srows + (e >> 7) + off);
-                    sok |= 1u << i;
-                } else {
-                    sv[i] = R::zero();
-                }
-            }
-            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += rb) {
+            const unsigned sok =
+                load_run_rows<NW>(erows, a.s_runs, sb, shi, wave, off, sv, R::zero(), WholeRow<kNtJoinLd>{});
+            unsigned found = 0;
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += SH::rb) {
                 if (rounds || !built) {
                     // ---- build rows of runs [r0, rhi): keys only, each key once
-                    const u64 rhi = r0 + rb < it.r_hi ? r0 + rb : it.r_hi;
-                    u64 bk[RI];
-                    unsigned rok = 0;
-#pragma unroll
-                    for (int i = 0; i < RI; ++i) {
-                        const u64 li = r0 + (u64)i * NW + wave;
-                        const u64 e = li < rhi ? sload(a.r_runs + li) : 0ull;
-                        bk[i] = 0ull;
-                        if (off < (unsigned)(e & 127u)) {
-                            const T *p = rrows + (e >> 7) + off;
-                            if constexpr (WIDE) bk[i] = *(const u64 *)p;   // (the key word of the 16-B row)
-                            else bk[i] = *p >> 32;
-                            rok |= 1u << i;
-                        }
-                    }
+                    const u64 rhi = r0 + SH::rb < it.r_hi ? r0 + SH::rb : it.r_hi;
+                    u64 bk[SH::RI];
+                    const unsigned rok =
+                        load_run_rows<NW>(trows, a.r_runs, r0, rhi, wave, off, bk, 0ull, KeyWord<WIDE>{});
                     __syncthreads();   // the previous table's probes are done
-                    for (int j = threadIdx.x; j < TS / 2; j += NT)
-                        ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+                    TB::clear(tkey);
                     if (threadIdx.x == 0) s_null = 0u;
                     __syncthreads();
                     bool nul = false;
 #pragma unroll
-                    for (int i = 0; i < RI; ++i) {
+                    for (int i = 0; i < SH::RI; ++i) {
                         if (!((rok >> i) & 1u)) continue;
-                        const u64 key = bk[i];
-                        if (WIDE && key == kEmptyKey64) {
-                            nul = true;
-                            continue;
-                        }
-                        unsigned h = (unsigned)(rhash(key) >> a.tshift) & kMask;
-                        while (true) {   // ends at EMPTY (claimed) or at the key itself
-                            const u64 old = atomicCAS(&tkey[h], kEmpty, key);
-                            if (old == kEmpty || old == key) break;
-                            h = (h + 1) & kMask;
-                        }
+                        if (WIDE && bk[i] == kEmptyKey64) nul = true;
+                        else TB::insert_once(tkey, bk[i], a.tshift);
                     }
                     if (nul) s_null = 1u;
                     __syncthreads();
                     built = true;
                 }
-                // ---- probe the rows still unmatched: first slots read before any is resolved
+                // ---- probe the rows still unmatched
                 unsigned hp[SI];
                 u64 e0[SI];
                 unsigned open = sok & ~found;
                 const bool nullr = s_null != 0u;
+                TB::probe_first(tkey, sv, a.tshift, open, hp, e0, [&](int i) {
+                    if (nullr) found |= 1u << i;
+                });
 #pragma unroll
-                for (int i = 0; i < SI; ++i) {
-                    const u64 key = R::key(sv[i]);
-                    if (WIDE && key == kEmptyKey64) {
-                        if (((open >> i) & 1u) && nullr) found |= 1u << i;
-                        open &= ~(1u << i);
-                    }
-                    hp[i] = (unsigned)(rhash(key) >> a.tshift) & kMask;
-                    e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
-                }
-#pragma unroll
-                for (int i = 0; i < SI; ++i) {
-                    if (!((open >> i) & 1u)) continue;
-                    const u64 key = R::key(sv[i]);
-                    unsigned h = hp[i];
-                    u64 e = e0[i];
-                    while (e != kEmpty && e != key) {
-                        h = (h + 1) & kMask;
-                        e = tkey[h];
-                    }
-                    if (e == key) found |= 1u << i;
-                }
+                for (int i = 0; i < SI; ++i)
+                    if (((open >> i) & 1u) && TB::find_key(tkey, R::key(sv[i]), hp[i], e0[i])) found |= 1u << i;
             }
             // ---- emit this sub-chunk's rows
             found = (found ^ flip) & sok;
             unsigned lpre[SI];
-#pragma unroll
-            for (int i = 0; i < SI; ++i) {
-                const u64 bal = __ballot((found >> i) & 1u);
-                lpre[i] = (unsigned)__popcll(bal & lt);
-                if (off == 0) s_cw[i * NW + wave] = (unsigned)__popcll(bal);
-            }
-            __syncthreads();
-            if (wave == 0) {   // exclusive scan of the SI * NW runs
-                const unsigned v = off < (unsigned)(SI * NW) ? s_cw[off] : 0u;
-                const unsigned x = wave_incl_add(v);
-                if (off < (unsigned)(SI * NW)) s_cw[off] = x - v;
-                if (off == 63) s_base = x ? atomicAdd(a.counter, (u64)x) : 0ull;
-            }
-            __syncthreads();
+            compact_emit<SI, NW>(found, a.counter, s_cw, s_base, wave, off, lpre);
 #pragma unroll
             for (int i = 0; i < SI; ++i) {
                 if (!((found >> i) & 1u)) continue;
@@ -3249,13 +3346,10 @@ __global__ __launch_bounds__(NT, WPS) void k_join_exists(JoinArgs a, unsigned an
 }
 
 // --------------------------------------------------------------- lookup join
-// Positional lookup over the work items: for each S row, the smallest (signed)
-// payload and the number of the R rows with its key, stored at the row index
-// the S row carries as its payload (radix_lookup).  k_join_exists' structure
-// -- its work map, its sub-chunks of S rows in registers, its build rounds of
-// RCAP = 5120 rows into 2^13 slots holding each key once, its
-// sub-chunks-outermost path when a partition's build side is more than one
-// round -- with two more words per slot: the running minimum payload (LDS
+// Positional lookup over the work items: for each emit (S) row, the smallest
+// (signed) payload and the number of the table (R) rows with its key, stored at
+// the row index the S row carries as its payload (radix_lookup).  k_join_exists'
+// table shape with two more words per slot: the running minimum payload (LDS
 // atomicMin: 64-bit signed for int64 rows, the 32-bit row id for i32 rows) and
 // the count of the round's rows with that key.  A round holds at most 5120
 // rows, so its counts fit 16 bits: two slots share a 32-bit word and an insert
@@ -3284,17 +3378,10 @@ __global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cn
     typedef typename R::T T;
     typedef typename std::conditional<WIDE, u64, unsigned>::type PT;          // output element, LDS payload word
     typedef typename std::conditional<WIDE, long long, unsigned>::type MT;    // its order (row ids are < 2^31)
-    constexpr int TS = 1 << kExistsTableLog;
-    constexpr unsigned kMask = TS - 1;
-    constexpr int RCAP = TS * 5 / 8;          // build rows per round
-    constexpr int RI = RCAP / NT;             // build rows per thread per round
-    constexpr int NW = NT / 64;
-    constexpr unsigned rb = (unsigned)RCAP >> kRunLog;         // runs per build round
-    constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;  // runs per sub-chunk
-    static_assert(RI * NT == RCAP, "a build round must load exactly RCAP rows");
-    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
-    static_assert(RCAP < 65536, "a round's count of one key must fit 16 bits");
-    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    typedef RoundShape<kExistsTableLog, NT, SI, true> SH;
+    typedef RoundTable<WIDE, SH> TB;
+    constexpr int TS = SH::TS, NW = SH::NW;
+    static_assert(SH::RCAP < 65536, "a round's count of one key must fit 16 bits");
     constexpr MT kMaxPay = WIDE ? (MT)0x7fffffffffffffffll : (MT)0xffffffffu;
     __shared__ u64 tkey[TS];
     __shared__ MT tpay[TS];
@@ -3304,8 +3391,8 @@ __global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cn
 
     const unsigned total = a.work_start[a.P];
     if (blockIdx.x >= total) return;
-    const T *rrows = (const T *)a.r;
-    const T *srows = (const T *)a.s;
+    const T *trows = (const T *)a.r;   // the table side
+    const T *erows = (const T *)a.s;   // the emit side
     PT *orr = (PT *)a.out_r;
     const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
     const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
@@ -3313,46 +3400,29 @@ __global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cn
 
     for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
         const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
-        const bool rounds = it.r_hi - it.r_lo > (u64)rb;   // more than one build round
+        const bool rounds = it.r_hi - it.r_lo > (u64)SH::rb;   // more than one build round
         bool built = false;
-        for (u64 sb = it.s_lo; sb < it.s_hi; sb += subb) {
-            const u64 shi = sb + subb < it.s_hi ? sb + subb : it.s_hi;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += SH::subb) {
+            const u64 shi = sb + SH::subb < it.s_hi ? sb + SH::subb : it.s_hi;
             T sv[SI];
-            unsigned sok = 0;
+            const unsigned sok =
+                load_run_rows<NW>(erows, a.s_runs, sb, shi, wave, off, sv, R::zero(), WholeRow<kNtJoinLd>{});
             unsigned cnt[SI];
             MT best[SI];
 #pragma unroll
             for (int i = 0; i < SI; ++i) {
-                const u64 li = sb + (u64)i * NW + wave;
-                const u64 e = li < shi ? sload(a.s_runs + li) : 0ull;
                 cnt[i] = 0u;
                 best[i] = kMaxPay;
-                if (off < (unsigned)(e & 127u)) {
-                    sv[i] = ld_s<kNtJoinLd>(srows + (e >> 7) + off);
-                    sok |= 1u << i;
-                } else {
-                    sv[i] = R::zero();
-                }
             }
-            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += rb) {
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += SH::rb) {
                 if (rounds || !built) {
                     // ---- build rows of runs [r0, rhi): each key once, with its minimum payload and count
-                    const u64 rhi = r0 + rb < it.r_hi ? r0 + rb : it.r_hi;
-                    T br[RI];
-                    unsigned rok = 0;
-#pragma unroll
-                    for (int i = 0; i < RI; ++i) {
-                        const u64 li = r0 + (u64)i * NW + wave;
-                        const u64 e = li < rhi ? sload(a.r_runs + li) : 0ull;
-                        br[i] = R::zero();
-                        if (off < (unsigned)(e & 127u)) {
-                            br[i] = rrows[(e >> 7) + off];
-                            rok |= 1u << i;
-                        }
-                    }
+                    const u64 rhi = r0 + SH::rb < it.r_hi ? r0 + SH::rb : it.r_hi;
+                    T br[SH::RI];
+                    const unsigned rok =
+                        load_run_rows<NW>(trows, a.r_runs, r0, rhi, wave, off, br, R::zero(), WholeRow<false>{});
                     __syncthreads();   // the previous table's probes are done
-                    for (int j = threadIdx.x; j < TS / 2; j += NT)
-                        ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+                    TB::clear(tkey);
                     for (int j = threadIdx.x; j < TS; j += NT) tpay[j] = kMaxPay;
                     for (int j = threadIdx.x; j < TS / 2; j += NT) tcnt[j] = 0u;
                     if (threadIdx.x == 0) {
@@ -3361,7 +3431,7 @@ __global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cn
                     }
                     __syncthreads();
 #pragma unroll
-                    for (int i = 0; i < RI; ++i) {
+                    for (int i = 0; i < SH::RI; ++i) {
                         if (!((rok >> i) & 1u)) continue;
                         const u64 key = R::key(br[i]);
                         const MT pay = (MT)R::pay(br[i]);
@@ -3370,48 +3440,29 @@ __global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cn
                             atomicMin(&s_nullmin, pay);
                             continue;
                         }
-                        unsigned h = (unsigned)(rhash(key) >> a.tshift) & kMask;
-                        while (true) {   // ends at EMPTY (claimed) or at the key itself
-                            const u64 old = atomicCAS(&tkey[h], kEmpty, key);
-                            if (old == kEmpty || old == key) break;
-                            h = (h + 1) & kMask;
-                        }
+                        const unsigned h = TB::insert_once(tkey, key, a.tshift);
                         atomicMin(&tpay[h], pay);
                         atomicAdd(&tcnt[h >> 1], 1u << ((h & 1u) * 16u));
                     }
                     __syncthreads();
                     built = true;
                 }
-                // ---- probe every row of the sub-chunk: first slots read before any is resolved
+                // ---- probe every row of the sub-chunk
                 unsigned hp[SI];
                 u64 e0[SI];
                 unsigned open = sok;
                 const unsigned nullc = s_nullc;
-#pragma unroll
-                for (int i = 0; i < SI; ++i) {
-                    const u64 key = R::key(sv[i]);
-                    if (WIDE && key == kEmptyKey64) {
-                        if (((open >> i) & 1u) && nullc) {
-                            const MT m = s_nullmin;
-                            cnt[i] += nullc;
-                            best[i] = m < best[i] ? m : best[i];
-                        }
-                        open &= ~(1u << i);
-                    }
-                    hp[i] = (unsigned)(rhash(key) >> a.tshift) & kMask;
-                    e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
-                }
+                TB::probe_first(tkey, sv, a.tshift, open, hp, e0, [&](int i) {
+                    if (!nullc) return;
+                    const MT m = s_nullmin;
+                    cnt[i] += nullc;
+                    best[i] = m < best[i] ? m : best[i];
+                });
 #pragma unroll
                 for (int i = 0; i < SI; ++i) {
                     if (!((open >> i) & 1u)) continue;
-                    const u64 key = R::key(sv[i]);
                     unsigned h = hp[i];
-                    u64 e = e0[i];
-                    while (e != kEmpty && e != key) {
-                        h = (h + 1) & kMask;
-                        e = tkey[h];
-                    }
-                    if (e == key) {
+                    if (TB::find_key(tkey, R::key(sv[i]), h, e0[i])) {
                         const MT m = tpay[h];
                         cnt[i] += (tcnt[h >> 1] >> ((h & 1u) * 16u)) & 0xffffu;
                         best[i] = m < best[i] ? m : best[i];
@@ -3435,14 +3486,11 @@ __global__ __launch_bounds__(NT, WPS) void k_join_lookup(JoinArgs a, int *out_cn
 }
 
 // --------------------------------------------------------------- expand join
-// The expand probe's fill (radix_expand): every partner of an S row, stored at
-// offs[row] + k, row being the index the S row carries as its payload.
-// k_join_lookup's structure -- its work map that keeps the items without build
-// rows, its sub-chunks of S rows in registers, its build rounds of RCAP = 5120
-// rows into 2^13 slots, its sub-chunks-outermost path when a partition's build
-// side is more than one round -- over a table of key and payload words alone
-// in which EVERY build row of the round claims a slot of its own (a CAS of
-// EMPTY only, linear probing past equal keys): no minimum, no count.  int64
+// The expand probe's fill (radix_expand): every partner of an emit (S) row,
+// stored at offs[row] + k, row being the index the S row carries as its
+// payload.  k_join_lookup's table shape and work map over key and payload words
+// alone, in which EVERY build row of the round claims a slot of its own (a CAS
+// of EMPTY only, linear probing past equal keys): no minimum, no count.  int64
 // rows 64 + 64 = 128 KiB, i32 rows 64 + 32 = 96 KiB: one workgroup per CU.
 // A probing lane walks from its key's slot to EMPTY and stores the payload of
 // each equal key at its running position pos[i], which is loaded from offs
@@ -3470,25 +3518,20 @@ __global__ __launch_bounds__(NT, WPS) void k_join_expand(JoinArgs a, const long 
     typedef Row<WIDE> R;
     typedef typename R::T T;
     typedef typename std::conditional<WIDE, u64, unsigned>::type PT;   // output element, LDS payload word
-    constexpr int TS = 1 << kExistsTableLog;
-    constexpr unsigned kMask = TS - 1;
-    constexpr int RCAP = TS * 5 / 8;          // build rows per round
-    constexpr int RI = RCAP / NT;             // build rows per thread per round
-    constexpr int NW = NT / 64;
-    constexpr unsigned rb = (unsigned)RCAP >> kRunLog;         // runs per build round
-    constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;  // runs per sub-chunk
-    static_assert(RI * NT == RCAP, "a build round must load exactly RCAP rows");
-    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
-    static_assert(RCAP < TS, "every row of a round has a slot and the walks end at an EMPTY one");
-    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    typedef RoundShape<kExistsTableLog, NT, SI, true> SH;
+    typedef RoundTable<WIDE, SH> TB;
+    constexpr int TS = SH::TS, NW = SH::NW;
+    constexpr unsigned kMask = SH::kMask;
+    constexpr u64 kEmpty = TB::kEmpty;
+    static_assert(SH::RCAP < TS, "every row of a round has a slot and the walks end at an EMPTY one");
     __shared__ u64 tkey[TS];
     __shared__ PT tpay[TS];
     __shared__ unsigned s_nulln;
 
     const unsigned total = a.work_start[a.P];
     if (blockIdx.x >= total) return;
-    const T *rrows = (const T *)a.r;
-    const T *srows = (const T *)a.s;
+    const T *trows = (const T *)a.r;   // the table side
+    const T *erows = (const T *)a.s;   // the emit side
     PT *orr = (PT *)a.out_r;
     const u64 cap = (u64)a.cap;
     const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
@@ -3497,49 +3540,34 @@ __global__ __launch_bounds__(NT, WPS) void k_join_expand(JoinArgs a, const long 
 
     for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
         const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
-        const bool rounds = it.r_hi - it.r_lo > (u64)rb;   // more than one build round
+        const bool rounds = it.r_hi - it.r_lo > (u64)SH::rb;   // more than one build round
         bool built = false, renull = false;
-        for (u64 sb = it.s_lo; sb < it.s_hi; sb += subb) {
-            const u64 shi = sb + subb < it.s_hi ? sb + subb : it.s_hi;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += SH::subb) {
+            const u64 shi = sb + SH::subb < it.s_hi ? sb + SH::subb : it.s_hi;
             T sv[SI];
+            unsigned sok = load_run_rows<NW>(erows, a.s_runs, sb, shi, wave, off, sv, R::zero(), WholeRow<kNtJoinLd>{});
             u64 pos[SI];
-            unsigned sok = 0, hit = 0;
+            unsigned hit = 0;
 #pragma unroll
             for (int i = 0; i < SI; ++i) {
-                const u64 li = sb + (u64)i * NW + wave;
-                const u64 e = li < shi ? sload(a.s_runs + li) : 0ull;
-                sv[i] = R::zero();
                 pos[i] = 0ull;
-                if (off < (unsigned)(e & 127u)) {
-                    sv[i] = ld_s<kNtJoinLd>(srows + (e >> 7) + off);
-                    const u64 row = R::pay(sv[i]);
-                    if (row < n) {   // (always: the partition wrote row indices below n)
-                        sok |= 1u << i;
-                        pos[i] = (u64)offs[row];
-                    }
-                }
+                if (!((sok >> i) & 1u)) continue;
+                const u64 row = R::pay(sv[i]);
+                if (row < n) pos[i] = (u64)offs[row];   // (always: the partition wrote row indices below n)
+                else sok &= ~(1u << i);
             }
-            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += rb) {
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += SH::rb) {
                 if (rounds || !built || renull) {
                     // ---- build rows of runs [r0, rhi): every row a slot of its own
-                    const u64 rhi = r0 + rb < it.r_hi ? r0 + rb : it.r_hi;
-                    T br[RI];
-                    unsigned rok = 0;
-#pragma unroll
-                    for (int i = 0; i < RI; ++i) {
-                        const u64 li = r0 + (u64)i * NW + wave;
-                        const u64 e = li < rhi ? sload(a.r_runs + li) : 0ull;
-                        br[i] = R::zero();
-                        if (off < (unsigned)(e & 127u)) {
-                            br[i] = rrows[(e >> 7) + off];
-                            rok |= 1u << i;
-                        }
-                    }
+                    const u64 rhi = r0 + SH::rb < it.r_hi ? r0 + SH::rb : it.r_hi;
+                    T br[SH::RI];
+                    const unsigned rok =
+                        load_run_rows<NW>(trows, a.r_runs, r0, rhi, wave, off, br, R::zero(), WholeRow<false>{});
                     __syncthreads();   // the previous table's probes are done
                     if constexpr (WIDE) {
                         // ---- the round's INT64_MIN rows, as a list in tpay, copied out before the table is made
 #pragma unroll
-                        for (int i = 0; i < RI; ++i)
+                        for (int i = 0; i < SH::RI; ++i)
                             if (((rok >> i) & 1u) && R::key(br[i]) == kEmptyKey64)
                                 tpay[atomicAdd(&s_nulln, 1u)] = (PT)R::pay(br[i]);
                         __syncthreads();
@@ -3555,33 +3583,26 @@ __global__ __launch_bounds__(NT, WPS) void k_join_expand(JoinArgs a, const long 
                             }
                         }
                     }
-                    for (int j = threadIdx.x; j < TS / 2; j += NT)
-                        ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+                    TB::clear(tkey);
                     __syncthreads();   // the table is empty, the list has been read
                     if (WIDE && threadIdx.x == 0) s_nulln = 0u;
 #pragma unroll
-                    for (int i = 0; i < RI; ++i) {
+                    for (int i = 0; i < SH::RI; ++i) {
                         if (!((rok >> i) & 1u)) continue;
                         const u64 key = R::key(br[i]);
                         if (WIDE && key == kEmptyKey64) continue;
-                        unsigned h = (unsigned)(rhash(key) >> a.tshift) & kMask;
+                        unsigned h = TB::slot(key, a.tshift);
                         while (atomicCAS(&tkey[h], kEmpty, key) != kEmpty) h = (h + 1) & kMask;
                         tpay[h] = (PT)R::pay(br[i]);
                     }
                     __syncthreads();
                     built = true;
                 }
-                // ---- probe every row of the sub-chunk: first slots read before any is resolved
+                // ---- probe every row of the sub-chunk (its INT64_MIN rows took the list above)
                 unsigned hp[SI];
                 u64 e0[SI];
                 unsigned open = sok;
-#pragma unroll
-                for (int i = 0; i < SI; ++i) {
-                    const u64 key = R::key(sv[i]);
-                    if (WIDE && key == kEmptyKey64) open &= ~(1u << i);
-                    hp[i] = (unsigned)(rhash(key) >> a.tshift) & kMask;
-                    e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
-                }
+                TB::probe_first(tkey, sv, a.tshift, open, hp, e0, [](int) {});
 #pragma unroll
                 for (int i = 0; i < SI; ++i) {
                     if (!((open >> i) & 1u)) continue;
@@ -3613,28 +3634,26 @@ __global__ __launch_bounds__(NT, WPS) void k_join_expand(JoinArgs a, const long 
 // --------------------------------------------------------------- group join
 // Join, then aggregate per build row (radix_group): for each R row the count,
 // the wrapping sum and the signed extremes of the payloads of the S rows with
-// its key.  k_join_lookup's structure with the two bucket sets exchanged, the
-// way radix_unmatched_build exchanges them for k_join_exists: the kernel's "r"
-// side -- the rows whose keys go into the LDS table -- is S's partition, its
-// "s" side -- the rows kept in registers and emitted -- is R's.  An insert ends
-// at EMPTY or at its own key (each S key takes one slot per round), then adds 1
-// to the slot's 16-bit round count (two slots to a word: a round holds at most
-// 2560 rows, no carry reaches the neighbour), adds the payload to the slot's
-// sum and applies atomicMin / atomicMax to its extremes (64-bit signed for
-// int64 rows; 32-bit for i32 rows, whose payloads are row ids below 2^31).
-// Wide INT64_MIN S keys are aggregated in LDS words of their own beside the
-// table.  2^12 slots: 32 (keys) + 32 + 32 + 32 + 8 (counts) = 136 KiB for
-// int64 rows, 32 + 32 + 16 + 16 + 8 = 104 KiB for i32 rows: one 1024-thread
-// workgroup per CU, rounds of RCAP = 2560 rows (40 runs; load <= 0.625).
+// its key.  The launcher exchanges the two bucket sets, the way
+// radix_unmatched_build does for k_join_exists: the TABLE side is S's
+// partition (aggregated per key in LDS), the EMIT side is R's (looked up and
+// written out).  An insert (each S key one slot per round) adds 1 to the slot's
+// 16-bit round count (two slots to a word: a round holds at most 2560 rows, no
+// carry reaches the neighbour), adds the payload to the slot's sum and applies
+// atomicMin / atomicMax to its extremes (64-bit signed for int64 rows; 32-bit
+// for i32 rows, whose payloads are row ids below 2^31).  Wide INT64_MIN S keys
+// are aggregated in LDS words of their own beside the table.  2^12 slots: 32
+// (keys) + 32 + 32 + 32 + 8 (counts) = 136 KiB for int64 rows, 32 + 32 + 16 +
+// 16 + 8 = 104 KiB for i32 rows: one 1024-thread workgroup per CU, rounds of
+// RCAP = 2560 rows (40 runs: the threads do not divide them, so the third row
+// slot of a round is used by half the waves -- RoundShape's EXACT_RI = false).
 // An R lane adds the round's count, sum and extremes of its key to the running
 // ones in its registers (the count 64-bit for int64 rows); after the last
-// round the sub-chunk is compacted as k_join_exists compacts (ballots, one scan,
-// ONE add on the output cursor per sub-chunk): kind MATCHED drops the rows
+// round the sub-chunk goes through compact_emit: kind MATCHED drops the rows
 // whose count is 0, ALL keeps every row (an item without S rows builds nothing
 // and emits empty groups: its map keeps such partitions).  Every column passed
 // is stored under cap per element; a column not passed is not aggregated
 // either.  Kind, cap and the columns are wave-uniform runtime branches.
-// S's partition is read once per R sub-chunk when it is more than one round.
 constexpr int kGroupTableLog = 12;
 constexpr int kGroupNT = 1024, kGroupSI = 3, kGroupWPS = 4;
 struct GroupCols {
@@ -3649,17 +3668,10 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
     typedef typename std::conditional<WIDE, u64, unsigned>::type PT;          // output element (r, cnt, min, max)
     typedef typename std::conditional<WIDE, long long, unsigned>::type MT;    // the extremes' order
     typedef typename std::conditional<WIDE, u64, unsigned>::type CT;          // running count
-    constexpr int TS = 1 << kGroupTableLog;
-    constexpr unsigned kMask = TS - 1;
-    constexpr int RCAP = TS * 5 / 8;          // table rows per round
-    constexpr int NW = NT / 64;
-    constexpr unsigned rb = (unsigned)RCAP >> kRunLog;         // runs per round
-    constexpr int RI = (int)((rb + NW - 1) / NW);              // row slots per thread per round (the last partly used)
-    constexpr unsigned subb = (unsigned)(NT * SI) >> kRunLog;  // runs per sub-chunk
-    static_assert((rb << kRunLog) == RCAP && subb == (unsigned)(SI * NW), "rounds must be whole runs");
-    static_assert(RCAP < 65536, "a round's count of one key must fit 16 bits");
-    static_assert(SI * NW <= 64, "one lane per (row slot, wave) run");
-    constexpr u64 kEmpty = WIDE ? kEmptyKey64 : ~0ull;
+    typedef RoundShape<kGroupTableLog, NT, SI, false> SH;
+    typedef RoundTable<WIDE, SH> TB;
+    constexpr int TS = SH::TS, NW = SH::NW;
+    static_assert(SH::RCAP < 65536, "a round's count of one key must fit 16 bits");
     constexpr MT kMinInit = WIDE ? (MT)0x7fffffffffffffffll : (MT)0xffffffffu;
     constexpr MT kMaxInit = WIDE ? (MT)0x8000000000000000ull : (MT)0u;
     __shared__ u64 tkey[TS];
@@ -3675,8 +3687,8 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
 
     const unsigned total = a.work_start[a.P];
     if (blockIdx.x >= total) return;
-    const T *trows = (const T *)a.r;   // S's partition: aggregated in the table
-    const T *erows = (const T *)a.s;   // R's partition: looked up and emitted
+    const T *trows = (const T *)a.r;   // the table side: S's partition
+    const T *erows = (const T *)a.s;   // the emit side: R's partition
     PT *orr = (PT *)a.out_r;
     PT *ocnt = (PT *)g.cnt;
     u64 *osum = (u64 *)g.sum;
@@ -3685,53 +3697,35 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
     const bool w_sum = osum != nullptr, w_min = omin != nullptr, w_max = omax != nullptr;
     const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
     const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
-    const u64 lt = off ? (~0ull >> (64 - off)) : 0ull;
 
     for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
         const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
-        const bool rounds = it.r_hi - it.r_lo > (u64)rb;   // more than one round of S rows
+        const bool rounds = it.r_hi - it.r_lo > (u64)SH::rb;   // more than one round of S rows
         bool built = false;
-        for (u64 sb = it.s_lo; sb < it.s_hi; sb += subb) {
-            const u64 shi = sb + subb < it.s_hi ? sb + subb : it.s_hi;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += SH::subb) {
+            const u64 shi = sb + SH::subb < it.s_hi ? sb + SH::subb : it.s_hi;
             T sv[SI];
-            unsigned sok = 0;
+            const unsigned sok =
+                load_run_rows<NW>(erows, a.s_runs, sb, shi, wave, off, sv, R::zero(), WholeRow<kNtJoinLd>{});
             CT cnt[SI];
             u64 sum[SI];
             MT lo[SI], hi[SI];
 #pragma unroll
             for (int i = 0; i < SI; ++i) {
-                const u64 li = sb + (u64)i * NW + wave;
-                const u64 e = li < shi ? sload(a.s_runs + li) : 0ull;
                 cnt[i] = 0;
                 sum[i] = 0ull;
                 lo[i] = kMinInit;
                 hi[i] = kMaxInit;
-                if (off < (unsigned)(e & 127u)) {
-                    sv[i] = ld_s<kNtJoinLd>(erows + (e >> 7) + off);
-                    sok |= 1u << i;
-                } else {
-                    sv[i] = R::zero();
-                }
             }
-            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += rb) {
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += SH::rb) {
                 if (rounds || !built) {
                     // ---- aggregate S's rows of runs [r0, rhi): each key once
-                    const u64 rhi = r0 + rb < it.r_hi ? r0 + rb : it.r_hi;
-                    T br[RI];
-                    unsigned rok = 0;
-#pragma unroll
-                    for (int i = 0; i < RI; ++i) {
-                        const u64 li = r0 + (u64)i * NW + wave;
-                        const u64 e = li < rhi ? sload(a.r_runs + li) : 0ull;
-                        br[i] = R::zero();
-                        if (off < (unsigned)(e & 127u)) {
-                            br[i] = trows[(e >> 7) + off];
-                            rok |= 1u << i;
-                        }
-                    }
+                    const u64 rhi = r0 + SH::rb < it.r_hi ? r0 + SH::rb : it.r_hi;
+                    T br[SH::RI];
+                    const unsigned rok =
+                        load_run_rows<NW>(trows, a.r_runs, r0, rhi, wave, off, br, R::zero(), WholeRow<false>{});
                     __syncthreads();   // the previous table's lookups are done
-                    for (int j = threadIdx.x; j < TS / 2; j += NT)
-                        ((ulonglong2 *)tkey)[j] = make_ulonglong2(kEmpty, kEmpty);
+                    TB::clear(tkey);
                     for (int j = threadIdx.x; j < TS / 2; j += NT) tcnt[j] = 0u;
                     if (w_sum)
                         for (int j = threadIdx.x; j < TS; j += NT) tsum[j] = 0ull;
@@ -3747,7 +3741,7 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
                     }
                     __syncthreads();
 #pragma unroll
-                    for (int i = 0; i < RI; ++i) {
+                    for (int i = 0; i < SH::RI; ++i) {
                         if (!((rok >> i) & 1u)) continue;
                         const u64 key = R::key(br[i]);
                         const u64 val = R::pay(br[i]);
@@ -3758,12 +3752,7 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
                             if (w_max) atomicMax(&s_nullmax, (MT)val);
                             continue;
                         }
-                        unsigned h = (unsigned)(rhash(key) >> a.tshift) & kMask;
-                        while (true) {   // ends at EMPTY (claimed) or at the key itself
-                            const u64 old = atomicCAS(&tkey[h], kEmpty, key);
-                            if (old == kEmpty || old == key) break;
-                            h = (h + 1) & kMask;
-                        }
+                        const unsigned h = TB::insert_once(tkey, key, a.tshift);
                         atomicAdd(&tcnt[h >> 1], 1u << ((h & 1u) * 16u));
                         if (w_sum) atomicAdd(&tsum[h], val);
                         if (w_min) atomicMin(&tmin[h], (MT)val);
@@ -3772,43 +3761,29 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
                     __syncthreads();
                     built = true;
                 }
-                // ---- every row of the sub-chunk looks its key up: first slots read before any is resolved
+                // ---- every row of the sub-chunk looks its key up
                 unsigned hp[SI];
                 u64 e0[SI];
                 unsigned open = sok;
                 const unsigned nullc = s_nullc;
-#pragma unroll
-                for (int i = 0; i < SI; ++i) {
-                    const u64 key = R::key(sv[i]);
-                    if (WIDE && key == kEmptyKey64) {
-                        if (((open >> i) & 1u) && nullc) {
-                            cnt[i] += nullc;
-                            if (w_sum) sum[i] += s_nullsum;
-                            if (w_min) {
-                                const MT m = s_nullmin;
-                                lo[i] = m < lo[i] ? m : lo[i];
-                            }
-                            if (w_max) {
-                                const MT m = s_nullmax;
-                                hi[i] = m > hi[i] ? m : hi[i];
-                            }
-                        }
-                        open &= ~(1u << i);
+                TB::probe_first(tkey, sv, a.tshift, open, hp, e0, [&](int i) {
+                    if (!nullc) return;
+                    cnt[i] += nullc;
+                    if (w_sum) sum[i] += s_nullsum;
+                    if (w_min) {
+                        const MT m = s_nullmin;
+                        lo[i] = m < lo[i] ? m : lo[i];
                     }
-                    hp[i] = (unsigned)(rhash(key) >> a.tshift) & kMask;
-                    e0[i] = ((open >> i) & 1u) ? tkey[hp[i]] : kEmpty;
-                }
+                    if (w_max) {
+                        const MT m = s_nullmax;
+                        hi[i] = m > hi[i] ? m : hi[i];
+                    }
+                });
 #pragma unroll
                 for (int i = 0; i < SI; ++i) {
                     if (!((open >> i) & 1u)) continue;
-                    const u64 key = R::key(sv[i]);
                     unsigned h = hp[i];
-                    u64 e = e0[i];
-                    while (e != kEmpty && e != key) {
-                        h = (h + 1) & kMask;
-                        e = tkey[h];
-                    }
-                    if (e == key) {
+                    if (TB::find_key(tkey, R::key(sv[i]), h, e0[i])) {
                         cnt[i] += (tcnt[h >> 1] >> ((h & 1u) * 16u)) & 0xffffu;
                         if (w_sum) sum[i] += tsum[h];
                         if (w_min) {
@@ -3828,20 +3803,7 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
             for (int i = 0; i < SI; ++i)
                 if (((sok >> i) & 1u) && (g.all || cnt[i] != 0)) keep |= 1u << i;
             unsigned lpre[SI];
-#pragma unroll
-            for (int i = 0; i < SI; ++i) {
-                const u64 bal = __ballot((keep >> i) & 1u);
-                lpre[i] = (unsigned)__popcll(bal & lt);
-                if (off == 0) s_cw[i * NW + wave] = (unsigned)__popcll(bal);
-            }
-            __syncthreads();
-            if (wave == 0) {   // exclusive scan of the SI * NW runs
-                const unsigned v = off < (unsigned)(SI * NW) ? s_cw[off] : 0u;
-                const unsigned x = wave_incl_add(v);
-                if (off < (unsigned)(SI * NW)) s_cw[off] = x - v;
-                if (off == 63) s_base = x ? atomicAdd(a.counter, (u64)x) : 0ull;
-            }
-            __syncthreads();
+            compact_emit<SI, NW>(keep, a.counter, s_cw, s_base, wave, off, lpre);
 #pragma unroll
             for (int i = 0; i < SI; ++i) {
                 if (!((keep >> i) & 1u)) continue;
@@ -3884,11 +3846,14 @@ __global__ __launch_bounds__(NT, WPS) void k_join_group(JoinArgs a, GroupCols g)
 //    dropped table was emitted, each key belongs to exactly one leaf, and a
 //    leaf of one key (k = 64) always fits: no row is dropped, no key emitted
 //    twice, bit 63 never set.  The partition is re-read per split.
-//  * The emit.  After the split's last row the occupied slots are compacted as
-//    k_join_exists compacts (ballots, one scan, ONE add on the output cursor
+//  * The emit.  After the split's last row the occupied slots are compacted the
+//    way compact_emit compacts (ballots, one scan, ONE add on the output cursor
 //    per split) and stored under cap per element, non-temporally; cap == 0
 //    adds the claimed-slot count alone.  Wide INT64_MIN keys (the EMPTY word)
-//    use LDS words beside the table and are the row behind the split's others.
+//    use LDS words beside the table and are the row behind the split's others:
+//    the cursor add takes that row with it and the scan's total is kept for
+//    its place, which is why this scan is written out here and is not
+//    compact_emit.
 // kAggTable = 3840 slots (not a power of two: slot = a multiply-shift of the
 // hash bits below the partition bits): 5 x 8 B x 3840 = 150 KiB for int64 rows
 // with the 64-bit count, 105 KiB for i32 rows; a power of two would be 2^12
@@ -4779,40 +4744,79 @@ hipError_t radix_join(bool wide, const RadixPlan &pl, const RadixWork &ws, const
 }
 
 namespace {
+// What the launchers of the kernels over a work map of their own start from:
+// the map m describes, over `emit`'s runs (null: one item per non-empty
+// partition of `table`, radix_detect's map), the kernel's arguments with
+// `table` as their r side and `emit` as their s side, tshift for an LDS table
+// of 2^table_log slots, and the persistent grid: m.grid, or the items if
+// fewer.  grid 0: a plan the joins cannot take (hipErrorInvalidValue).
+struct Stage {
+    JoinArgs a;
+    unsigned grid = 0;
+};
+Stage table_stage(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &table, const BucketSet *emit,
+                  const OutDev &out, const WorkMapSpec &m, int table_log, hipStream_t st) {
+    const int P = 1 << pl.total_bits;
+    Stage g;
+    const WorkMap w = work_map(pl, P, ws, table, emit, m, st);
+    if (!w.items) return g;
+    g.a = join_args(wide, pl, table, emit ? *emit : table, P, ws, out, nullptr, nullptr);
+    g.a.tshift = 64 - pl.skip - pl.total_bits - table_log;
+    g.grid = w.items < m.grid ? w.items : m.grid;
+    return g;
+}
+// f(std::true_type{}) for int64 rows, f(std::false_type{}) for i32 rows
+template <typename F>
+void by_width(bool wide, F f) {
+    if (wide) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // k_join_exists over a work map of its own.  null_pay: the outer join's
 // unmatched-rows stage (radix_unmatched), else the plain semi / anti probe.
 hipError_t exists_stage(bool wide, bool anti, const unsigned long long *null_pay, const RadixPlan &pl,
                         const RadixWork &ws, const BucketSet &r, const BucketSet &s, const OutDev &out, hipStream_t st) {
-    const int P = 1 << pl.total_bits;
-    const unsigned pg = (unsigned)(2 * cu_count());   // two 64-KiB tables per CU
     WorkMapSpec m;
     m.subb = (unsigned)((kExistsNT * kExistsSI) >> kRunLog);
-    m.grid = pg;
+    m.grid = (unsigned)(2 * cu_count());   // two 64-KiB tables per CU
     // semi: partitions without build rows have nothing to emit; anti: those S
     // rows are exactly the ones to emit, so every non-empty S partition is live
     m.r_gates = !anti;
     // the unmatched-rows stage appends behind the pairs: the counter stays
     m.counter = null_pay ? nullptr : out.counter;
-    const WorkMap w = work_map(pl, P, ws, r, &s, m, st);
-    if (!w.items) return hipErrorInvalidValue;
-    JoinArgs a = join_args(wide, pl, r, s, P, ws, out, nullptr, nullptr);
-    a.tshift = 64 - pl.skip - pl.total_bits - kExistsTableLog;
-    const unsigned grid = w.items < pg ? w.items : pg;
+    const Stage g = table_stage(wide, pl, ws, r, &s, out, m, kExistsTableLog, st);
+    if (!g.grid) return hipErrorInvalidValue;
     const unsigned kind = anti ? 1u : 0u;
-    auto launch = [&](auto w_, auto... nullv) {
-        constexpr bool W = decltype(w_)::value;
-        hipLaunchKernelGGL((k_join_exists<W, kExistsNT, kExistsSI, kExistsWPS, decltype(nullv)...>), dim3(grid),
-                           dim3(kExistsNT), 0, st, a, kind, nullv...);
+    auto launch = [&](auto... nullv) {
+        by_width(wide, [&](auto w_) {
+            constexpr bool W = decltype(w_)::value;
+            hipLaunchKernelGGL((k_join_exists<W, kExistsNT, kExistsSI, kExistsWPS, decltype(nullv)...>), dim3(g.grid),
+                               dim3(kExistsNT), 0, st, g.a, kind, nullv...);
+        });
     };
-    if (null_pay) {
-        const u64 nv = *null_pay;
-        if (wide) launch(std::true_type{}, nv);
-        else launch(std::false_type{}, nv);
-    } else {
-        if (wide) launch(std::true_type{});
-        else launch(std::false_type{});
-    }
+    if (null_pay) launch((u64)*null_pay);
+    else launch();
     return hipGetLastError();
+}
+
+void launch_lookup(bool wide, unsigned grid, const JoinArgs &a, int *cnt, u64 null_pay, u64 rows, hipStream_t st) {
+    by_width(wide, [&](auto w_) {
+        hipLaunchKernelGGL((k_join_lookup<decltype(w_)::value, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid),
+                           dim3(kLookupNT), 0, st, a, cnt, null_pay, rows);
+    });
+}
+// radix_lookup's stage (the exists stage's anti work map: the same sub-chunk,
+// so the work area covers it as it covers that stage's): every non-empty S
+// partition is an item, build rows or not.  One workgroup per CU (its table).
+Stage lookup_stage(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
+                   const OutDev &out, hipStream_t st) {
+    static_assert(kLookupNT * kLookupSI == kExistsNT * kExistsSI, "the lookup's items are the exists stage's");
+    WorkMapSpec m;
+    m.subb = (unsigned)((kLookupNT * kLookupSI) >> kRunLog);
+    m.grid = (unsigned)cu_count();
+    m.r_gates = false;
+    m.counter = out.counter;
+    return table_stage(wide, pl, ws, r, &s, out, m, kExistsTableLog, st);
 }
 }  // namespace
 
@@ -4821,31 +4825,11 @@ hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWo
     return exists_stage(wide, anti, nullptr, pl, ws, r, s, out, st);
 }
 
-// k_join_lookup over the exists stage's anti work map (the same sub-chunk, so
-// the work area covers it as it covers that stage's): every non-empty S
-// partition is an item, build rows or not.  One workgroup per CU (its table).
 hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, const RadixPlan &pl, const RadixWork &ws,
                         const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt, hipStream_t st) {
-    static_assert(kLookupNT * kLookupSI == kExistsNT * kExistsSI, "the lookup's items are the exists stage's");
-    const int P = 1 << pl.total_bits;
-    const unsigned pg = (unsigned)cu_count();
-    WorkMapSpec m;
-    m.subb = (unsigned)((kLookupNT * kLookupSI) >> kRunLog);
-    m.grid = pg;
-    m.r_gates = false;
-    m.counter = out.counter;
-    const WorkMap w = work_map(pl, P, ws, r, &s, m, st);
-    if (!w.items) return hipErrorInvalidValue;
-    JoinArgs a = join_args(wide, pl, r, s, P, ws, out, nullptr, nullptr);
-    a.tshift = 64 - pl.skip - pl.total_bits - kExistsTableLog;
-    const unsigned grid = w.items < pg ? w.items : pg;
-    const u64 rows = (u64)(n > 0 ? n : 0);
-    if (wide)
-        hipLaunchKernelGGL((k_join_lookup<true, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, a,
-                           cnt, (u64)null_pay, rows);
-    else
-        hipLaunchKernelGGL((k_join_lookup<false, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, a,
-                           cnt, (u64)null_pay, rows);
+    const Stage g = lookup_stage(wide, pl, ws, r, s, out, st);
+    if (!g.grid) return hipErrorInvalidValue;
+    launch_lookup(wide, g.grid, g.a, cnt, (u64)null_pay, (u64)(n > 0 ? n : 0), st);
     return hipGetLastError();
 }
 
@@ -4858,38 +4842,21 @@ hipError_t radix_expand(bool wide, bool outer, unsigned long long null_pay, long
                         const RadixWork &ws, const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt,
                         long long *off, unsigned long long *sums, hipStream_t st) {
     static_assert(kExpandNT * kExpandSI == kLookupNT * kLookupSI, "the fill's items are the count stage's");
-    const int P = 1 << pl.total_bits;
-    const unsigned pg = (unsigned)cu_count();
-    WorkMapSpec m;
-    m.subb = (unsigned)((kLookupNT * kLookupSI) >> kRunLog);
-    m.grid = pg;
-    m.r_gates = false;
-    m.counter = out.counter;
-    const WorkMap w = work_map(pl, P, ws, r, &s, m, st);
-    if (!w.items) return hipErrorInvalidValue;
-    JoinArgs a = join_args(wide, pl, r, s, P, ws, out, nullptr, nullptr);
-    a.tshift = 64 - pl.skip - pl.total_bits - kExistsTableLog;
-    const unsigned grid = w.items < pg ? w.items : pg;
+    const Stage g = lookup_stage(wide, pl, ws, r, s, out, st);
+    if (!g.grid) return hipErrorInvalidValue;
     const u64 rows = (u64)(n > 0 ? n : 0);
-    JoinArgs c = a;
+    JoinArgs c = g.a;
     c.out_r = nullptr;   // the count column alone
-    if (wide)
-        hipLaunchKernelGGL((k_join_lookup<true, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, c,
-                           cnt, 0ull, rows);
-    else
-        hipLaunchKernelGGL((k_join_lookup<false, kLookupNT, kLookupSI, kLookupWPS>), dim3(grid), dim3(kLookupNT), 0, st, c,
-                           cnt, 0ull, rows);
+    launch_lookup(wide, g.grid, c, cnt, 0ull, rows, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = launch_expand_scan(cnt, n, outer, sums, off, out.counter, st);
     if (e != hipSuccess || out.cap <= 0) return e;
     const unsigned o = outer ? 1u : 0u;
-    if (wide)
-        hipLaunchKernelGGL((k_join_expand<true, kExpandNT, kExpandSI, kExpandWPS>), dim3(grid), dim3(kExpandNT), 0, st, a,
-                           (const long long *)off, (u64)null_pay, o, rows);
-    else
-        hipLaunchKernelGGL((k_join_expand<false, kExpandNT, kExpandSI, kExpandWPS>), dim3(grid), dim3(kExpandNT), 0, st,
-                           a, (const long long *)off, (u64)null_pay, o, rows);
+    by_width(wide, [&](auto w_) {
+        hipLaunchKernelGGL((k_join_expand<decltype(w_)::value, kExpandNT, kExpandSI, kExpandWPS>), dim3(g.grid),
+                           dim3(kExpandNT), 0, st, g.a, (const long long *)off, (u64)null_pay, o, rows);
+    });
     return hipGetLastError();
 }
 
@@ -4901,23 +4868,19 @@ hipError_t radix_expand(bool wide, bool outer, unsigned long long null_pay, long
 // workgroup per CU (its table).
 hipError_t radix_group(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
                        const GroupOut &out, hipStream_t st) {
-    const int P = 1 << pl.total_bits;
-    const unsigned pg = (unsigned)cu_count();
     WorkMapSpec m;
     m.subb = (unsigned)((kGroupNT * kGroupSI) >> kRunLog);
-    m.grid = pg;
+    m.grid = (unsigned)cu_count();
     m.r_gates = !out.all;
     m.counter = out.counter;
-    const WorkMap w = work_map(pl, P, ws, s, &r, m, st);
-    if (!w.items) return hipErrorInvalidValue;
-    JoinArgs a = join_args(wide, pl, s, r, P, ws, OutDev{out.r, nullptr, out.cap, out.counter}, nullptr, nullptr);
-    a.tshift = 64 - pl.skip - pl.total_bits - kGroupTableLog;
-    const GroupCols g{out.cnt, out.sum, out.mn, out.mx, (u64)out.null_val, out.all ? 1u : 0u};
-    const unsigned grid = w.items < pg ? w.items : pg;
-    if (wide)
-        hipLaunchKernelGGL((k_join_group<true, kGroupNT, kGroupSI, kGroupWPS>), dim3(grid), dim3(kGroupNT), 0, st, a, g);
-    else
-        hipLaunchKernelGGL((k_join_group<false, kGroupNT, kGroupSI, kGroupWPS>), dim3(grid), dim3(kGroupNT), 0, st, a, g);
+    const Stage g =
+        table_stage(wide, pl, ws, s, &r, OutDev{out.r, nullptr, out.cap, out.counter}, m, kGroupTableLog, st);
+    if (!g.grid) return hipErrorInvalidValue;
+    const GroupCols c{out.cnt, out.sum, out.mn, out.mx, (u64)out.null_val, out.all ? 1u : 0u};
+    by_width(wide, [&](auto w_) {
+        hipLaunchKernelGGL((k_join_group<decltype(w_)::value, kGroupNT, kGroupSI, kGroupWPS>), dim3(g.grid),
+                           dim3(kGroupNT), 0, st, g.a, c);
+    });
     return hipGetLastError();
 }
 
@@ -4927,18 +4890,16 @@ hipError_t radix_group(bool wide, const RadixPlan &pl, const RadixWork &ws, cons
 // nothing.  One workgroup per CU (its table).
 hipError_t radix_aggregate(bool wide, const RadixPlan &pl, const RadixWork &ws, const BucketSet &s, const GroupOut &out,
                            hipStream_t st) {
-    const int P = 1 << pl.total_bits;
-    const unsigned pg = (unsigned)cu_count();
     WorkMapSpec m;
+    m.grid = (unsigned)cu_count();
     m.counter = out.counter;
-    const WorkMap w = work_map(pl, P, ws, s, nullptr, m, st);
-    if (!w.items) return hipErrorInvalidValue;
-    JoinArgs a = join_args(wide, pl, s, s, P, ws, OutDev{out.r, nullptr, out.cap, out.counter}, nullptr, nullptr);
-    a.tshift = pl.skip + pl.total_bits;   // the hash bits above the LDS slot's (k_join_aggregate shifts them out)
-    const AggCols g{out.r, out.cnt, out.sum, out.mn, out.mx};
-    const unsigned grid = w.items < pg ? w.items : pg;
-    if (wide) hipLaunchKernelGGL((k_join_aggregate<true>), dim3(grid), dim3(kAggNT), 0, st, a, g);
-    else hipLaunchKernelGGL((k_join_aggregate<false>), dim3(grid), dim3(kAggNT), 0, st, a, g);
+    Stage g = table_stage(wide, pl, ws, s, nullptr, OutDev{out.r, nullptr, out.cap, out.counter}, m, 0, st);
+    if (!g.grid) return hipErrorInvalidValue;
+    g.a.tshift = pl.skip + pl.total_bits;   // the hash bits above the LDS slot's (k_join_aggregate shifts them out)
+    const AggCols c{out.r, out.cnt, out.sum, out.mn, out.mx};
+    by_width(wide, [&](auto w_) {
+        hipLaunchKernelGGL((k_join_aggregate<decltype(w_)::value>), dim3(g.grid), dim3(kAggNT), 0, st, g.a, c);
+    });
     return hipGetLastError();
 }
 

@@ -30,3 +30,13 @@ def test_exists_round_must_load_every_row(tmp_path):
     good = _instantiate(tmp_path, "template __global__ void k_join_exists<false, kExistsNT, kExistsSI, kExistsWPS>"
                                   "(JoinArgs, unsigned);")
     assert good.returncode == 0, good.stderr[-2000:]
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_lookup_round_must_load_every_row(tmp_path):
+    """The same bad shape for k_join_lookup: the assert is the shared round
+    shape's, so every kernel built on it refuses 768 threads."""
+    bad = _instantiate(tmp_path, "template __global__ void k_join_lookup<true, 768, 3, 6>"
+                                 "(JoinArgs, int *, unsigned long long, unsigned long long);")
+    assert bad.returncode != 0
+    assert "a build round must load exactly RCAP rows" in bad.stderr
