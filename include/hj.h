@@ -54,6 +54,7 @@ extern "C" {
 #define HJ_ERR_NOMEM (-3)    /* device or host allocation failed */
 #define HJ_ERR_STATE (-4)    /* call order: probe before build, wrong layout */
 #define HJ_ERR_CAPACITY (-5) /* output memref smaller than the join result */
+#define HJ_ERR_RANGE (-6)        /* the columns' joint range needs more than 64 bits */
 
 typedef struct hj_ctx hj_ctx;
 
@@ -580,6 +581,85 @@ int hj_dev_probe_full_tuples_i64(hj_ctx *ctx, int kind, const int64_t *tuples, i
 int hj_dev_probe_full_i32(hj_ctx *ctx, int kind, const int32_t *skey, int64_t n, int64_t row_base, int32_t null_row_r,
                           int32_t null_row_s, int32_t *out_r, int32_t *out_s, int64_t out_cap, uint64_t *d_count,
                           void *stream);
+
+/* ---------------------------------------------------------- Composite keys
+ * Exact range packing of up to four key columns into ONE int64 key, so that
+ * `ON a.x = b.x AND a.y = b.y` and `GROUP BY a, b` run through every entry
+ * point above unchanged.  A key codec is an object of its own, independent of
+ * hj_ctx; it owns one small device block (a few hundred bytes) holding the
+ * plan.  Columns are signed int32 or int64 (col_bits[c] = 32 | 64), ncols is
+ * 1 .. HJ_KEYS_MAX_COLS.
+ *
+ * Call order: reset -> observe (once per relation that will be packed) ->
+ * seal -> pack / unpack.  A freshly created codec is in the reset state.
+ *   reset    forgets every observation, the seal and the out-of-range count (a
+ *            kernel, not a memset).
+ *   observe  folds the n rows of the given columns into the per-column signed
+ *            minimum lo[c] and maximum hi[c] (int32 columns sign-extended) and
+ *            adds n to rows_observed.  Any number of calls; n == 0 reads
+ *            nothing and accepts null column pointers (and a null cols).
+ *   seal     one tiny kernel computes the plan on the device:
+ *              span    = (uint64)hi[c] - (uint64)lo[c]
+ *              bits[c] = 0 if span == 0, else 64 - clz(span)
+ *              shift[c] = bits[c+1] + ... + bits[ncols-1]   (column 0 is the highest field)
+ *              total   = the sum of bits[c]; total > 64 sets the range flag.
+ *            With no row observed at all every width is 0 and lo = hi = 0.
+ *            Sealing a sealed codec recomputes the same plan.
+ *   pack     key = OR over the columns with bits[c] > 0 of
+ *                  ((uint64)(v[c] - lo[c]) << shift[c]).
+ *            A 0-bit column contributes nothing and is never shifted: the pair
+ *            (constant, full-range int64) gives bits = {0, 64}, shift = {64, 0},
+ *            and two full-range int32 columns give bits = {32, 32}; both total
+ *            exactly 64 and both are legal.
+ *              - pack is injective on the observed box [lo, hi];
+ *              - the UNSIGNED order of the packed keys equals the lexicographic
+ *                order of the column tuples;
+ *              - any 64-bit pattern can occur, the INT64_MIN word included --
+ *                the joins and the aggregate treat that word as an ordinary key.
+ *            Exactly n words are written (pack_tuples: 2n, the 16-B rows
+ *            {key, pay[row]} of the hj_dev_*_tuples_i64 entry points) and
+ *            nothing past them.
+ *   unpack   the exact inverse on the observed box: out_cols[c][row] =
+ *            lo[c] + ((key >> shift[c]) & (2^bits[c] - 1)), int32 columns
+ *            written as int32; a NULL entry of out_cols is skipped.
+ * Values outside the sealed range (a relation that was not observed is
+ * packed): a row with some v[c] outside [lo[c], hi[c]] is counted in
+ * rows_out_of_range and its key is unspecified; the call stays memory-safe
+ * and every other row's key is exact.
+ * Range flag set (total > 64): pack and unpack launch and write nothing (they
+ * read the flag on the device), and hj_keycodec_info returns HJ_ERR_RANGE with
+ * the widths filled in, so the caller sees which column is to blame.  The
+ * joint range is never joined approximately; there is no hash-and-verify
+ * fallback.
+ * Errors, in this order: a null codec; a bad column set (null cols, or a null
+ * column with n > 0), a null output, n < 0 -- each HJ_ERR_ARG with the message
+ * in hj_last_error; then the call order, tracked on the host (it is call
+ * order, not data): observe after a seal and before a reset, and pack or
+ * unpack before a seal, are HJ_ERR_STATE.  hj_keycodec_create checks ncols and
+ * col_bits BEFORE it touches a device and returns NULL with a message.
+ * Every hj_dev_keycodec_* call is asynchronous on the stream (NULL = default
+ * stream), launches kernels only, allocates nothing and never synchronises.
+ * Column pointers travel by value in the kernel arguments; the plan is read
+ * from the device block.  The sequence reset, observe, observe, seal, pack,
+ * pack is capturable as a LINEAR graph and, replayed over new data in the
+ * same buffers, yields the new data's plan and keys.
+ * hj_keycodec_info synchronises the device and reads the sealed plan back
+ * (HJ_ERR_STATE before a seal): the sum of the widths, per column the width
+ * and the observed [lo, hi], the rows observed and the rows packed out of
+ * range since the reset; entries past ncols are 0; any pointer may be NULL. */
+#define HJ_KEYS_MAX_COLS 4
+typedef struct hj_keycodec hj_keycodec;
+hj_keycodec *hj_keycodec_create(int device, int ncols, const int col_bits[]);
+void hj_keycodec_destroy(hj_keycodec *kc);
+int hj_dev_keycodec_reset(hj_keycodec *kc, void *stream);
+int hj_dev_keycodec_observe(hj_keycodec *kc, const void *const cols[], int64_t n, void *stream);
+int hj_dev_keycodec_seal(hj_keycodec *kc, void *stream);
+int hj_dev_keycodec_pack(hj_keycodec *kc, const void *const cols[], int64_t n, int64_t *out_key, void *stream);
+int hj_dev_keycodec_pack_tuples(hj_keycodec *kc, const void *const cols[], const int64_t *pay, int64_t n,
+                                int64_t *out_tuples, void *stream);
+int hj_dev_keycodec_unpack(hj_keycodec *kc, const int64_t *key, int64_t n, void *const out_cols[], void *stream);
+int hj_keycodec_info(hj_keycodec *kc, int *total_bits, int bits[4], int64_t lo[4], int64_t hi[4],
+                     uint64_t *rows_observed, uint64_t *rows_out_of_range);
 
 /* Radix partition of rows into nparts (1..8192) groups by a key hash independent of
  * the table's slot hash: out_tuples (2*n int64) receives packed {key, pay}

@@ -2582,6 +2582,183 @@ void hj_free_result(void *allocated) { std::free(allocated); }
 
 }  // extern "C"
 
+// --------------------------------------------------------- composite keys
+// A key codec: the column set and, on the device, the plan block every
+// hj_keys.hip kernel reads.  The host keeps only the call order (sealed or
+// not); what was observed lives on the device alone.
+struct hj_keycodec {
+    int device = 0;
+    int ncols = 0;
+    unsigned w64 = 0;            // bit c: column c is int64
+    hj::KeyPlan *plan = nullptr; // device
+    bool sealed = false;
+};
+
+namespace {
+
+int keys_cols(const hj_keycodec *kc, const void *const cols[], int64_t n, hj::KeyCols *out) {
+    if (n < 0) HJ_FAIL(HJ_ERR_ARG, "negative row count");
+    for (int c = 0; c < hj::kKeysMaxCols; ++c) out->p[c] = nullptr;
+    if (n == 0) return HJ_OK;
+    if (!cols) HJ_FAIL(HJ_ERR_ARG, "bad column set: null column array");
+    for (int c = 0; c < kc->ncols; ++c) {
+        if (!cols[c]) HJ_FAIL(HJ_ERR_ARG, "bad column set: null column");
+        out->p[c] = cols[c];
+    }
+    return HJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+hj_keycodec *hj_keycodec_create(int device, int ncols, const int col_bits[]) {
+    // the arguments first, before anything touches a device
+    if (ncols < 1 || ncols > HJ_KEYS_MAX_COLS) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "key codec: ncols must be 1.." + std::to_string(HJ_KEYS_MAX_COLS));
+        return nullptr;
+    }
+    if (!col_bits) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "key codec: null col_bits");
+        return nullptr;
+    }
+    unsigned w64 = 0;
+    for (int c = 0; c < ncols; ++c) {
+        if (col_bits[c] != 32 && col_bits[c] != 64) {
+            fail(HJ_ERR_ARG, __FILE__, __LINE__, "key codec: col_bits must be 32 or 64");
+            return nullptr;
+        }
+        w64 |= (col_bits[c] == 64 ? 1u : 0u) << c;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        fail(HJ_ERR_HIP, __FILE__, __LINE__, "no HIP device visible");
+        return nullptr;
+    }
+    if (device < 0 || device >= n) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "device index out of range");
+        return nullptr;
+    }
+    hj_keycodec *kc = new hj_keycodec();
+    kc->device = device;
+    kc->ncols = ncols;
+    kc->w64 = w64;
+    // the reset state, written by the reset kernel and waited for here: the
+    // first call may come on any stream
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void **)&kc->plan, sizeof(hj::KeyPlan));
+    if (e == hipSuccess) e = hj::keys_reset(kc->plan, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        fail(e == hipErrorOutOfMemory ? HJ_ERR_NOMEM : HJ_ERR_HIP, __FILE__, __LINE__,
+             std::string("key codec: ") + hipGetErrorString(e));
+        if (kc->plan) (void)hipFree(kc->plan);
+        delete kc;
+        return nullptr;
+    }
+    return kc;
+}
+
+void hj_keycodec_destroy(hj_keycodec *kc) {
+    if (!kc) return;
+    (void)hipSetDevice(kc->device);
+    (void)hipDeviceSynchronize();
+    if (kc->plan) (void)hipFree(kc->plan);
+    delete kc;
+}
+
+int hj_dev_keycodec_reset(hj_keycodec *kc, void *stream) {
+    if (!kc) HJ_FAIL(HJ_ERR_ARG, "null codec");
+    HJ_HIP(hipSetDevice(kc->device));
+    HJ_HIP(hj::keys_reset(kc->plan, (hipStream_t)stream));
+    kc->sealed = false;
+    return HJ_OK;
+}
+
+int hj_dev_keycodec_observe(hj_keycodec *kc, const void *const cols[], int64_t n, void *stream) {
+    if (!kc) HJ_FAIL(HJ_ERR_ARG, "null codec");
+    hj::KeyCols kcols;
+    HJ_TRY(keys_cols(kc, cols, n, &kcols));
+    if (kc->sealed) HJ_FAIL(HJ_ERR_STATE, "key codec: observe after seal (reset first)");
+    HJ_HIP(hipSetDevice(kc->device));
+    HJ_HIP(hj::keys_observe(kc->plan, kc->ncols, kc->w64, kcols, n, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+int hj_dev_keycodec_seal(hj_keycodec *kc, void *stream) {
+    if (!kc) HJ_FAIL(HJ_ERR_ARG, "null codec");
+    HJ_HIP(hipSetDevice(kc->device));
+    HJ_HIP(hj::keys_seal(kc->plan, kc->ncols, (hipStream_t)stream));
+    kc->sealed = true;
+    return HJ_OK;
+}
+
+int hj_dev_keycodec_pack(hj_keycodec *kc, const void *const cols[], int64_t n, int64_t *out_key, void *stream) {
+    if (!kc) HJ_FAIL(HJ_ERR_ARG, "null codec");
+    hj::KeyCols kcols;
+    HJ_TRY(keys_cols(kc, cols, n, &kcols));
+    if (n > 0 && !out_key) HJ_FAIL(HJ_ERR_ARG, "null output");
+    if (!kc->sealed) HJ_FAIL(HJ_ERR_STATE, "key codec: pack before seal");
+    HJ_HIP(hipSetDevice(kc->device));
+    HJ_HIP(hj::keys_pack(kc->plan, kc->ncols, kc->w64, kcols, nullptr, n, (unsigned long long *)out_key, false,
+                         (hipStream_t)stream));
+    return HJ_OK;
+}
+
+int hj_dev_keycodec_pack_tuples(hj_keycodec *kc, const void *const cols[], const int64_t *pay, int64_t n,
+                                int64_t *out_tuples, void *stream) {
+    if (!kc) HJ_FAIL(HJ_ERR_ARG, "null codec");
+    hj::KeyCols kcols;
+    HJ_TRY(keys_cols(kc, cols, n, &kcols));
+    if (n > 0 && !pay) HJ_FAIL(HJ_ERR_ARG, "bad column set: null payload column");
+    if (n > 0 && !out_tuples) HJ_FAIL(HJ_ERR_ARG, "null output");
+    if (!kc->sealed) HJ_FAIL(HJ_ERR_STATE, "key codec: pack before seal");
+    HJ_HIP(hipSetDevice(kc->device));
+    HJ_HIP(hj::keys_pack(kc->plan, kc->ncols, kc->w64, kcols, (const long long *)pay, n,
+                         (unsigned long long *)out_tuples, true, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+int hj_dev_keycodec_unpack(hj_keycodec *kc, const int64_t *key, int64_t n, void *const out_cols[], void *stream) {
+    if (!kc) HJ_FAIL(HJ_ERR_ARG, "null codec");
+    if (n < 0) HJ_FAIL(HJ_ERR_ARG, "negative row count");
+    if (n > 0 && !key) HJ_FAIL(HJ_ERR_ARG, "bad column set: null key column");
+    if (n > 0 && !out_cols) HJ_FAIL(HJ_ERR_ARG, "null output");
+    if (!kc->sealed) HJ_FAIL(HJ_ERR_STATE, "key codec: unpack before seal");
+    hj::KeyOutCols o;
+    for (int c = 0; c < hj::kKeysMaxCols; ++c) o.p[c] = n > 0 && c < kc->ncols ? out_cols[c] : nullptr;
+    HJ_HIP(hipSetDevice(kc->device));
+    HJ_HIP(hj::keys_unpack(kc->plan, kc->ncols, kc->w64, (const unsigned long long *)key, n, o, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+int hj_keycodec_info(hj_keycodec *kc, int *total_bits, int bits[4], int64_t lo[4], int64_t hi[4],
+                     uint64_t *rows_observed, uint64_t *rows_out_of_range) {
+    if (!kc) HJ_FAIL(HJ_ERR_ARG, "null codec");
+    if (!kc->sealed) HJ_FAIL(HJ_ERR_STATE, "key codec: info before seal");
+    hj::KeyPlan p;
+    HJ_HIP(hipSetDevice(kc->device));
+    HJ_HIP(hipDeviceSynchronize());
+    HJ_HIP(hipMemcpy(&p, kc->plan, sizeof(p), hipMemcpyDeviceToHost));
+    if (total_bits) *total_bits = p.total;
+    for (int c = 0; c < hj::kKeysMaxCols; ++c) {
+        if (bits) bits[c] = p.bits[c];
+        if (lo) lo[c] = p.lo[c];
+        if (hi) hi[c] = p.hi[c];
+    }
+    if (rows_observed) *rows_observed = p.rows;
+    if (rows_out_of_range) *rows_out_of_range = p.oor;
+    if (p.range) {
+        std::string w;
+        for (int c = 0; c < kc->ncols; ++c) w += (c ? " + " : "") + std::to_string(p.bits[c]);
+        HJ_FAIL(HJ_ERR_RANGE, "key codec: the columns' joint range needs " + w + " = " + std::to_string(p.total) +
+                                  " bits, more than 64");
+    }
+    return HJ_OK;
+}
+
+}  // extern "C"
+
 void hj_placement_stats(long long *probes, long long *rejected, double *last_kept, double *worst_kept) {
     std::lock_guard<std::mutex> lk(g_place_mu);
     if (probes) *probes = g_place.probes;

@@ -434,6 +434,45 @@ hipError_t launch_gather_rows_i32(const int *x, long long ldx, int cx, const int
                                   const int *px, const int *py, const unsigned long long *count, long long cap,
                                   int *out, long long ldo, hipStream_t st);
 
+// ------------------------------------------------------------ composite keys
+// (hj_keys.hip) exact range packing of up to four int32 / int64 key columns
+// into one int64 key (hj.h "Composite keys").  The plan lives in one device
+// block; every kernel reads it there, so a captured sequence replayed over new
+// data follows the new data's plan.
+constexpr int kKeysMaxCols = 4;
+constexpr int kKeysBlock = 256;        // threads per workgroup of the streaming kernels
+constexpr int kKeysTile = 2048;        // rows per workgroup and loop step (observe, pack and unpack alike)
+constexpr int kKeysGridPerCu = 8;      // the grid is capped at this many workgroups per CU; the loop strides past it
+struct KeyPlan {
+    long long mn[kKeysMaxCols], mx[kKeysMaxCols];   // observed signed extremes (reset: INT64_MAX / INT64_MIN)
+    unsigned long long rows;                        // rows observed
+    unsigned long long oor;                         // rows packed with a value outside [lo, hi]
+    // the sealed plan
+    long long lo[kKeysMaxCols], hi[kKeysMaxCols];
+    unsigned long long span[kKeysMaxCols];          // (u64)hi - (u64)lo
+    unsigned long long mask[kKeysMaxCols];          // the low bits[c] bits set (0 for a 0-bit column)
+    int bits[kKeysMaxCols];
+    int shift[kKeysMaxCols];                        // 0 for a 0-bit column: such a column is masked out, never shifted by 64
+    int total;                                      // the sum of bits
+    int range;                                      // 1: total > 64, pack and unpack write nothing
+};
+struct KeyCols {                                    // column pointers, by value in the kernel arguments
+    const void *p[kKeysMaxCols];
+};
+struct KeyOutCols {
+    void *p[kKeysMaxCols];                          // null: the column is not written
+};
+// w64: bit c set = column c is int64 (else int32, sign-extended).  All launch
+// kernels only; n == 0 launches nothing.
+hipError_t keys_reset(KeyPlan *plan, hipStream_t st);
+hipError_t keys_observe(KeyPlan *plan, int ncols, unsigned w64, const KeyCols &cols, long long n, hipStream_t st);
+hipError_t keys_seal(KeyPlan *plan, int ncols, hipStream_t st);
+// out: n keys, or with pay (tuples) 2n words {key, pay}
+hipError_t keys_pack(KeyPlan *plan, int ncols, unsigned w64, const KeyCols &cols, const long long *pay, long long n,
+                     unsigned long long *out, bool tuples, hipStream_t st);
+hipError_t keys_unpack(const KeyPlan *plan, int ncols, unsigned w64, const unsigned long long *key, long long n,
+                       const KeyOutCols &out, hipStream_t st);
+
 hipError_t launch_gen_pkfk(unsigned long long seed, long long NR, unsigned long long hit_thr,
                            long long r0, long long nr, long long *rkey, long long *rpay,
                            long long s0, long long ns, long long *skey, long long *spay,

@@ -19,6 +19,7 @@ HJ_ERR_HIP = -2
 HJ_ERR_NOMEM = -3
 HJ_ERR_STATE = -4
 HJ_ERR_CAPACITY = -5
+HJ_ERR_RANGE = -6
 
 HJ_STRATEGY_AUTO = 0
 HJ_STRATEGY_GLOBAL = 1
@@ -37,6 +38,12 @@ HJ_EXPAND_OUTER = 1
 # the one workgroup that scans them) -- the sizes at which its paths change, for the tests
 EXPAND_SCAN_TILE = 2048
 EXPAND_SCAN_FAN = 1024
+# composite keys (hj_keys.hip: kKeysBlock threads walk kKeysTile rows per loop step over a grid capped at
+# kKeysGridPerCu workgroups per CU) -- the sizes at which the observe / pack / unpack loops wrap, for the tests
+HJ_KEYS_MAX_COLS = 4
+KEYS_BLOCK = 256
+KEYS_TILE = 2048
+KEYS_GRID_PER_CU = 8
 HJ_GROUP_MATCHED = 0
 HJ_GROUP_ALL = 1
 HJ_OUTER_BUILD = 1
@@ -117,6 +124,16 @@ def _load():
         "hj_dev_probe_full_tuples_i64": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_probe_full_i32": (_int, [_vp, _int, _vp, _i64, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp,
                                          _vp]),
+        "hj_keycodec_create": (_vp, [_int, _int, C.POINTER(C.c_int)]),
+        "hj_keycodec_destroy": (None, [_vp]),
+        "hj_dev_keycodec_reset": (_int, [_vp, _vp]),
+        "hj_dev_keycodec_observe": (_int, [_vp, C.POINTER(_vp), _i64, _vp]),
+        "hj_dev_keycodec_seal": (_int, [_vp, _vp]),
+        "hj_dev_keycodec_pack": (_int, [_vp, C.POINTER(_vp), _i64, _vp, _vp]),
+        "hj_dev_keycodec_pack_tuples": (_int, [_vp, C.POINTER(_vp), _vp, _i64, _vp, _vp]),
+        "hj_dev_keycodec_unpack": (_int, [_vp, _vp, _i64, C.POINTER(_vp), _vp]),
+        "hj_keycodec_info": (_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(_i64),
+                                    C.POINTER(_u64), C.POINTER(_u64)]),
         "hj_dev_partition_i64": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_dev_partition_tuples_i64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_partition_of": (_int, [_i64, _int]),

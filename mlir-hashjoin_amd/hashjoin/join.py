@@ -21,8 +21,8 @@ import os
 
 import torch
 
-from ._lib import (HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
-                   HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, check, lib)
+from ._lib import (HJ_ERR_RANGE, HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_KEYS_MAX_COLS, HJ_OK, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
+                   HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, HJError, check, lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
 EXISTS_KINDS = {"semi": HJ_EXISTS_SEMI, "anti": HJ_EXISTS_ANTI}
@@ -45,6 +45,145 @@ def _need_cuda(*ts):
     for t in ts:
         if t is not None and (not t.is_cuda or not t.is_contiguous()):
             raise ValueError("hash join inputs must be contiguous device tensors")
+
+
+class KeyCodec:
+    """Composite keys (hj.h "Composite keys"): exact range packing of up to
+    four int32 / int64 key columns into one int64 key that every join, probe
+    and aggregate of HashJoin takes as it takes any int64 key -- build_table,
+    probe_lookup, probe_expand, probe_group and the rest are called with
+    pack()'s output directly.
+
+        kc = KeyCodec([torch.int32, torch.int64])
+        kc.observe([r_a, r_b]); kc.observe([s_a, s_b]); kc.seal()
+        rk, sk = kc.pack([r_a, r_b]), kc.pack([s_a, s_b])
+
+    observe every relation that will be packed, then seal, then pack / unpack;
+    reset() starts over.  Columns are 1-D contiguous device tensors of the
+    codec's dtypes and of one length.  info() (synchronises) tells whether the
+    joint range fits 64 bits; while it does not, pack and unpack write nothing."""
+
+    def __init__(self, dtypes, device=0):
+        dtypes = tuple(dtypes)
+        if not 1 <= len(dtypes) <= HJ_KEYS_MAX_COLS:
+            raise ValueError(f"a key codec takes 1..{HJ_KEYS_MAX_COLS} columns")
+        if any(d not in (torch.int32, torch.int64) for d in dtypes):
+            raise TypeError("key columns must be int32 or int64")
+        if not torch.cuda.is_available():
+            raise RuntimeError("KeyCodec needs a HIP device (no CPU fallback)")
+        self.dtypes = dtypes
+        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        bits = (C.c_int * len(dtypes))(*[64 if d == torch.int64 else 32 for d in dtypes])
+        self._kc = lib.hj_keycodec_create(self.device.index, len(dtypes), bits)
+        if not self._kc:
+            raise HJError("hj_keycodec_create failed: " + lib.hj_last_error().decode())
+
+    def close(self):
+        if getattr(self, "_kc", None):
+            lib.hj_keycodec_destroy(self._kc)
+            self._kc = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _cols(self, cols, what="columns"):
+        """(pointer array, n) of a column set; raises TypeError / ValueError on a bad one."""
+        cols = list(cols)
+        if len(cols) != len(self.dtypes):
+            raise ValueError(f"{what}: expected {len(self.dtypes)} columns, got {len(cols)}")
+        for t, d in zip(cols, self.dtypes):
+            if not isinstance(t, torch.Tensor) or t.dtype != d:
+                raise TypeError(f"{what}: column dtypes must be {self.dtypes}")
+            if not t.is_cuda or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f"{what}: columns must be 1-D contiguous device tensors")
+        n = cols[0].numel()
+        if any(t.numel() != n for t in cols):
+            raise ValueError(f"{what}: columns differ in length")
+        return (C.c_void_p * len(cols))(*[t.data_ptr() for t in cols]), n
+
+    def reset(self, stream=None):
+        check(lib.hj_dev_keycodec_reset(self._kc, _stream(self.device, stream)), "hj_dev_keycodec_reset")
+
+    def observe(self, cols, stream=None):
+        """Fold one relation's key columns into the per-column [lo, hi]."""
+        ptrs, n = self._cols(cols)
+        check(lib.hj_dev_keycodec_observe(self._kc, ptrs, n, _stream(self.device, stream)), "hj_dev_keycodec_observe")
+
+    def seal(self, stream=None):
+        """Fix the plan (one tiny kernel; the widths stay on the device)."""
+        check(lib.hj_dev_keycodec_seal(self._kc, _stream(self.device, stream)), "hj_dev_keycodec_seal")
+
+    def pack(self, cols, out=None, stream=None):
+        """The int64 key column of a relation's key columns; exactly len rows of `out` are written."""
+        ptrs, n = self._cols(cols)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or not out.is_cuda
+              or not out.is_contiguous() or out.numel() < n):
+            raise ValueError("out must be a contiguous int64 device tensor of at least the columns' length")
+        check(lib.hj_dev_keycodec_pack(self._kc, ptrs, n, _ptr(out), _stream(self.device, stream)),
+              "hj_dev_keycodec_pack")
+        return out
+
+    def pack_tuples(self, cols, pay, out=None, stream=None):
+        """(n, 2) int64 {key, pay} rows: the exchange format of build_tuples / probe_tuples."""
+        ptrs, n = self._cols(cols)
+        if (not isinstance(pay, torch.Tensor) or pay.dtype != torch.int64 or not pay.is_cuda or pay.dim() != 1
+                or not pay.is_contiguous() or pay.numel() != n):
+            raise ValueError("pay must be a 1-D contiguous int64 device tensor of the columns' length")
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or not out.is_cuda
+              or not out.is_contiguous() or out.numel() < 2 * n):
+            raise ValueError("out must be a contiguous int64 device tensor of at least 2 x the columns' length")
+        check(lib.hj_dev_keycodec_pack_tuples(self._kc, ptrs, _ptr(pay), n, _ptr(out), _stream(self.device, stream)),
+              "hj_dev_keycodec_pack_tuples")
+        return out
+
+    def unpack(self, keys, outs=None, stream=None):
+        """The key columns of packed keys (the inverse of pack): a list with one
+        tensor per column.  outs: a list of output tensors of the codec's
+        dtypes, None entries are skipped (and stay None in the result)."""
+        if (not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1
+                or not keys.is_contiguous()):
+            raise ValueError("keys must be a 1-D contiguous int64 device tensor")
+        n = keys.numel()
+        if outs is None:
+            outs = [torch.empty(n, dtype=d, device=self.device) for d in self.dtypes]
+        outs = list(outs)
+        if len(outs) != len(self.dtypes):
+            raise ValueError(f"outs: expected {len(self.dtypes)} entries")
+        for t, d in zip(outs, self.dtypes):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != d:
+                raise TypeError(f"outs: column dtypes must be {self.dtypes}")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() < n:
+                raise ValueError("outs: contiguous device tensors of at least the keys' length")
+        ptrs = (C.c_void_p * len(outs))(*[None if t is None else t.data_ptr() for t in outs])
+        check(lib.hj_dev_keycodec_unpack(self._kc, _ptr(keys), n, ptrs, _stream(self.device, stream)),
+              "hj_dev_keycodec_unpack")
+        return outs
+
+    def info(self):
+        """The sealed plan (synchronises): {"total_bits", "bits", "lo", "hi",
+        "rows_observed", "rows_out_of_range", "fits"}; fits is False when the
+        joint range needs more than 64 bits (HJ_ERR_RANGE) -- the widths say
+        which column is to blame."""
+        total = C.c_int(0)
+        bits = (C.c_int * 4)()
+        lo = (C.c_int64 * 4)()
+        hi = (C.c_int64 * 4)()
+        rows, oor = C.c_uint64(0), C.c_uint64(0)
+        rc = lib.hj_keycodec_info(self._kc, C.byref(total), bits, lo, hi, C.byref(rows), C.byref(oor))
+        if rc not in (HJ_OK, HJ_ERR_RANGE):
+            check(rc, "hj_keycodec_info")
+        k = len(self.dtypes)
+        return {"total_bits": total.value, "bits": list(bits)[:k], "lo": list(lo)[:k], "hi": list(hi)[:k],
+                "rows_observed": rows.value, "rows_out_of_range": oor.value, "fits": rc == HJ_OK}
 
 
 class HashJoin:
@@ -349,7 +488,8 @@ class HashJoin:
         key maps to, the smallest when R repeats the key, `null` when R lacks
         it), or (out_r, out_cnt) if with_counts.  int64 keys with rpay None:
         the payload is R's row index (the id -> index mapping); int32 keys
-        always carry R's row ids."""
+        always carry R's row ids.  Composite keys: pass KeyCodec.pack's
+        output of both relations as rkey / skey."""
         self.probe_hint(skey.numel())
         try:
             if rkey.dtype == torch.int64 and rpay is None:
@@ -406,7 +546,8 @@ class HashJoin:
     def expand(self, rkey, rpay, skey, how="inner", null=-1, stream=None):
         """Build R, then probe_expand sized exactly: (offsets, out_r), a CSR over
         S's rows in input order.  int64 keys with rpay None: the payload is R's
-        row index; int32 keys always carry R's row ids."""
+        row index; int32 keys always carry R's row ids.  Composite keys: pass
+        KeyCodec.pack's output of both relations as rkey / skey."""
         self.probe_hint(skey.numel())
         try:
             if rkey.dtype == torch.int64 and rpay is None:
@@ -502,7 +643,8 @@ class HashJoin:
         """Build R, then probe_group into outputs of |R| rows (the most the
         result can hold) or `capacity`: returns (rpay, {agg: tensor}) trimmed
         to M, for aggs among "count", "sum", "min", "max".  int32 keys: rpay
-        and sval are None (row ids)."""
+        and sval are None (row ids).  Composite keys: pass KeyCodec.pack's
+        output of both relations as rkey / skey."""
         if how not in GROUP_KINDS:
             raise ValueError("how must be 'matched' or 'all'")
         if any(a not in GROUP_AGGS for a in aggs):
@@ -916,6 +1058,80 @@ class HashJoin:
                 return out_r[:m], out_s[:m]
             cap = m
         raise RuntimeError("join output did not fit after resizing")
+
+    # ---- composite keys (hj.h "Composite keys"): up to four key columns, packed exactly into one int64 key
+    JOIN_ON_KINDS = ("inner", "semi", "anti", "left", "right", "full")
+
+    def _packed_keys(self, relations, stream=None):
+        """(codec, [one packed int64 key column per relation]) for relations
+        given as lists of key columns: a codec of the call's own (the caller
+        closes it) observes all, seals, packs each, then the plan is read ONCE
+        (the one synchronisation): HJError when the joint range needs more than
+        64 bits (the packs wrote nothing then) or a row was packed out of range
+        -- before the caller builds anything."""
+        kc = KeyCodec(tuple(getattr(t, "dtype", None) for t in relations[0]), self.device.index)
+        try:
+            for cols in relations:
+                kc.observe(cols, stream=stream)
+            kc.seal(stream=stream)
+            keys = [kc.pack(cols, stream=stream) for cols in relations]
+            info = kc.info()
+            if not info["fits"]:
+                raise HJError(f"composite key: the columns' joint range needs {info['bits']} = {info['total_bits']} "
+                              f"bits, more than 64 (HJ_ERR_RANGE {HJ_ERR_RANGE})")
+            if info["rows_out_of_range"]:
+                raise HJError(f"composite key: {info['rows_out_of_range']} rows packed outside the observed range")
+        except BaseException:
+            kc.close()
+            raise
+        return kc, keys
+
+    def join_on(self, rcols, rpay, scols, spay=None, how="inner", stream=None, **kw):
+        """The join ON r.c0 = s.c0 AND r.c1 = s.c1 ...: rcols / scols are lists
+        of 1..4 key columns (1-D contiguous int32 / int64 device tensors, the
+        same dtypes on both sides), rpay / spay int64 payload columns (None:
+        the row index).  how = 'inner' (join), 'semi' / 'anti' (semi_join /
+        anti_join: S rows with / without a partner), 'left' (outer_join: every
+        S row), 'right' (full_join how="build": every R row), 'full'
+        (full_join); returns what that method returns, and takes its keyword
+        arguments (capacity, null, null_r, null_s, with_keys -- the keys of
+        with_keys are the packed ones).  Both relations are observed, the plan
+        sealed and read once: HJError when the joint range needs more than 64
+        bits, before any build."""
+        if how not in self.JOIN_ON_KINDS:
+            raise ValueError("how must be one of " + ", ".join(self.JOIN_ON_KINDS))
+        kc, (rk, sk) = self._packed_keys([rcols, scols], stream=stream)
+        kc.close()   # the packed columns stand alone
+        if rpay is None:
+            rpay = torch.arange(rk.numel(), dtype=torch.int64, device=self.device)
+        if spay is None:
+            spay = torch.arange(sk.numel(), dtype=torch.int64, device=self.device)
+        if how == "inner":
+            return self.join(rk, rpay, sk, spay, stream=stream, **kw)
+        if how in ("semi", "anti"):
+            f = self.semi_join if how == "semi" else self.anti_join
+            return f(rk, sk, spay, rpay, stream=stream, **kw)
+        if how == "left":
+            return self.outer_join(rk, rpay, sk, spay, stream=stream, **kw)
+        return self.full_join(rk, rpay, sk, spay, how="build" if how == "right" else "full", stream=stream, **kw)
+
+    def aggregate_on(self, cols, val=None, aggs=("count", "sum"), stream=None):
+        """GROUP BY c0, c1, ...: {"keys": [one tensor per column, in the
+        columns' dtypes], agg: tensor, ...} with one row per distinct tuple,
+        for aggs among "count", "sum", "min", "max" over the int64 column val.
+        Packs, calls aggregate, unpacks the key column."""
+        kc, (key,) = self._packed_keys([cols], stream=stream)
+        try:
+            a = self.aggregate(key, val, aggs=aggs, stream=stream)
+            out = {"keys": kc.unpack(a.pop("key").contiguous(), stream=stream)}
+        finally:
+            kc.close()
+        out.update(a)
+        return out
+
+    def distinct_on(self, cols, stream=None):
+        """SELECT DISTINCT c0, c1, ...: the distinct tuples' columns, in no particular order."""
+        return self.aggregate_on(cols, aggs=(), stream=stream)["keys"]
 
 
 # ------------------------------------------------------------------ datagen
