@@ -2759,6 +2759,212 @@ int hj_keycodec_info(hj_keycodec *kc, int *total_bits, int bits[4], int64_t lo[4
 
 }  // extern "C"
 
+// -------------------------------------------------------------- key filter
+// A key filter: the words (its own or the caller's) and apply's workspace --
+// tile counts, scan sums and the row bitmap in ONE grow-only allocation.
+struct hj_filter {
+    int device = 0;
+    int64_t nblocks = 0;
+    unsigned *words = nullptr;   // device, nblocks * 8 words
+    bool owns = false;
+    void *work = nullptr;        // device
+    int64_t work_rows = -1;      // rows the workspace admits
+    hj::FilterWork ws{nullptr, nullptr, nullptr};
+};
+
+namespace {
+
+constexpr int64_t kFilterMaxBlocks = (int64_t(1) << 31) - 1;
+
+int filter_work(hj_filter *f, int64_t rows) {
+    if (rows <= f->work_rows) return HJ_OK;
+    const size_t nt = hj::filter_tiles(rows) + 1;
+    const size_t tiles_b = (nt * 8 + 15) & ~size_t(15), sums_b = (hj::exclusive_scan_sums(nt) * 8 + 15) & ~size_t(15);
+    const size_t map_b = hj::filter_bitmap_bytes(rows) + 16;
+    HJ_HIP(hipSetDevice(f->device));
+    if (f->work) HJ_HIP(hipFree(f->work));   // (waits for the device: nothing in flight reads the old one)
+    f->work = nullptr;
+    f->work_rows = -1;
+    if (hipMalloc(&f->work, tiles_b + sums_b + map_b) != hipSuccess) {
+        (void)hipGetLastError();
+        HJ_FAIL(HJ_ERR_NOMEM, "key filter: hipMalloc of the apply workspace for " + std::to_string(rows) + " rows");
+    }
+    f->ws.tiles = (unsigned long long *)f->work;
+    f->ws.sums = (unsigned long long *)((char *)f->work + tiles_b);
+    f->ws.bitmap = (unsigned char *)f->work + tiles_b + sums_b;
+    f->work_rows = rows;
+    return HJ_OK;
+}
+
+int filter_insert(hj_filter *f, int form, const void *key, int64_t n, void *stream) {
+    if (!f) HJ_FAIL(HJ_ERR_ARG, "null filter");
+    if (n < 0 || (n > 0 && !key)) HJ_FAIL(HJ_ERR_ARG, "bad relation: null keys or a negative row count");
+    HJ_HIP(hipSetDevice(f->device));
+    HJ_HIP(hj::filter_insert(f->words, f->nblocks, form, key, n, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+// any_out: some output pointer is non-null; rel_err: what is wrong with the relation (null: nothing)
+int filter_apply(hj_filter *f, int form, int kind, const void *key, const int64_t *pay, int64_t n, int64_t row_base,
+                 const char *rel_err, void *out_key, void *out_pay, void *out_row, int64_t cap, uint64_t *d_count,
+                 void *stream) {
+    if (!f) HJ_FAIL(HJ_ERR_ARG, "null filter");
+    if (kind != HJ_FILTER_PASS && kind != HJ_FILTER_REJECT) HJ_FAIL(HJ_ERR_ARG, "unknown filter kind");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (n < 0 || (n > 0 && !key)) HJ_FAIL(HJ_ERR_ARG, "bad relation: null keys or a negative row count");
+    if (rel_err) HJ_FAIL(HJ_ERR_ARG, std::string("bad relation: ") + rel_err);
+    const bool any_out = out_key || out_pay || out_row;
+    if (cap < 0) HJ_FAIL(HJ_ERR_ARG, "negative output capacity");
+    if (cap > 0 && !any_out) HJ_FAIL(HJ_ERR_ARG, "out_cap > 0 with every output null (the count form is out_cap == 0)");
+    if (cap == 0 && any_out) HJ_FAIL(HJ_ERR_ARG, "out_cap == 0 with an output (the count form takes none)");
+    HJ_TRY(filter_work(f, n));
+    HJ_HIP(hipSetDevice(f->device));
+    HJ_HIP(hj::filter_apply(f->words, f->nblocks, form, kind, key, (const long long *)pay, n, row_base, out_key,
+                            out_pay, out_row, cap, (unsigned long long *)d_count, f->ws, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t hj_filter_blocks_for(int64_t n_keys, int bits_per_key) {
+    if (n_keys < 0 || bits_per_key < 4 || bits_per_key > 64) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "key filter: n_keys >= 0 and bits_per_key in 4..64");
+        return HJ_ERR_ARG;
+    }
+    const unsigned __int128 bits = (unsigned __int128)n_keys * (unsigned)bits_per_key;
+    const unsigned __int128 blocks = (bits + 255) / 256;
+    if (blocks > (unsigned __int128)kFilterMaxBlocks) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "key filter: more than 2^31 - 1 blocks");
+        return HJ_ERR_ARG;
+    }
+    return blocks ? (int64_t)blocks : 1;
+}
+
+int hj_filter_place(int64_t key, int64_t nblocks, int64_t *block, uint32_t mask[8]) {
+    if (nblocks < 1 || nblocks > kFilterMaxBlocks) HJ_FAIL(HJ_ERR_ARG, "key filter: nblocks must be in [1, 2^31)");
+    const uint64_t h = hj::filter_hash(key);
+    if (block) *block = (int64_t)hj::filter_block(h, (uint64_t)nblocks);
+    if (mask)
+        for (int w = 0; w < 8; ++w) mask[w] = hj::filter_mask((uint32_t)h, w);
+    return HJ_OK;
+}
+
+hj_filter *hj_filter_create(int device, int64_t nblocks, void *d_words) {
+    // the arguments first, before anything touches a device
+    if (nblocks < 1 || nblocks > kFilterMaxBlocks) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "key filter: nblocks must be in [1, 2^31)");
+        return nullptr;
+    }
+    if (((uintptr_t)d_words) & 31) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "key filter: the words buffer must be 32-byte aligned");
+        return nullptr;
+    }
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        fail(HJ_ERR_HIP, __FILE__, __LINE__, "no HIP device visible");
+        return nullptr;
+    }
+    if (device < 0 || device >= n) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "device index out of range");
+        return nullptr;
+    }
+    hj_filter *f = new hj_filter();
+    f->device = device;
+    f->nblocks = nblocks;
+    f->words = (unsigned *)d_words;
+    if (!d_words) {
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = hipMalloc((void **)&f->words, (size_t)nblocks * 32);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            fail(e == hipErrorOutOfMemory ? HJ_ERR_NOMEM : HJ_ERR_HIP, __FILE__, __LINE__,
+                 std::string("key filter: ") + hipGetErrorString(e));
+            delete f;
+            return nullptr;
+        }
+        f->owns = true;
+    }
+    return f;
+}
+
+void hj_filter_destroy(hj_filter *f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    (void)hipDeviceSynchronize();
+    if (f->owns && f->words) (void)hipFree(f->words);
+    if (f->work) (void)hipFree(f->work);
+    delete f;
+}
+
+int hj_filter_words(hj_filter *f, void **d_words, int64_t *nblocks) {
+    if (!f) HJ_FAIL(HJ_ERR_ARG, "null filter");
+    if (d_words) *d_words = f->words;
+    if (nblocks) *nblocks = f->nblocks;
+    return HJ_OK;
+}
+
+int hj_filter_reserve(hj_filter *f, int64_t max_rows) {
+    if (!f) HJ_FAIL(HJ_ERR_ARG, "null filter");
+    if (max_rows < 0) HJ_FAIL(HJ_ERR_ARG, "negative row count");
+    return filter_work(f, max_rows);
+}
+
+int hj_dev_filter_clear(hj_filter *f, void *stream) {
+    if (!f) HJ_FAIL(HJ_ERR_ARG, "null filter");
+    HJ_HIP(hipSetDevice(f->device));
+    HJ_HIP(hj::filter_clear(f->words, f->nblocks, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+int hj_dev_filter_insert_i64(hj_filter *f, const int64_t *key, int64_t n, void *stream) {
+    return filter_insert(f, hj::kCols64, key, n, stream);
+}
+
+int hj_dev_filter_insert_tuples_i64(hj_filter *f, const int64_t *tuples, int64_t n, void *stream) {
+    return filter_insert(f, hj::kPacked64, tuples, n, stream);
+}
+
+int hj_dev_filter_insert_i32(hj_filter *f, const int32_t *key, int64_t n, void *stream) {
+    return filter_insert(f, hj::kCol32, key, n, stream);
+}
+
+int hj_dev_filter_merge(hj_filter *f, const hj_filter *other, void *stream) {
+    if (!f) HJ_FAIL(HJ_ERR_ARG, "null filter");
+    if (!other) HJ_FAIL(HJ_ERR_ARG, "key filter: null filter to merge in");
+    if (other->nblocks != f->nblocks || other->device != f->device)
+        HJ_FAIL(HJ_ERR_ARG, "key filter: merge of filters of different geometry (" + std::to_string(f->nblocks) +
+                                " and " + std::to_string(other->nblocks) + " blocks) or devices");
+    HJ_HIP(hipSetDevice(f->device));
+    HJ_HIP(hj::filter_merge(f->words, other->words, f->nblocks, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+int hj_dev_filter_apply_i64(hj_filter *f, int kind, const int64_t *skey, const int64_t *spay, int64_t n,
+                            int64_t *out_key, int64_t *out_pay, int64_t *out_row, int64_t out_cap, uint64_t *d_count,
+                            void *stream) {
+    const bool no_pay = n > 0 && out_pay && !spay;
+    return filter_apply(f, hj::kCols64, kind, skey, spay, n, 0, no_pay ? "null payload column" : nullptr, out_key,
+                        out_pay, out_row, out_cap, d_count, stream);
+}
+
+int hj_dev_filter_apply_tuples_i64(hj_filter *f, int kind, const int64_t *tuples, int64_t n, int64_t *out_tuples,
+                                   int64_t *out_row, int64_t out_cap, uint64_t *d_count, void *stream) {
+    return filter_apply(f, hj::kPacked64, kind, tuples, nullptr, n, 0, nullptr, out_tuples, nullptr, out_row, out_cap,
+                        d_count, stream);
+}
+
+int hj_dev_filter_apply_i32(hj_filter *f, int kind, const int32_t *skey, int64_t n, int64_t row_base,
+                            int32_t *out_key, int32_t *out_row, int64_t out_cap, uint64_t *d_count, void *stream) {
+    const bool bad_ids = n >= 0 && (row_base < 0 || row_base > INT32_MAX - n);
+    return filter_apply(f, hj::kCol32, kind, skey, nullptr, n, bad_ids ? 0 : row_base,
+                        bad_ids ? "row ids past 2^31 - 1" : nullptr, out_key, nullptr, out_row, out_cap, d_count,
+                        stream);
+}
+
+}  // extern "C"
+
 void hj_placement_stats(long long *probes, long long *rejected, double *last_kept, double *worst_kept) {
     std::lock_guard<std::mutex> lk(g_place_mu);
     if (probes) *probes = g_place.probes;

@@ -473,6 +473,43 @@ hipError_t keys_pack(KeyPlan *plan, int ncols, unsigned w64, const KeyCols &cols
 hipError_t keys_unpack(const KeyPlan *plan, int ncols, unsigned w64, const unsigned long long *key, long long n,
                        const KeyOutCols &out, hipStream_t st);
 
+// ---------------------------------------------------------------- key filter
+// (hj_filter.hip) a split-block Bloom filter of a build side's keys (hj.h "Key
+// filter"): nblocks blocks of eight uint32 words; a key owns one bit in each
+// word of one block.  The placement is one function for the kernels and the
+// host (hj_filter_place).
+constexpr int kFilterBlock = 256;      // threads per workgroup
+constexpr int kFilterTile = 2048;      // rows per workgroup and loop step (insert, count and write alike)
+constexpr int kFilterGridPerCu = 8;    // the grid is capped at this many workgroups per CU; the loop strides past it
+HJ_HD uint64_t filter_hash(int64_t key) { return fmix64((uint64_t)key ^ 0x9E3779B97F4A7C15ull); }
+HJ_HD uint64_t filter_block(uint64_t h, uint64_t nblocks) { return ((h >> 32) * nblocks) >> 32; }   // nblocks < 2^31
+HJ_HD uint32_t filter_mask(uint32_t lo, int w) {   // the bit of word w (0..7) for a key whose hash's low word is lo
+    constexpr uint32_t salt[8] = {0x47b6137bu, 0x44974d91u, 0x8824ad5bu, 0xa2b7289du,
+                                  0x705495c7u, 0x2df1424bu, 0x9efc4947u, 0x5c6bfb31u};
+    return 1u << ((uint32_t)(lo * salt[w]) >> 27);
+}
+struct FilterWork {                    // apply's workspace, owned by the filter object
+    unsigned long long *tiles;         // >= filter_tiles(n) + 1 words
+    unsigned long long *sums;          // >= exclusive_scan_sums(filter_tiles(n) + 1) words
+    unsigned char *bitmap;             // >= filter_bitmap_bytes(n) bytes
+};
+size_t filter_tiles(long long n);
+size_t filter_bitmap_bytes(long long n);
+// All launch kernels only.  form: kCols64 (int64 column), kPacked64 (16-byte
+// {key, pay} tuples) or kCol32 (int32 column, sign-extended).
+hipError_t filter_clear(unsigned *words, long long nblocks, hipStream_t st);
+hipError_t filter_insert(unsigned *words, long long nblocks, int form, const void *key, long long n, hipStream_t st);
+hipError_t filter_merge(unsigned *words, const unsigned *other, long long nblocks, hipStream_t st);
+// kind 0: the rows whose key passes, 1: the others; compacted in input order.
+// out_key: int64 keys / 16-byte tuples / int32 keys by form; out_pay: kCols64
+// only; out_row: int64 source positions (kCol32: int32 row ids row_base + row).
+// Every output may be null; nothing is written at or past cap; *count = all
+// qualifying rows.  n == 0 writes the count alone.
+hipError_t filter_apply(const unsigned *words, long long nblocks, int form, int kind, const void *key,
+                        const long long *pay, long long n, long long row_base, void *out_key, void *out_pay,
+                        void *out_row, long long cap, unsigned long long *count, const FilterWork &ws,
+                        hipStream_t st);
+
 hipError_t launch_gen_pkfk(unsigned long long seed, long long NR, unsigned long long hit_thr,
                            long long r0, long long nr, long long *rkey, long long *rpay,
                            long long s0, long long ns, long long *skey, long long *spay,

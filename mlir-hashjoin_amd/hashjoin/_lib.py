@@ -44,6 +44,13 @@ HJ_KEYS_MAX_COLS = 4
 KEYS_BLOCK = 256
 KEYS_TILE = 2048
 KEYS_GRID_PER_CU = 8
+# the key filter (hj_filter.hip: kFilterBlock threads walk kFilterTile rows per loop step over a grid capped at
+# kFilterGridPerCu workgroups per CU) -- the sizes at which the insert / apply loops wrap, for the tests
+HJ_FILTER_PASS = 0
+HJ_FILTER_REJECT = 1
+FILTER_BLOCK = 256
+FILTER_TILE = 2048
+FILTER_GRID_PER_CU = 8
 HJ_GROUP_MATCHED = 0
 HJ_GROUP_ALL = 1
 HJ_OUTER_BUILD = 1
@@ -134,6 +141,20 @@ def _load():
         "hj_dev_keycodec_unpack": (_int, [_vp, _vp, _i64, C.POINTER(_vp), _vp]),
         "hj_keycodec_info": (_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(_i64),
                                     C.POINTER(_u64), C.POINTER(_u64)]),
+        "hj_filter_blocks_for": (_i64, [_i64, _int]),
+        "hj_filter_place": (_int, [_i64, _i64, C.POINTER(_i64), C.POINTER(C.c_uint32)]),
+        "hj_filter_create": (_vp, [_int, _i64, _vp]),
+        "hj_filter_destroy": (None, [_vp]),
+        "hj_filter_words": (_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+        "hj_filter_reserve": (_int, [_vp, _i64]),
+        "hj_dev_filter_clear": (_int, [_vp, _vp]),
+        "hj_dev_filter_insert_i64": (_int, [_vp, _vp, _i64, _vp]),
+        "hj_dev_filter_insert_tuples_i64": (_int, [_vp, _vp, _i64, _vp]),
+        "hj_dev_filter_insert_i32": (_int, [_vp, _vp, _i64, _vp]),
+        "hj_dev_filter_merge": (_int, [_vp, _vp, _vp]),
+        "hj_dev_filter_apply_i64": (_int, [_vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_filter_apply_tuples_i64": (_int, [_vp, _int, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_filter_apply_i32": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_partition_i64": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_dev_partition_tuples_i64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_partition_of": (_int, [_i64, _int]),

@@ -308,6 +308,33 @@ def _probe_parts(hj, parts, capacity, total, device, probes=None):
     return (torch.cat([out_r[:pos]] + [e[0] for e in extra]), torch.cat([out_s[:pos]] + [e[1] for e in extra]))
 
 
+def _or_reduce_start(flt, group):
+    """Start the bitwise OR of every rank's filter words into flt.words.  One
+    all-reduce with ReduceOp.BOR where the backend has it (gloo); RCCL has no
+    bitwise reductions, so there the words are all-gathered and
+    _or_reduce_finish ORs the other ranks' in with the filter's merge kernel
+    (world x the filter's bytes received per rank: 2 bytes per build key and
+    rank at 16 bits per key)."""
+    if dist.get_backend(group) != "nccl":
+        return dist.all_reduce(flt.words, op=dist.ReduceOp.BOR, group=group, async_op=True), None
+    world = dist.get_world_size(group)
+    if world == 1:
+        return None, None
+    gathered = torch.empty((world, flt.words.numel()), dtype=flt.words.dtype, device=flt.words.device)
+    return dist.all_gather_into_tensor(gathered, flt.words, group=group, async_op=True), gathered
+
+
+def _or_reduce_finish(flt, started, group):
+    work, gathered = started
+    if work is not None:
+        work.wait()
+    if gathered is not None:
+        me = dist.get_rank(group)
+        for p in range(gathered.shape[0]):
+            if p != me:
+                flt.merge_words(gathered[p])
+
+
 # S moves in this many consecutive batches when ranks exchange over links, so
 # that the probe of one part overlaps the transfer of the next (a part of
 # 2^24 rows probes in ~0.56 ms, about what its 0.25 GiB take on the links at
@@ -317,7 +344,7 @@ S_PARTS = 2
 
 def distributed_join(hj, rkey, rpay, skey, spay, group=None, capacity=None, phases=None,
                      replicate_max_rows=None, max_rows=None, self_p2p=False, n_build_global=None,
-                     s_parts=None, route_bits=None):
+                     s_parts=None, route_bits=None, prefilter=None):
     """Join this rank's slices of R and S against every other rank's.
 
     hj: a hashjoin.HashJoin on this rank's GPU (or any object with its
@@ -333,7 +360,18 @@ def distributed_join(hj, rkey, rpay, skey, spay, group=None, capacity=None, phas
     replicating and shuffling R (~0.15 ms per call).  s_parts: batches the
     shuffled S moves in (default S_PARTS, 1 at world size 1).  route_bits: the
     folded routing's bins per owner (default hj.route_plan's choice; 0 routes
-    by owner only and the receivers run both local passes)."""
+    by owner only and the receivers run both local passes).  prefilter: bits
+    per build key of a key filter (hj.h "Key filter") that every rank builds
+    from its R slice, OR-reduced over the ranks while R is routed, and applied
+    to S BEFORE S is routed, so that only the S rows that may have a partner
+    cross the links; None (the default): no filter.  The shuffle modes only
+    (replicated R: S never crosses a link, the keyword is ignored); hj needs
+    key_filter.  phases then gains the event "s_filter" (the filter is applied:
+    s_route -> s_filter is the wait for the reduced filter and its
+    application, s_filter -> routed S's routing) and "filtered" = (S rows in,
+    S rows kept) of this rank."""
+    if prefilter is not None and not hasattr(hj, "key_filter"):
+        raise ValueError("prefilter needs an hj with key_filter")
     if replicate_max_rows is None:
         replicate_max_rows = REPLICATE_MAX_ROWS
     cuda = rkey.is_cuda
@@ -361,6 +399,24 @@ def distributed_join(hj, rkey, rpay, skey, spay, group=None, capacity=None, phas
     world = dist.get_world_size(group)
     if s_parts is None:
         s_parts = S_PARTS if world > 1 else 1
+    flt = flt_work = None
+    if prefilter is not None:
+        # this rank's R keys, then OR over the ranks while R is routed below
+        flt = hj.key_filter(int(n_build_global), int(prefilter))
+        flt.clear()
+        flt.insert(rkey)
+        flt_work = _or_reduce_start(flt, group)
+
+    def filter_s(skey, spay):
+        if flt is None:
+            return skey, spay
+        _or_reduce_finish(flt, flt_work, group)
+        n_in = skey.numel()
+        skey, spay = flt.apply(skey, spay)
+        ev("s_filter")
+        if phases is not None:
+            phases["filtered"] = (n_in, skey.numel())
+        return skey, spay
     if route_bits is not None:
         sub = int(route_bits) if (world & (world - 1)) == 0 else 0
     else:
@@ -372,6 +428,7 @@ def distributed_join(hj, rkey, rpay, skey, spay, group=None, capacity=None, phas
         send_r, cr = hj.route(rkey, rpay, world, sub, slot="r")
         xr = RoutedExchange(send_r, cr, nb, group, max_rows, self_p2p)
         ev("s_route")   # S's share of the route phase: its first partition pass happens here
+        skey, spay = filter_s(skey, spay)
         send_s, cs = hj.route(skey, spay, world, sub, slot="s")
         xs = RoutedExchange(send_s, cs, nb, group, max_rows, self_p2p, parts=s_parts)
         ev("routed")
@@ -393,6 +450,7 @@ def distributed_join(hj, rkey, rpay, skey, spay, group=None, capacity=None, phas
     send_r, cr = hj.partition(rkey, rpay, world)
     xr = Exchange(send_r, cr, group, max_rows, self_p2p)
     ev("s_route")
+    skey, spay = filter_s(skey, spay)
     send_s, cs = hj.partition(skey, spay, world)
     xs = Exchange(send_s, cs, group, max_rows, self_p2p, parts=s_parts)
     ev("routed")

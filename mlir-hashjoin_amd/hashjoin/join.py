@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from ._lib import (HJ_ERR_RANGE, HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_KEYS_MAX_COLS, HJ_OK, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
+from ._lib import (HJ_ERR_RANGE, HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_FILTER_PASS, HJ_FILTER_REJECT, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_KEYS_MAX_COLS, HJ_OK, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
                    HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, HJError, check, lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
@@ -30,6 +30,7 @@ FULL_KINDS = {"build": HJ_OUTER_BUILD, "full": HJ_OUTER_FULL}
 GROUP_KINDS = {"matched": HJ_GROUP_MATCHED, "all": HJ_GROUP_ALL}
 GROUP_AGGS = ("count", "sum", "min", "max")
 EXPAND_KINDS = {"inner": HJ_EXPAND_INNER, "outer": HJ_EXPAND_OUTER}
+FILTER_KINDS = {"pass": HJ_FILTER_PASS, "reject": HJ_FILTER_REJECT}
 
 
 def _ptr(t):
@@ -184,6 +185,158 @@ class KeyCodec:
         k = len(self.dtypes)
         return {"total_bits": total.value, "bits": list(bits)[:k], "lo": list(lo)[:k], "hi": list(hi)[:k],
                 "rows_observed": rows.value, "rows_out_of_range": oor.value, "fits": rc == HJ_OK}
+
+
+class KeyFilter:
+    """A key filter (hj.h "Key filter"): a split-block Bloom filter of a build
+    side's keys, applied to a probe side before the expensive step.  No false
+    negatives: a row that fails certainly has no partner.
+
+        f = KeyFilter(n_keys=rkey.numel())          # 16 bits per key: ~0.13 % false positives
+        f.clear(); f.insert(rkey)
+        skey, spay = f.apply(skey, spay)            # the rows that may have a partner, in input order
+
+    The words live in `words`, a torch.int64 tensor of nblocks * 4 elements
+    that the filter uses in place, so the filters of several ranks combine
+    with one bitwise-OR all-reduce of that tensor (or merge() on one device).
+    Keys are 1-D int64 or int32 columns or (n, 2) int64 {key, pay} tuples."""
+
+    def __init__(self, n_keys=None, bits_per_key=16, nblocks=None, device=0, words=None):
+        if words is not None:   # a filter over the caller's words (e.g. another rank's, gathered)
+            if (not isinstance(words, torch.Tensor) or words.dtype != torch.int64 or not words.is_cuda
+                    or not words.is_contiguous() or words.numel() % 4 or words.numel() == 0):
+                raise ValueError("words must be a contiguous int64 device tensor of nblocks * 4 elements")
+            nblocks, device = words.numel() // 4, words.device.index
+        if nblocks is None:
+            if n_keys is None:
+                raise ValueError("a key filter needs n_keys or nblocks")
+            nblocks = lib.hj_filter_blocks_for(int(n_keys), int(bits_per_key))
+            if nblocks < 0:
+                raise ValueError("key filter: " + lib.hj_last_error().decode())
+        nblocks = int(nblocks)
+        if not 1 <= nblocks < (1 << 31):
+            raise ValueError("key filter: nblocks must be in [1, 2^31)")
+        if not torch.cuda.is_available():
+            raise RuntimeError("KeyFilter needs a HIP device (no CPU fallback)")
+        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        self.nblocks = nblocks
+        self.bits_per_key = int(bits_per_key)
+        self.words = torch.empty(nblocks * 4, dtype=torch.int64, device=self.device) if words is None else words
+        self._merged = []
+        self._count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._f = lib.hj_filter_create(self.device.index, nblocks, _ptr(self.words))
+        if not self._f:
+            raise HJError("hj_filter_create failed: " + lib.hj_last_error().decode())
+
+    def close(self):
+        for o in getattr(self, "_merged", []):
+            o.close()
+        self._merged = []
+        if getattr(self, "_f", None):
+            lib.hj_filter_destroy(self._f)
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _form(keys, what="keys"):
+        """'i64' | 'tuples' | 'i32' of a key tensor; raises on anything else."""
+        if not isinstance(keys, torch.Tensor) or not keys.is_cuda or not keys.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous device tensor")
+        if keys.dtype == torch.int64 and keys.dim() == 1:
+            return "i64"
+        if keys.dtype == torch.int64 and keys.dim() == 2 and keys.shape[1] == 2:
+            return "tuples"
+        if keys.dtype == torch.int32 and keys.dim() == 1:
+            return "i32"
+        raise TypeError(f"{what} must be a 1-D int64 / int32 column or (n, 2) int64 tuples")
+
+    def reserve(self, rows):
+        """Size apply's workspace for `rows` rows (grow-only); after it clear /
+        insert / apply launch kernels only and can be captured in a graph."""
+        check(lib.hj_filter_reserve(self._f, int(rows)), "hj_filter_reserve")
+
+    def clear(self, stream=None):
+        check(lib.hj_dev_filter_clear(self._f, _stream(self.device, stream)), "hj_dev_filter_clear")
+
+    def insert(self, keys, stream=None):
+        form = self._form(keys)
+        f = {"i64": lib.hj_dev_filter_insert_i64, "tuples": lib.hj_dev_filter_insert_tuples_i64,
+             "i32": lib.hj_dev_filter_insert_i32}[form]
+        check(f(self._f, _ptr(keys), keys.shape[0], _stream(self.device, stream)), "hj_dev_filter_insert")
+
+    def merge(self, other, stream=None):
+        """self |= other (same nblocks, same device)."""
+        check(lib.hj_dev_filter_merge(self._f, other._f, _stream(self.device, stream)), "hj_dev_filter_merge")
+
+    def merge_words(self, words, stream=None):
+        """self |= a filter given as its words tensor (nblocks * 4 int64, this
+        device).  The wrapper object lives until close(): the merge is
+        asynchronous and destroying a filter waits for the device."""
+        other = KeyFilter(words=words)
+        self._merged.append(other)
+        self.merge(other, stream=stream)
+
+    def apply_into(self, skey, spay=None, kind="pass", out_key=None, out_pay=None, out_row=None, count=None,
+                   row_base=0, stream=None):
+        """The raw call: writes min(M, cap) qualifying rows, in input order,
+        into the outputs given (cap = their common length; none: the count
+        form); `count` (int64 device tensor) receives M.  Returns count."""
+        form = self._form(skey, "skey")
+        outs = [o for o in (out_key, out_pay, out_row) if o is not None]
+        _need_cuda(spay, *outs)
+        cap = outs[0].shape[0] if outs else 0
+        if any(o.shape[0] != cap for o in outs):
+            raise ValueError("output columns differ in length")
+        count = self._count if count is None else count
+        st, k, n = _stream(self.device, stream), FILTER_KINDS[kind], skey.shape[0]
+        if form == "i64":
+            if spay is not None and (spay.dtype != torch.int64 or spay.numel() != n):
+                raise ValueError("spay must be an int64 column of skey's length")
+            check(lib.hj_dev_filter_apply_i64(self._f, k, _ptr(skey), _ptr(spay), n, _ptr(out_key), _ptr(out_pay),
+                                              _ptr(out_row), cap, _ptr(count), st), "hj_dev_filter_apply_i64")
+        elif form == "tuples":
+            if spay is not None or out_pay is not None:
+                raise ValueError("tuples carry their payloads")
+            check(lib.hj_dev_filter_apply_tuples_i64(self._f, k, _ptr(skey), n, _ptr(out_key), _ptr(out_row), cap,
+                                                     _ptr(count), st), "hj_dev_filter_apply_tuples_i64")
+        else:
+            if spay is not None or out_pay is not None:
+                raise ValueError("i32 relations carry row ids, not payloads")
+            check(lib.hj_dev_filter_apply_i32(self._f, k, _ptr(skey), n, int(row_base), _ptr(out_key), _ptr(out_row),
+                                              cap, _ptr(count), st), "hj_dev_filter_apply_i32")
+        return count
+
+    def apply(self, skey, spay=None, kind="pass", with_rows=False, capacity=None, stream=None):
+        """The rows of S whose key passes (kind='pass') / fails ('reject'),
+        compacted in input order: the key column (tuples: the rows), then the
+        payload column if spay is given, then the source positions (i32: row
+        ids) if with_rows -- one tensor, or a tuple of them.  Outputs are sized
+        |S| rows, or `capacity` with one more call at the exact M.
+        Synchronises to read M."""
+        form = self._form(skey, "skey")
+        n = skey.shape[0]
+        cap = max(1, n if capacity is None else int(capacity))
+        for _ in range(2):
+            shape = (cap, 2) if form == "tuples" else (cap,)
+            out_key = torch.empty(shape, dtype=skey.dtype, device=self.device)
+            out_pay = torch.empty(cap, dtype=torch.int64, device=self.device) if spay is not None else None
+            out_row = torch.empty(cap, dtype=skey.dtype, device=self.device) if with_rows else None
+            m = int(self.apply_into(skey, spay, kind, out_key, out_pay, out_row, stream=stream).item())
+            if m <= cap:
+                outs = [o[:m] for o in (out_key, out_pay, out_row) if o is not None]
+                return outs[0] if len(outs) == 1 else tuple(outs)
+            cap = m
+        raise RuntimeError("filter output did not fit after resizing")
+
+    def count(self, skey, kind="pass", stream=None, sync=True):
+        """How many rows of S pass ('pass') / fail ('reject')."""
+        cnt = self.apply_into(skey, kind=kind, stream=stream)
+        return int(cnt.item()) if sync else cnt
 
 
 class HashJoin:
@@ -1058,6 +1211,47 @@ class HashJoin:
                 return out_r[:m], out_s[:m]
             cap = m
         raise RuntimeError("join output did not fit after resizing")
+
+    # ---- key filter (hj.h "Key filter"): opt-in, nothing here turns it on by itself
+    FILTERED_JOIN_KINDS = ("inner", "semi", "anti")
+
+    def key_filter(self, n_keys, bits_per_key=16):
+        """A KeyFilter for n_keys build keys on this context's device (not yet cleared)."""
+        return KeyFilter(n_keys, bits_per_key, device=self.device.index)
+
+    def filtered_join(self, rkey, rpay, skey, spay=None, how="inner", bits_per_key=16, stream=None, **kw):
+        """join / semi_join / anti_join behind a key filter built from rkey:
+        the S rows whose key fails the filter never reach the build and probe.
+        how = 'inner' -> join(R, PASS rows), 'semi' -> semi_join(R, PASS rows),
+        'anti' -> the REJECT rows plus anti_join(R, PASS rows); the result
+        multisets equal the unfiltered calls'.  int64 keys; spay None is the
+        row index.  Takes the underlying method's keyword arguments (capacity,
+        with_keys).  last_filtered = (S rows in, S rows kept)."""
+        if how not in self.FILTERED_JOIN_KINDS:
+            raise ValueError("how must be one of " + ", ".join(self.FILTERED_JOIN_KINDS))
+        if rkey.dtype != torch.int64 or skey.dtype != torch.int64 or rkey.dim() != 1 or skey.dim() != 1:
+            raise TypeError("filtered_join takes 1-D int64 key columns")
+        _need_cuda(rkey, rpay, skey, spay)
+        if spay is None:
+            spay = torch.arange(skey.numel(), dtype=torch.int64, device=self.device)
+        f = self.key_filter(rkey.numel(), bits_per_key)
+        try:
+            f.clear(stream=stream)
+            f.insert(rkey, stream=stream)
+            pk, pp = f.apply(skey, spay, "pass", stream=stream)
+            self.last_filtered = (skey.numel(), pk.numel())
+            if how == "inner":
+                return self.join(rkey, rpay, pk, pp, stream=stream, **kw)
+            if how == "semi":
+                return self.semi_join(rkey, pk, pp, rpay, stream=stream, **kw)
+            rk, rp = f.apply(skey, spay, "reject", stream=stream)
+        finally:
+            f.close()
+        with_keys = kw.get("with_keys", False)
+        a = self.anti_join(rkey, pk, pp, rpay, stream=stream, **kw)
+        if with_keys:
+            return torch.cat([rk, a[0]]), torch.cat([rp, a[1]])
+        return torch.cat([rp, a])
 
     # ---- composite keys (hj.h "Composite keys"): up to four key columns, packed exactly into one int64 key
     JOIN_ON_KINDS = ("inner", "semi", "anti", "left", "right", "full")
