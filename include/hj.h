@@ -132,7 +132,7 @@ int hj_ctx_last_timing_ex(hj_ctx *ctx, float ms[8]);
 int hj_ctx_timing_accumulate(hj_ctx *ctx, int enable);
 int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 /* RADIX: the join kernel of the last probe, whichever entry point ran it
- * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_probe_full_*, hj_dev_count_*, hj_dev_exists_*, hj_dev_lookup_*, hj_dev_expand_*, and after a routed build
+ * (hj_dev_probe_*, hj_dev_probe_outer_*, hj_dev_probe_full_*, hj_dev_count_*, hj_dev_exists_*, hj_dev_lookup_*, hj_dev_asof_*, hj_dev_expand_*, and after a routed build
  * hj_dev_probe_routed_i64 too).  A pure function of the row
  * width, the probe / build size ratio (>= 8: the probe-heavy shape) and the
  * build side's repeated keys, sampled at build time over up to 64 partitions
@@ -158,6 +158,8 @@ int hj_ctx_timing_totals(hj_ctx *ctx, float ms[8], long long *sets);
 #define HJ_JOIN_KERNEL_AGGREGATE 9
 /* k_join_expand: the last probe was a radix expand (hj_dev_expand_*) */
 #define HJ_JOIN_KERNEL_EXPAND 10
+/* k_join_asof: the last probe was a radix as-of probe (hj_dev_asof_*) */
+#define HJ_JOIN_KERNEL_ASOF 11   /* k_join_asof */
 int hj_ctx_join_kernel(hj_ctx *ctx);
 
 /* ------------------------------------------------------------ device phases
@@ -272,6 +274,64 @@ int hj_dev_lookup_i64(hj_ctx *ctx, const int64_t *skey, int64_t n, int64_t null_
                       int64_t *out_r, int32_t *out_cnt, uint64_t *d_count, void *stream);
 int hj_dev_lookup_i32(hj_ctx *ctx, const int32_t *skey, int64_t n, int32_t null_row,
                       int32_t *out_r, int32_t *out_cnt, uint64_t *d_count, void *stream);
+
+/* As-of probe (pandas merge_asof(by=key, on=time), the ASOF JOIN of DuckDB,
+ * ClickHouse and kdb+, "the last quote before each trade") over the table an
+ * ordinary hj_dev_build_* left: per probe row, among the build rows with its
+ * key, the one whose payload is the nearest at or before (or at or after) the
+ * row's own bound.  For the built relation R and the probe relation S of n
+ * rows, with j the row's position in S as passed in, let
+ * P(j) = { R.pay[i] : R.key[i] == S.key[j] }; then
+ *   HJ_ASOF_BACKWARD: out_r[j] = max { p in P(j) : p <= sbound[j] };
+ *   HJ_ASOF_FORWARD:  out_r[j] = min { p in P(j) : p >= sbound[j] };
+ *   | HJ_ASOF_STRICT: p < sbound[j]  /  p > sbound[j]  instead.
+ * Payloads and bounds are compared as signed int64.  i32: the payload is R's
+ * row id (hj_dev_build_i32's row_base + row), zero-extended, and the bound is
+ * sign-extended -- "the last R row with this key at or before row b".
+ * A row without a candidate gets null_pay (i32: null_row), written verbatim.
+ * Validity comes from the set being empty, never from a sentinel: INT64_MIN and
+ * INT64_MAX are payloads and bounds like any other, and the strict kinds are
+ * true strict compares, not bound -+ 1 (strict backward with bound INT64_MIN
+ * and strict forward with bound INT64_MAX have no candidate).
+ * Every position 0 .. n-1 of out_r is written exactly once and nothing at or
+ * past n; out_r is required when n > 0.  d_count = the number of S rows that
+ * got a candidate, zeroed by the call; bit 63 as above (no as-of path sets it).
+ * The result is a function of the data alone -- a max or a min of a set -- and
+ * bit-equal across strategies, kernels and runs; repeated build keys need no
+ * tie rule.  INT64_MIN is a key like any other, on both sides.  R empty: every
+ * row is null_pay and d_count = 0.  S empty: nothing is written.
+ * Errors in hj_dev_lookup_*'s order: a null context (HJ_ERR_ARG); a kind
+ * outside {0, 1, 2, 3} (HJ_ERR_ARG); no build of that layout (HJ_ERR_STATE); a
+ * null count pointer, a null skey or sbound with n > 0, a null out_r with
+ * n > 0, n < 0 (HJ_ERR_ARG); for i32, n > INT32_MAX (HJ_ERR_ARG).
+ * Asynchronous on the stream, kernels ONLY once hj_ctx_reserve /
+ * hj_ctx_reserve_probe sized the workspace (the counter is zeroed by a kernel
+ * on both strategies, not by a memset): capturable as a linear graph, a build
+ * in front of the probe included.  The strategy is chosen exactly as for
+ * hj_dev_probe_* (the AUTO dual build included) and hj_ctx_strategy_used
+ * reports it; the probe timing works as for hj_dev_lookup_* (RADIX: [4] S's
+ * one partition, whose rows carry their index through the passes, [5] the
+ * rest) and hj_ctx_join_kernel returns HJ_JOIN_KERNEL_ASOF after a radix one.
+ * Nothing the build left is written -- not the table, R's partition, the side
+ * list, the "build keys repeat" flag or the mark bitmap: as-of, lookup, expand,
+ * group, inner, semi, anti, outer, build and full probes of one build may
+ * follow each other in any order and each returns what it returned before, and
+ * hj_ctx_build_has_duplicates keeps its answer.  Valid after
+ * hj_dev_build_routed_i64 too, over unrouted rows.
+ * Cost: the lookup's, plus one read of the bound per row
+ * -- contiguous beside the key on GLOBAL, scattered on RADIX, which joins S in
+ * hash order.  Every copy of a build key sits in a slot of its own of one probe
+ * chain that each probe of the key walks whole: fine at a handful of versions
+ * per key, the expand probe's weak spot at thousands.
+ * There is no tuples form and no routed bin-range form, for the reasons the
+ * lookup gives. */
+#define HJ_ASOF_BACKWARD 0   /* out_r[j] = max { p in P(j) : p <= sbound[j] } */
+#define HJ_ASOF_FORWARD  1   /* out_r[j] = min { p in P(j) : p >= sbound[j] } */
+#define HJ_ASOF_STRICT   2   /* flag, ORed into the kind: p < sbound[j]  /  p > sbound[j] */
+int hj_dev_asof_i64(hj_ctx *ctx, int kind, const int64_t *skey, const int64_t *sbound, int64_t n, int64_t null_pay,
+                    int64_t *out_r, uint64_t *d_count, void *stream);
+int hj_dev_asof_i32(hj_ctx *ctx, int kind, const int32_t *skey, const int32_t *sbound, int64_t n, int32_t null_row,
+                    int32_t *out_r, uint64_t *d_count, void *stream);
 
 /* Expand probe (the join as a CSR: merge(how="inner" | "left") in the left
  * frame's order, a ragged id -> rows lookup, neighbour lists, an inverted

@@ -221,6 +221,7 @@ struct hj_ctx {
     bool join_ran = false, join_wide = false, join_stream = false;
     bool exists_ran = false;   // the last probe was a radix semi- / anti-join (HJ_JOIN_KERNEL_EXISTS)
     bool lookup_ran = false;   // the last probe was a radix lookup (HJ_JOIN_KERNEL_LOOKUP)
+    bool asof_ran = false;     // the last probe was a radix as-of probe (HJ_JOIN_KERNEL_ASOF)
     bool group_ran = false;    // the last probe was a radix group probe (HJ_JOIN_KERNEL_GROUP)
     bool expand_ran = false;   // the last probe was a radix expand (HJ_JOIN_KERNEL_EXPAND)
     bool agg_ran = false;      // an aggregate (hj_dev_aggregate_*) ran since the last build: layout < 0, and used,
@@ -590,7 +591,7 @@ int begin_build(hj_ctx *c, int layout, int64_t n, int used, bool dual, bool rout
     c->routed = routed;
     c->plan = plan;
     c->probe_used = -1;
-    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = c->expand_ran = c->agg_ran = c->dup_checked = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = c->asof_ran = c->group_ran = c->expand_ran = c->agg_ran = c->dup_checked = false;
     // (hj_count_*'s kept table is gone; a host join's own build keeps the
     // EXACT copies it has just taken of its inputs)
     if (c->host_building) c->memo.valid = false;
@@ -651,7 +652,7 @@ int do_build(hj_ctx *c, int layout, const hj::SrcDev &src, hipStream_t st) {
 
 // One probe of the current build, after the entry point's argument checks.
 enum ProbeKind { kProbeInner, kProbeCount, kProbeSemi, kProbeAnti, kProbeOuter, kProbeBuild, kProbeFull, kProbeLookup,
-                 kProbeGroup, kProbeExpand };
+                 kProbeGroup, kProbeExpand, kProbeAsof };
 struct ProbeReq {
     RadixSrc in;       // S; routed: bins [bin0, bin0 + in.nbins) of the build's first pass
     int bin0 = 0;
@@ -664,6 +665,8 @@ struct ProbeReq {
     hj::GroupOut grp{};                // group: the result columns, the kind and the null value (its counter is out.counter)
     long long *out_off = nullptr;      // expand: the n + 1 offsets (out.r the values, may be null with out.cap == 0)
     bool expand_outer = false;         // expand: a row without a partner gets one null_pay entry
+    const void *bound = nullptr;       // asof: S's bound column (int64 / int32 by layout; out.r the per-row result)
+    int asof_kind = 0;                 // asof: HJ_ASOF_* direction | strict
 };
 
 // The global-table group probe's accumulators for a table of 2^bits slots (and
@@ -692,11 +695,11 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
     const bool r_nulls = q.kind == kProbeBuild || q.kind == kProbeFull;
     const bool radix = c->used == HJ_STRATEGY_RADIX || (c->dual && src.n >= kRadixProbeMinRows);
     c->probe_used = radix ? HJ_STRATEGY_RADIX : HJ_STRATEGY_GLOBAL;
-    c->join_ran = c->exists_ran = c->lookup_ran = c->group_ran = c->expand_ran = false;
+    c->join_ran = c->exists_ran = c->lookup_ran = c->asof_ran = c->group_ran = c->expand_ran = false;
     if (q.kind == kProbeExpand) HJ_TRY(ensure_expand(c, src.n));
     if (!radix) {
-        // (expand: the scan's last launch stores the counter, nothing reads it before)
-        if (q.kind != kProbeExpand) HJ_HIP(hipMemsetAsync(q.out.counter, 0, sizeof(uint64_t), st));
+        // (expand: the scan's last launch stores the counter, nothing reads it before; asof: its launcher zeroes it by a kernel)
+        if (q.kind != kProbeExpand && q.kind != kProbeAsof) HJ_HIP(hipMemsetAsync(q.out.counter, 0, sizeof(uint64_t), st));
         record(c, kEvProbe0, st);
         if (q.kind == kProbeExpand) {
             // counts (the lookup's kernel without its payload column), their scan, the fill
@@ -710,6 +713,8 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
             HJ_HIP(hj::launch_probe_exists(table_dev(c), c->layout, src, q.out, q.kind == kProbeAnti, st));
         } else if (q.kind == kProbeLookup) {
             HJ_HIP(hj::launch_probe_lookup(table_dev(c), c->layout, src, q.out, q.out_cnt, q.null_pay, st));
+        } else if (q.kind == kProbeAsof) {
+            HJ_HIP(hj::launch_probe_asof(table_dev(c), c->layout, q.asof_kind, src, q.bound, q.out, q.null_pay, st));
         } else if (q.kind == kProbeGroup) {
             HJ_TRY(ensure_group_acc(c, c->bits, c->layout, q.grp.sum, q.grp.mn, q.grp.mx));
             const hj::GroupAcc acc{c->acc_cnt.p, q.grp.sum ? (unsigned long long *)c->acc_sum.p : nullptr,
@@ -740,7 +745,7 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
         HJ_TRY(ensure_radix_scratch(c, c->sset, src.n, wide, c->plan, q.in.nsrc));
         trace("probe: workspace", st, (long long)c->sset.max_buckets);
         record(c, kEvProbe0, st);
-        if ((q.kind == kProbeLookup || q.kind == kProbeExpand || (q.kind == kProbeGroup && !src.pay && src.form == hj::kCols64)) && wide) {
+        if ((q.kind == kProbeLookup || q.kind == kProbeExpand || q.kind == kProbeAsof || (q.kind == kProbeGroup && !src.pay && src.form == hj::kCols64)) && wide) {
             // S's rows carry their index through the passes: the key column alone is read
             // (a group probe without a value column: no aggregate reads the payload)
             RadixSrc in = q.in;
@@ -767,6 +772,10 @@ int run_probe(hj_ctx *c, const ProbeReq &q, hipStream_t st) {
             HJ_RADIX(c, st, hj::radix_lookup(wide, q.null_pay, src.n, c->plan, radix_work(c), r, bucket_set(c->sset),
                                              q.out, q.out_cnt, st));
             c->lookup_ran = true;
+        } else if (q.kind == kProbeAsof) {
+            HJ_RADIX(c, st, hj::radix_asof(wide, q.asof_kind, q.null_pay, src.n, q.bound, c->plan, radix_work(c), r,
+                                           bucket_set(c->sset), q.out, st));
+            c->asof_ran = true;
         } else if (q.kind == kProbeExpand) {
             HJ_RADIX(c, st, hj::radix_expand(wide, q.expand_outer, q.null_pay, src.n, c->plan, radix_work(c), r,
                                              bucket_set(c->sset), q.out, (int *)c->exp_cnt.p, q.out_off,
@@ -853,6 +862,30 @@ int do_lookup(hj_ctx *c, int layout, const hj::SrcDev &src, unsigned long long n
     q.out_cnt = out_cnt;
     q.kind = kProbeLookup;
     q.null_pay = null_pay;
+    return run_probe(c, q, st);
+}
+
+// As-of probe (hj_dev_asof_*): per S row the nearest R payload at or before
+// (after) the row's bound.  do_lookup's order of checks behind the kind's.
+// Reads what do_lookup reads.
+int do_asof(hj_ctx *c, int layout, int kind, const hj::SrcDev &src, const void *sbound, unsigned long long null_pay,
+            void *out_r, uint64_t *d_count, hipStream_t st) {
+    if (!c) HJ_FAIL(HJ_ERR_ARG, "null context");
+    if (kind < 0 || kind > (HJ_ASOF_FORWARD | HJ_ASOF_STRICT))
+        HJ_FAIL(HJ_ERR_ARG, "kind must be HJ_ASOF_BACKWARD or HJ_ASOF_FORWARD, with or without HJ_ASOF_STRICT");
+    if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, "probe without a matching build");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (src.n < 0 || (src.n > 0 && !src.key)) HJ_FAIL(HJ_ERR_ARG, "bad probe relation");
+    if (src.n > 0 && !sbound) HJ_FAIL(HJ_ERR_ARG, "null bound column");
+    if (src.n > 0 && !out_r) HJ_FAIL(HJ_ERR_ARG, "null output");
+    if (layout == kNarrow && src.n > 0x7fffffffll) HJ_FAIL(HJ_ERR_ARG, "i32 row ids: probe side must have < 2^31 rows");
+    ProbeReq q;
+    q.in.src = src;
+    q.out = hj::OutDev{out_r, nullptr, src.n, (unsigned long long *)d_count};
+    q.kind = kProbeAsof;
+    q.null_pay = null_pay;
+    q.bound = sbound;
+    q.asof_kind = kind;
     return run_probe(c, q, st);
 }
 
@@ -1837,6 +1870,7 @@ int hj_ctx_join_kernel(hj_ctx *c) {
     if (c->agg_ran) return c->used == HJ_STRATEGY_RADIX ? HJ_JOIN_KERNEL_AGGREGATE : 0;
     if (c->exists_ran && c->layout >= 0) return HJ_JOIN_KERNEL_EXISTS;
     if (c->lookup_ran && c->layout >= 0) return HJ_JOIN_KERNEL_LOOKUP;
+    if (c->asof_ran && c->layout >= 0) return HJ_JOIN_KERNEL_ASOF;
     if (c->group_ran && c->layout >= 0) return HJ_JOIN_KERNEL_GROUP;
     if (c->expand_ran && c->layout >= 0) return HJ_JOIN_KERNEL_EXPAND;
     if (!c->join_ran || c->layout < 0) return 0;
@@ -2042,6 +2076,18 @@ int hj_dev_lookup_i32(hj_ctx *c, const int32_t *skey, int64_t n, int32_t null_ro
                       uint64_t *d_count, void *stream) {
     return do_lookup(c, kNarrow, src_col32(skey, n, 0), (unsigned long long)(long long)null_row, out_r, out_cnt,
                      d_count, (hipStream_t)stream);
+}
+
+int hj_dev_asof_i64(hj_ctx *c, int kind, const int64_t *skey, const int64_t *sbound, int64_t n, int64_t null_pay,
+                    int64_t *out_r, uint64_t *d_count, void *stream) {
+    // (the key column stands in for the payload column, which no as-of kernel reads)
+    return do_asof(c, kWide, kind, src_cols64(skey, skey, n), sbound, (unsigned long long)null_pay, out_r, d_count,
+                   (hipStream_t)stream);
+}
+int hj_dev_asof_i32(hj_ctx *c, int kind, const int32_t *skey, const int32_t *sbound, int64_t n, int32_t null_row,
+                    int32_t *out_r, uint64_t *d_count, void *stream) {
+    return do_asof(c, kNarrow, kind, src_col32(skey, n, 0), sbound, (unsigned long long)(long long)null_row, out_r,
+                   d_count, (hipStream_t)stream);
 }
 
 int hj_dev_expand_i64(hj_ctx *c, int kind, const int64_t *skey, int64_t n, int64_t null_pay, int64_t *out_off,

@@ -134,6 +134,37 @@ hipError_t launch_probe_exists(const TableDev &t, int layout, const SrcDev &src,
 // One launch; reads meta[0..1], writes no build state.
 hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src, const OutDev &out, int *cnt,
                                unsigned long long null_pay, hipStream_t st);
+// The as-of probes' order (hj.h "As-of probe"; KIND = HJ_ASOF_* direction |
+// strict, a template argument of both kernels): payloads and bounds compare as
+// signed int64.  A running best starts at asof_start (the identity of the
+// kind's max / min) beside a found bit that alone says whether the set was
+// empty: INT64_MIN and INT64_MAX are payloads like any other.
+template <int KIND>
+__device__ __forceinline__ bool asof_admits(long long p, long long b) {
+    if constexpr (KIND == 0) return p <= b;        // backward
+    else if constexpr (KIND == 1) return p >= b;   // forward
+    else if constexpr (KIND == 2) return p < b;    // backward, strict
+    else return p > b;                             // forward, strict
+}
+template <int KIND>
+constexpr long long asof_start = (KIND & 1) ? 0x7fffffffffffffffll : -0x7fffffffffffffffll - 1;
+// folds payload p into `best` under bound b; true if p was a candidate
+template <int KIND>
+__device__ __forceinline__ bool asof_fold(long long p, long long b, long long &best) {
+    if (!asof_admits<KIND>(p, b)) return false;
+    if constexpr (KIND & 1) best = p < best ? p : best;
+    else best = p > best ? p : best;
+    return true;
+}
+// as-of probe over the global table (k_probe_asof): for S row j, out.r[j] =
+// the largest payload <= bound[j] (kind HJ_ASOF_*: or the smallest >= it,
+// strictly or not) of the R rows with its key, or null_pay; out.counter += the
+// S rows with a candidate.  src as launch_probe_lookup's; bound: S's own
+// element width (int64 / int32, sign-extended).  Two launches, the first
+// zeroing out.counter (kernels only, n == 0 too); reads meta[0..1] and the side
+// list, writes no build state.
+hipError_t launch_probe_asof(const TableDev &t, int layout, int kind, const SrcDev &src, const void *bound,
+                             const OutDev &out, unsigned long long null_pay, hipStream_t st);
 // The expand probe's scan (hj_kernels.hip; both strategies): cnt[0..n) are the
 // per-row partner counts (launch_probe_lookup's / radix_lookup's cnt column),
 // width = cnt, or max(1, cnt) when outer.  off[j] = the widths before row j,
@@ -313,6 +344,16 @@ hipError_t radix_exists(bool wide, bool anti, const RadixPlan &pl, const RadixWo
 // r, writes neither it nor the repeat flag.
 hipError_t radix_lookup(bool wide, unsigned long long null_pay, long long n, const RadixPlan &pl, const RadixWork &ws,
                         const BucketSet &r, const BucketSet &s, const OutDev &out, int *cnt, hipStream_t st);
+// As-of probe over the partitioned relations (k_join_asof): s partitioned as
+// for radix_lookup (each row carries its index in S), n = |S|, bound the S
+// column of n bounds in input order (int64 / int32 by width).  For S row j,
+// out.r[j] = the best payload under kind (HJ_ASOF_*) and bound[j] among the R
+// rows with its key, or null_pay; out.counter = the S rows with a candidate.
+// radix_lookup's work map: every row index is written exactly once, nothing
+// needs a prefill.  Reads r, writes neither it nor the repeat flag.
+hipError_t radix_asof(bool wide, int kind, unsigned long long null_pay, long long n, const void *bound,
+                      const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
+                      const OutDev &out, hipStream_t st);
 // Expand probe over the partitioned relations: s partitioned as for
 // radix_lookup (each row carries its index in S), n = |S|.  One work map
 // (radix_lookup's: every non-empty S partition is an item) serves both

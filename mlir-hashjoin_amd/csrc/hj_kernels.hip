@@ -9,7 +9,7 @@
 //                                          reads, ballot-compacted output,
 //                                          one global cursor add per block
 // plus the exists probes (k_probe_exists), the positional lookup probe
-// (k_probe_lookup), the expand probe's scan and global-table fill
+// (k_probe_lookup), the as-of probe (k_probe_asof), the expand probe's scan and global-table fill
 // (k_expand_sums, k_expand_scan_sums, k_expand_offsets, k_probe_expand),
 // the outer probe (k_probe_outer),
 // the build-side outer stages (k_probe_mark, k_emit_unmatched),
@@ -23,7 +23,7 @@
 // independent, no warp-32 idioms.  Integer/byte work: no MFMA.
 //
 // Written once, used by several kernels / launchers:
-//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists, k_probe_lookup, k_probe_expand, k_probe_outer)
+//   TableView        the table in global memory or staged in LDS (k_probe, k_probe_exists, k_probe_lookup, k_probe_asof, k_probe_expand, k_probe_outer)
 //   wave_incl_add    every wave prefix sum (hj_internal.h: DPP, no LDS round trips)
 //   with_layout_form the (layout, form) -> template-argument dispatch of the launchers
 //   probe_grid       the tile probes' grid and LDS bytes
@@ -825,6 +825,142 @@ __global__ __launch_bounds__(kBlock) void k_probe_lookup(TableDev t, SrcDev src,
             if (orr) orr[row] = (out_t)(C[i] ? RP[i] : (long long)null_pay);
             if (cnt) cnt[row] = (int)C[i];
             hits += C[i] ? 1u : 0u;
+        }
+    }
+    const unsigned x = wave_incl_add(hits);
+    if (lane == 63) s_hits[wv] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sum = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sum += s_hits[w];
+        if (sum) atomicAdd(out.counter, sum);
+    }
+}
+
+// ------------------------------------------------------------------ as-of probe
+// As-of probe: for S row j, out.r[j] = the largest payload <= bound[j] (KIND:
+// the smallest >= it; strictly or not -- asof_admits) among the R rows with its
+// key, or null_pay.  k_probe_lookup's shape -- 2048-row tiles over S's keys
+// alone, every row's first slot load issued before any is resolved, TableView,
+// stores at the row's own index, LDS: the next tile loaded ahead -- with one
+// more input column, the bounds, read contiguously beside the keys in S's own
+// element width (int64, or int32 sign-extended).  The chain walk keeps the
+// running best of the payloads the bound admits and a found bit (the best
+// alone says nothing: INT64_MIN and INT64_MAX are payloads); it ends at the
+// first equal key when the build's repeat flag (meta[1]) is clear, whether or
+// not that one qualifies, else it goes on to EMPTY.  A wide INT64_MIN probe
+// key answers from the side list, which holds payloads and is scanned by each
+// such row itself, every row having its own bound (rare, and all such rows'
+// partners sit in that one list).  KIND is a template argument: the walk holds
+// one compare and one select.  The rows with a candidate are summed per lane
+// and added to out.counter once per workgroup, after its last tile.
+// out.counter is zeroed by k_counter_clear in front, not by a memset: as a node
+// of a captured build + probe sequence the one-word memset was replayed with a
+// stale pattern (the counter came back as 0x2929292929292929 + the count on an
+// MI355X; radix_state_clear met the same with its fill).  A kernel's arguments
+// travel in its node.
+__global__ __launch_bounds__(64) void k_counter_clear(unsigned long long *counter) {
+    if (threadIdx.x == 0) *counter = 0ull;
+}
+template <int L>
+__device__ __forceinline__ long long load_bound(const void *b, long long row) {
+    if constexpr (L == kWide) return ((const long long *)b)[row];
+    else return (long long)((const int *)b)[row];
+}
+template <int L, int FORM, bool LDS, int KIND>
+__global__ __launch_bounds__(kBlock) void k_probe_asof(TableDev t, SrcDev src, const void *bound, OutDev out,
+                                                       unsigned long long null_pay) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    constexpr int NW = kBlock / 64;
+    __shared__ unsigned s_hits[NW];
+    extern __shared__ ulonglong2 s_tab[];
+
+    const TableView<L, LDS> tab(t, s_tab);
+    const bool unique = (__hip_atomic_load(&t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull);
+    const unsigned long long side_n = L == kWide ? t.meta[0] : 0ull;   // INT64_MIN build rows
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
+    out_t *orr = (out_t *)out.r;
+    unsigned hits = 0;
+    // the keys and bounds of tile q (bits of the result: the rows the source holds)
+    auto load_rows = [&](unsigned long long q, unsigned long long (&K)[kProbeItems], long long (&B)[kProbeItems]) {
+        unsigned valid = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            const long long row = (long long)q * kProbeTile + (long long)i * kBlock + threadIdx.x;
+            K[i] = 0ull;
+            B[i] = 0ll;
+            if (row < src.n) {
+                valid |= 1u << i;
+                K[i] = load_key<FORM>(src, row);
+                B[i] = load_bound<L>(bound, row);
+            }
+        }
+        return valid;
+    };
+    // (LDS: the next tile's rows are loaded ahead, as k_probe_lookup's keys are)
+    [[maybe_unused]] unsigned long long KN[kProbeItems];
+    [[maybe_unused]] long long BN[kProbeItems];
+    [[maybe_unused]] unsigned valid_n = 0;
+    if constexpr (LDS) {
+        if (blockIdx.x < nt) valid_n = load_rows(blockIdx.x, KN, BN);
+    }
+    for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
+        unsigned long long K[kProbeItems], H[kProbeItems];
+        long long B[kProbeItems], RP[kProbeItems];
+        unsigned valid, walk = 0, found = 0;
+        if constexpr (LDS) {
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i) {
+                K[i] = KN[i];
+                B[i] = BN[i];
+            }
+            valid = valid_n;
+            if (q + gridDim.x < nt) valid_n = load_rows(q + gridDim.x, KN, BN);
+        } else {
+            valid = load_rows(q, K, B);
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            RP[i] = asof_start<KIND>;
+            if (!((valid >> i) & 1u)) continue;
+            if (LY::null_key(K[i])) {
+                for (unsigned long long j = 0; j < side_n; ++j)
+                    if (asof_fold<KIND>((long long)t.side[j], B[i], RP[i])) found |= 1u << i;
+            } else {
+                walk |= 1u << i;
+            }
+        }
+        slot_t S[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            H[i] = slot_of(K[i], t.shift);
+            if ((walk >> i) & 1u) S[i] = tab.at(H[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((walk >> i) & 1u)) continue;
+            slot_t sv = S[i];
+            unsigned long long hh = H[i];
+            while (!LY::empty(sv)) {
+                if (LY::key(sv) == K[i]) {
+                    if (asof_fold<KIND>((long long)LY::pay(sv), B[i], RP[i])) found |= 1u << i;
+                    if (unique) break;
+                }
+                hh = (hh + 1) & t.mask;
+                sv = tab.at(hh);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((valid >> i) & 1u)) continue;
+            const long long row = (long long)q * kProbeTile + (long long)i * kBlock + threadIdx.x;
+            const bool f = (found >> i) & 1u;
+            orr[row] = (out_t)(f ? RP[i] : (long long)null_pay);
+            hits += f ? 1u : 0u;
         }
     }
     const unsigned x = wave_incl_add(hits);
@@ -2314,6 +2450,32 @@ hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src,
     };
     if (layout == kWide && src.form == kCols64) return launch(int_c<kWide>{}, int_c<kCols64>{});
     if (layout == kNarrow && src.form == kCol32) return launch(int_c<kNarrow>{}, int_c<kCol32>{});
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_probe_asof(const TableDev &t, int layout, int kind, const SrcDev &src, const void *bound,
+                             const OutDev &out, unsigned long long null_pay, hipStream_t st) {
+    hipLaunchKernelGGL(k_counter_clear, dim3(1), dim3(64), 0, st, out.counter);
+    if (src.n <= 0) return hipGetLastError();
+    const ProbeGrid pg = probe_grid(t, layout, src.n);
+    // (a key column only, as the lookup's; one instantiation per kind: the walk holds no kind branch)
+    auto launch = [&](auto l, auto f, auto k_) {
+        constexpr int L = decltype(l)::value, F = decltype(f)::value, K = decltype(k_)::value;
+        const auto k = pg.lds ? k_probe_asof<L, F, true, K> : k_probe_asof<L, F, false, K>;
+        hipLaunchKernelGGL(k, dim3(pg.grid), dim3(kBlock), pg.lds ? pg.tbytes : 0, st, t, src, bound, out, null_pay);
+        return hipGetLastError();
+    };
+    auto by_kind = [&](auto l, auto f) {
+        switch (kind) {
+        case 0: return launch(l, f, int_c<0>{});
+        case 1: return launch(l, f, int_c<1>{});
+        case 2: return launch(l, f, int_c<2>{});
+        case 3: return launch(l, f, int_c<3>{});
+        default: return hipErrorInvalidValue;
+        }
+    };
+    if (layout == kWide && src.form == kCols64) return by_kind(int_c<kWide>{}, int_c<kCols64>{});
+    if (layout == kNarrow && src.form == kCol32) return by_kind(int_c<kNarrow>{}, int_c<kCol32>{});
     return hipErrorInvalidValue;
 }
 

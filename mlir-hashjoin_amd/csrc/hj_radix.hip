@@ -3062,7 +3062,7 @@ __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
 }
 
 // --------------------------------------------------------------- rounded-table kernels: the shared skeleton
-// k_join_exists, k_join_lookup, k_join_expand and k_join_group share one
+// k_join_exists, k_join_lookup, k_join_expand, k_join_asof and k_join_group share one
 // structure over the work items (work_map); each kernel's header says only
 // what is its own.  An item names a partition's TABLE side (JoinArgs' r and
 // r_runs: the rows whose keys go into an LDS table) and a chunk of its EMIT
@@ -3091,14 +3091,15 @@ __global__ __launch_bounds__(NT, 4) void k_join_grp(JoinArgs a) {
 //    walks linearly.
 // The loop nest (item, sub-chunk, round) is written out in each kernel; what is
 // inside it comes from here:
-//   RoundShape        the constants and the asserts that tie them      all four
-//   load_run_rows     a sub-chunk's or a round's rows, one per lane    all four
-//   RoundTable::clear        the key slots to EMPTY                    all four
+//   RoundShape        the constants and the asserts that tie them      all five
+//   load_run_rows     a sub-chunk's or a round's rows, one per lane    all five
+//   RoundTable::clear        the key slots to EMPTY                    all five
 //   RoundTable::insert_once  CAS to EMPTY or the key itself            exists, lookup, group
-//   RoundTable::probe_first  first slots, INT64_MIN rows set apart     all four
+//   RoundTable::probe_first  first slots, INT64_MIN rows set apart     all five
 //   RoundTable::find_key     the walk to EMPTY or the key              exists, lookup, group
 //   compact_emit      ballots, one scan, ONE add on the output cursor  exists, group
-// (k_join_expand claims a slot per ROW and walks to EMPTY: its own two loops.)
+// (k_join_expand and k_join_asof claim a slot per ROW and walk to EMPTY: each
+// its own two loops -- expand stores every partner, asof keeps the best one.)
 // All are __forceinline__: the tables reach them as pointers, and only inlined
 // do those stay LDS addresses (ds_* accesses and LDS atomics, not flat ones).
 constexpr int kExistsTableLog = 13;
@@ -3629,6 +3630,161 @@ __global__ __launch_bounds__(NT, WPS) void k_join_expand(JoinArgs a, const long 
             }
         }
     }
+}
+
+// --------------------------------------------------------------- as-of join
+// The as-of probe over the work items (radix_asof): for each emit (S) row, the
+// largest table (R) payload <= the row's bound among the rows with its key
+// (KIND, HJ_ASOF_*: the smallest >= it; strictly or not -- asof_admits), stored
+// at the row index the S row carries as its payload.  The table is
+// k_join_expand's, not k_join_lookup's: that one keeps one slot per key with a
+// minimum reduced at build time, and here the bound differs per probe row, so
+// every build row of a round claims a slot of its own (a CAS of EMPTY only,
+// linear probing past equal keys; tpay[h] is written by the row that claimed
+// tkey[h]).  int64 rows 64 + 64 = 128 KiB, i32 rows 64 + 32 = 96 KiB: one
+// workgroup per CU.  The work map is radix_lookup's: every non-empty S
+// partition is an item, so this kernel writes every row, the rows of items
+// without build rows among them (null_pay), and nothing prefills.
+// Per sub-chunk a lane reads its rows' bounds from sbound[row] once (guarded
+// by n, as k_join_expand guards offs[row]; the bound column's element width is
+// S's: int64, or int32 sign-extended) -- one scattered load per row, the only
+// traffic the lookup does not have -- and keeps best[SI] and a found bit in
+// registers across the build rounds; a probing lane walks from its key's slot
+// to EMPTY and folds the payload of each equal key under its own bound
+// (asof_fold: payloads compare as signed int64, i32 row ids zero-extended).
+// After the last round it stores best or null_pay at out_r[row] with plain
+// stores (kNtLookupSt).  The found bit alone says whether a row had a
+// candidate: INT64_MIN and INT64_MAX are payloads like any other.
+// INT64_MIN build keys (wide): k_join_expand's list in tpay[0 .. nn), made
+// before a round's table; the sub-chunk's INT64_MIN probe rows fold its words
+// under their own bounds, then the table is cleared and filled, and an item
+// that has shown such a row rebuilds for every sub-chunk (renull).
+// The rows with a candidate are summed per lane and added to the counter once
+// per wave when the workgroup has run out of items.  KIND is a template
+// argument: the walk holds one compare and one select, no kind branch.
+// Cost: a build key with c copies is a chain of c slots that every insert and
+// every probe of it walks, as in k_join_expand.
+constexpr int kAsofNT = kExpandNT, kAsofSI = kExpandSI, kAsofWPS = kExpandWPS;
+template <bool WIDE, int NT, int SI, int WPS, int KIND = 0>
+__global__ __launch_bounds__(NT, WPS) void k_join_asof(JoinArgs a, const void *sbound, u64 null_pay, u64 n) {
+    typedef Row<WIDE> R;
+    typedef typename R::T T;
+    typedef typename std::conditional<WIDE, u64, unsigned>::type PT;   // output element, LDS payload word
+    typedef RoundShape<kExistsTableLog, NT, SI, true> SH;
+    typedef RoundTable<WIDE, SH> TB;
+    constexpr int TS = SH::TS, NW = SH::NW;
+    constexpr unsigned kMask = SH::kMask;
+    constexpr u64 kEmpty = TB::kEmpty;
+    static_assert(SH::RCAP < TS, "every row of a round has a slot and the walks end at an EMPTY one");
+    __shared__ u64 tkey[TS];
+    __shared__ PT tpay[TS];
+    __shared__ unsigned s_nulln;
+
+    const unsigned total = a.work_start[a.P];
+    if (blockIdx.x >= total) return;
+    const T *trows = (const T *)a.r;   // the table side
+    const T *erows = (const T *)a.s;   // the emit side
+    PT *orr = (PT *)a.out_r;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> kRunLog);
+    const unsigned off = threadIdx.x & ((1u << kRunLog) - 1u);
+    unsigned hits = 0;
+    if (threadIdx.x == 0) s_nulln = 0u;   // (read behind the first round's barriers)
+
+    for (unsigned w = blockIdx.x; w < total; w += gridDim.x) {
+        const ItemDesc it = sload(a.desc + w);   // (wave-uniform words: scalar loads)
+        const bool rounds = it.r_hi - it.r_lo > (u64)SH::rb;   // more than one build round
+        bool built = false, renull = false;
+        for (u64 sb = it.s_lo; sb < it.s_hi; sb += SH::subb) {
+            const u64 shi = sb + SH::subb < it.s_hi ? sb + SH::subb : it.s_hi;
+            T sv[SI];
+            unsigned sok = load_run_rows<NW>(erows, a.s_runs, sb, shi, wave, off, sv, R::zero(), WholeRow<kNtJoinLd>{});
+            long long bnd[SI], best[SI];
+            unsigned found = 0;
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                bnd[i] = 0ll;
+                best[i] = asof_start<KIND>;
+                if (!((sok >> i) & 1u)) continue;
+                const u64 row = R::pay(sv[i]);
+                if (row >= n) {   // (never: the partition wrote row indices below n)
+                    sok &= ~(1u << i);
+                    continue;
+                }
+                if constexpr (WIDE) bnd[i] = ((const long long *)sbound)[row];
+                else bnd[i] = (long long)((const int *)sbound)[row];
+            }
+            for (u64 r0 = it.r_lo; r0 < it.r_hi; r0 += SH::rb) {
+                if (rounds || !built || renull) {
+                    // ---- build rows of runs [r0, rhi): every row a slot of its own
+                    const u64 rhi = r0 + SH::rb < it.r_hi ? r0 + SH::rb : it.r_hi;
+                    T br[SH::RI];
+                    const unsigned rok =
+                        load_run_rows<NW>(trows, a.r_runs, r0, rhi, wave, off, br, R::zero(), WholeRow<false>{});
+                    __syncthreads();   // the previous table's probes are done
+                    if constexpr (WIDE) {
+                        // ---- the round's INT64_MIN rows, as a list in tpay, folded before the table is made
+#pragma unroll
+                        for (int i = 0; i < SH::RI; ++i)
+                            if (((rok >> i) & 1u) && R::key(br[i]) == kEmptyKey64)
+                                tpay[atomicAdd(&s_nulln, 1u)] = (PT)R::pay(br[i]);
+                        __syncthreads();
+                        const unsigned nn = s_nulln;
+                        if (nn) {   // (uniform)
+                            renull = true;
+#pragma unroll
+                            for (int i = 0; i < SI; ++i) {
+                                if (!((sok >> i) & 1u) || R::key(sv[i]) != kEmptyKey64) continue;
+                                for (unsigned k = 0; k < nn; ++k)
+                                    if (asof_fold<KIND>((long long)tpay[k], bnd[i], best[i])) found |= 1u << i;
+                            }
+                        }
+                    }
+                    TB::clear(tkey);
+                    __syncthreads();   // the table is empty, the list has been read
+                    if (WIDE && threadIdx.x == 0) s_nulln = 0u;
+#pragma unroll
+                    for (int i = 0; i < SH::RI; ++i) {
+                        if (!((rok >> i) & 1u)) continue;
+                        const u64 key = R::key(br[i]);
+                        if (WIDE && key == kEmptyKey64) continue;
+                        unsigned h = TB::slot(key, a.tshift);
+                        while (atomicCAS(&tkey[h], kEmpty, key) != kEmpty) h = (h + 1) & kMask;
+                        tpay[h] = (PT)R::pay(br[i]);
+                    }
+                    __syncthreads();
+                    built = true;
+                }
+                // ---- probe every row of the sub-chunk (its INT64_MIN rows took the list above)
+                unsigned hp[SI];
+                u64 e0[SI];
+                unsigned open = sok;
+                TB::probe_first(tkey, sv, a.tshift, open, hp, e0, [](int) {});
+#pragma unroll
+                for (int i = 0; i < SI; ++i) {
+                    if (!((open >> i) & 1u)) continue;
+                    const u64 key = R::key(sv[i]);
+                    unsigned h = hp[i];
+                    u64 e = e0[i];
+                    while (e != kEmpty) {
+                        if (e == key && asof_fold<KIND>((long long)tpay[h], bnd[i], best[i])) found |= 1u << i;
+                        h = (h + 1) & kMask;
+                        e = tkey[h];
+                    }
+                }
+            }
+            // ---- store this sub-chunk's rows at their own indices
+#pragma unroll
+            for (int i = 0; i < SI; ++i) {
+                if (!((sok >> i) & 1u)) continue;
+                const u64 row = R::pay(sv[i]);
+                const bool f = (found >> i) & 1u;
+                st_s<kNtLookupSt>(orr + row, f ? (PT)best[i] : (PT)null_pay);
+                hits += f ? 1u : 0u;
+            }
+        }
+    }
+    const unsigned x = wave_incl_add(hits);
+    if (off == 63 && x) atomicAdd(a.counter, (u64)x);
 }
 
 // --------------------------------------------------------------- group join
@@ -4857,6 +5013,31 @@ hipError_t radix_expand(bool wide, bool outer, unsigned long long null_pay, long
         hipLaunchKernelGGL((k_join_expand<decltype(w_)::value, kExpandNT, kExpandSI, kExpandWPS>), dim3(g.grid),
                            dim3(kExpandNT), 0, st, g.a, (const long long *)off, (u64)null_pay, o, rows);
     });
+    return hipGetLastError();
+}
+
+// The as-of probe: k_join_asof over radix_lookup's work map, unchanged (the
+// same sub-chunk and grid: one 128 / 96 KiB table per CU).
+hipError_t radix_asof(bool wide, int kind, unsigned long long null_pay, long long n, const void *bound,
+                      const RadixPlan &pl, const RadixWork &ws, const BucketSet &r, const BucketSet &s,
+                      const OutDev &out, hipStream_t st) {
+    static_assert(kAsofNT * kAsofSI == kLookupNT * kLookupSI, "the as-of probe's items are the lookup's");
+    if (kind < 0 || kind > 3) return hipErrorInvalidValue;
+    const Stage g = lookup_stage(wide, pl, ws, r, s, out, st);
+    if (!g.grid) return hipErrorInvalidValue;
+    const u64 rows = (u64)(n > 0 ? n : 0);
+    auto launch = [&](auto k_) {
+        by_width(wide, [&](auto w_) {
+            hipLaunchKernelGGL((k_join_asof<decltype(w_)::value, kAsofNT, kAsofSI, kAsofWPS, decltype(k_)::value>),
+                               dim3(g.grid), dim3(kAsofNT), 0, st, g.a, bound, (u64)null_pay, rows);
+        });
+    };
+    switch (kind) {
+    case 0: launch(std::integral_constant<int, 0>{}); break;
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    default: launch(std::integral_constant<int, 3>{}); break;
+    }
     return hipGetLastError();
 }
 

@@ -32,8 +32,12 @@ HJ_JOIN_KERNEL_LOOKUP = 7
 HJ_JOIN_KERNEL_GROUP = 8
 HJ_JOIN_KERNEL_AGGREGATE = 9
 HJ_JOIN_KERNEL_EXPAND = 10
+HJ_JOIN_KERNEL_ASOF = 11
 HJ_EXPAND_INNER = 0
 HJ_EXPAND_OUTER = 1
+HJ_ASOF_BACKWARD = 0
+HJ_ASOF_FORWARD = 1
+HJ_ASOF_STRICT = 2
 # the expand probe's scan (hj_kernels.hip: kExpandTile counts per tile, kExpandFan tile sums per step of
 # the one workgroup that scans them) -- the sizes at which its paths change, for the tests
 EXPAND_SCAN_TILE = 2048
@@ -113,6 +117,8 @@ def _load():
         "hj_dev_exists_i32": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_lookup_i64": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
         "hj_dev_lookup_i32": (_int, [_vp, _vp, _i64, C.c_int32, _vp, _vp, _vp, _vp]),
+        "hj_dev_asof_i64": (_int, [_vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+        "hj_dev_asof_i32": (_int, [_vp, _int, _vp, _vp, _i64, C.c_int32, _vp, _vp, _vp]),
         "hj_dev_expand_i64": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_expand_i32": (_int, [_vp, _int, _vp, _i64, C.c_int32, _vp, _vp, _i64, _vp, _vp]),
         "hj_ctx_reserve_expand": (_int, [_vp, _i64, _int]),

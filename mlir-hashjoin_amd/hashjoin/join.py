@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from ._lib import (HJ_ERR_RANGE, HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_FILTER_PASS, HJ_FILTER_REJECT, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_KEYS_MAX_COLS, HJ_OK, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
+from ._lib import (HJ_ASOF_BACKWARD, HJ_ASOF_FORWARD, HJ_ASOF_STRICT, HJ_ERR_RANGE, HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_FILTER_PASS, HJ_FILTER_REJECT, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_KEYS_MAX_COLS, HJ_OK, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
                    HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, HJError, check, lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
@@ -31,6 +31,7 @@ GROUP_KINDS = {"matched": HJ_GROUP_MATCHED, "all": HJ_GROUP_ALL}
 GROUP_AGGS = ("count", "sum", "min", "max")
 EXPAND_KINDS = {"inner": HJ_EXPAND_INNER, "outer": HJ_EXPAND_OUTER}
 FILTER_KINDS = {"pass": HJ_FILTER_PASS, "reject": HJ_FILTER_REJECT}
+ASOF_DIRECTIONS = {"backward": HJ_ASOF_BACKWARD, "forward": HJ_ASOF_FORWARD}
 
 
 def _ptr(t):
@@ -352,6 +353,7 @@ class HashJoin:
         self._count = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.key_bits = None
         self._routed = {}   # slot -> (rows, 2) int64 routed-tuple buffer (route(..., slot=))
+        self.asof_out = None   # the last probe_asof's result column (the one it allocated when given none)
 
     def close(self):
         self._routed = {}
@@ -424,7 +426,7 @@ class HashJoin:
 
     JOIN_KERNELS = {1: "k_join_b", 2: "k_join_u", 3: "k_join_u_stream", 4: "k_join_grp", 5: "k_join",
                     6: "k_join_exists", 7: "k_join_lookup", 8: "k_join_group", 9: "aggregate",
-                    10: "k_join_expand"}
+                    10: "k_join_expand", 11: "k_join_asof"}
 
     @property
     def join_kernel(self):
@@ -432,7 +434,8 @@ class HashJoin:
         'k_join_u_stream', 'k_join_grp', 'k_join', 'k_join_exists' (a radix
         semi- / anti-join), 'k_join_lookup' (a radix lookup), 'k_join_group' (a
         radix group probe), 'aggregate' (a radix hash aggregate: k_join_aggregate),
-        'k_join_expand' (a radix expand), or None (no radix join)."""
+        'k_join_expand' (a radix expand), 'k_join_asof' (a radix as-of probe),
+        or None (no radix join)."""
         r = lib.hj_ctx_join_kernel(self._ctx)
         if r < 0:
             check(r, "hj_ctx_join_kernel")
@@ -656,6 +659,113 @@ class HashJoin:
         if m < 0:   # bit 63 (hj.h)
             raise RuntimeError("hash join: internal work list overflow (count flagged)")
         return (out_r, out_cnt) if with_counts else out_r
+
+    # ---- as-of probe (hj.h "As-of probe"): per probe row, the nearest partner at or before a bound
+    def probe_asof(self, skey, sbound, out_r=None, direction="backward", strict=False, null=-1, count=None,
+                   stream=None):
+        """One result per probe row, in input order: out_r[j] = the largest R
+        payload (i32: R row id) <= sbound[j] among the R rows with key skey[j]
+        (direction "forward": the smallest >= it; strict: < / >), or `null`
+        written verbatim.  skey and sbound share dtype and length; out_r has
+        that dtype and at least that length, and only its first len(skey)
+        elements are written.  out_r None: a fresh column, kept as
+        self.asof_out.  `count` (int64 device tensor) receives the number of S
+        rows with a candidate.  Returns count."""
+        _need_cuda(skey, sbound, out_r)
+        st = _stream(self.device, stream)
+        count = self._count if count is None else count
+        n = skey.numel()
+        if skey.dtype not in (torch.int64, torch.int32):
+            raise TypeError("keys must be int32 or int64")
+        if sbound is None or sbound.dtype != skey.dtype or sbound.numel() != n:
+            raise ValueError("sbound carries the probe key's dtype and length")
+        if out_r is None:
+            out_r = torch.empty(n, dtype=skey.dtype, device=self.device)
+        elif out_r.dtype != skey.dtype or out_r.numel() < n:
+            raise ValueError("out_r carries the probe key's dtype and at least its length")
+        kind = ASOF_DIRECTIONS[direction] | (HJ_ASOF_STRICT if strict else 0)
+        f, name = ((lib.hj_dev_asof_i64, "hj_dev_asof_i64") if skey.dtype == torch.int64
+                   else (lib.hj_dev_asof_i32, "hj_dev_asof_i32"))
+        check(f(self._ctx, kind, _ptr(skey), _ptr(sbound), n, int(null), _ptr(out_r), _ptr(count), st), name)
+        self.asof_out = out_r
+        return count
+
+    def asof(self, rkey, rpay, skey, sbound, direction="backward", strict=False, null=-1, stream=None):
+        """Build R, then probe_asof: out_r of length |S|.  int64 keys with rpay
+        None: the payload is R's row index ("the last R row with this key at or
+        before row b"); int32 keys always carry R's row ids."""
+        self.probe_hint(skey.numel())
+        try:
+            if rkey.dtype == torch.int64 and rpay is None:
+                rpay = torch.arange(rkey.numel(), dtype=torch.int64, device=self.device)
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+        out_r = torch.empty(skey.numel(), dtype=skey.dtype, device=self.device)
+        m = int(self.probe_asof(skey, sbound, out_r, direction=direction, strict=strict, null=null,
+                                stream=stream).item())
+        if m < 0:   # bit 63 (hj.h)
+            raise RuntimeError("hash join: internal work list overflow (count flagged)")
+        return out_r
+
+    def asof_join(self, rkey, rtime, skey, stime, direction="backward", allow_exact_matches=True, tolerance=None,
+                  stream=None):
+        """pandas merge_asof(by=key, on=time) without its sortedness
+        requirement: per S row, the index of the R row with its key whose time
+        is the nearest at or before ("forward": at or after; "nearest": either,
+        a distance tie going to backward) stime, or -1.  Among R rows of equal
+        key and time backward takes the last and forward the first, as pandas
+        does.  allow_exact_matches=False excludes equal times; tolerance drops
+        matches further than it.  Plumbing over probe_asof: the build payload is
+        (rtime - t0) << rowbits | row, with t0 the minimum over both time
+        columns and rowbits the width of len(R) - 1; ValueError if that needs
+        more than 63 bits."""
+        if direction not in ("backward", "forward", "nearest"):
+            raise ValueError("direction must be 'backward', 'forward' or 'nearest'")
+        for t in (rkey, rtime, skey, stime):
+            if t.dtype != torch.int64:
+                raise TypeError("asof_join takes int64 key and time columns")
+        if rtime.numel() != rkey.numel() or stime.numel() != skey.numel():
+            raise ValueError("key and time columns of a relation share their length")
+        nr, ns = rkey.numel(), skey.numel()
+        none = torch.full((ns,), -1, dtype=torch.int64, device=self.device)
+        if nr == 0 or ns == 0:
+            return none
+        t0 = min(int(rtime.min().item()), int(stime.min().item()))
+        span = max(int(rtime.max().item()), int(stime.max().item())) - t0
+        rowbits = (nr - 1).bit_length()
+        if span.bit_length() + rowbits > 63:
+            raise ValueError(f"asof_join: times spanning {span.bit_length()} bits and {rowbits} row bits do not "
+                             "pack into 63 bits")
+        low = (1 << rowbits) - 1
+        rpay = ((rtime - t0) << rowbits) | torch.arange(nr, dtype=torch.int64, device=self.device)
+        sbase = (stime - t0) << rowbits
+        self.probe_hint(ns)
+        try:
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+
+        def probe(fwd):
+            # backward: the low bits all ones admit every row of an equal time and the max takes the last;
+            # without exact matches the low bits are zero and the compare strict.  forward: the mirror image
+            ones = (not fwd) == bool(allow_exact_matches)
+            out = torch.empty(ns, dtype=torch.int64, device=self.device)
+            self.probe_asof(skey, sbase | low if ones else sbase, out, direction="forward" if fwd else "backward",
+                            strict=not allow_exact_matches, null=-1, stream=stream)
+            hit = out >= 0   # (payloads are non-negative)
+            return hit, out & low, (out >> rowbits) + t0
+
+        if direction == "nearest":
+            hb, ib, tb = probe(False)
+            hf, i_f, tf = probe(True)
+            take_b = hb & (~hf | ((stime - tb) <= (tf - stime)))
+            hit, idx, tm = hb | hf, torch.where(take_b, ib, i_f), torch.where(take_b, tb, tf)
+        else:
+            hit, idx, tm = probe(direction == "forward")
+        if tolerance is not None:
+            hit = hit & ((tm - stime).abs() <= int(tolerance))
+        return torch.where(hit, idx, none)
 
     # ---- expand probe (hj.h "Expand probe"): all partners per probe row, as a CSR in input order
     def reserve_expand(self, num_tuples, key_bits=64):
