@@ -107,7 +107,8 @@ int64_t hj_ctx_table_capacity(const hj_ctx *ctx);
 /* RADIX: partition passes of the current build (1..3) and their fan-out bits
  * (bits[0..passes-1]); returns 0 passes for GLOBAL / no build. */
 int hj_ctx_radix_plan(const hj_ctx *ctx, int *passes, int bits[3]);
-/* 1 if the build side repeats a key, 0 if not (synchronises).  Known after
+/* 1 if the build side repeats a key, 0 if not (synchronises); INT64_MIN is a
+ * key like any other here too: two build rows that hold it repeat it.  Known after
  * the build (GLOBAL) or after the first probe (RADIX: a repeat that a probe
  * row met is flagged by the join; the first call after a join whose kernel
  * was k_join_b checks every partition of the build side on the device,

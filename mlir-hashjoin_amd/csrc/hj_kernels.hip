@@ -158,6 +158,8 @@ __global__ __launch_bounds__(kBlock) void k_init(TableDev t, unsigned long long 
 // duplicate key (both rows walk the same probe sequence, so the later one
 // must fail on the earlier one's slot); that sets meta[1], and probes then
 // keep walking past matches.  Without duplicates a probe stops at its match.
+// INT64_MIN keys sit in the side list, not in a slot: the row that finds the
+// list non-empty is the repeat (hj_ctx_build_has_duplicates answers for them too).
 template <int L, int FORM>
 __global__ __launch_bounds__(kBlock) void k_build(TableDev t, SrcDev src) {
     using LY = Lay<L>;
@@ -174,18 +176,19 @@ __global__ __launch_bounds__(kBlock) void k_build(TableDev t, SrcDev src) {
         k[i] = tp.k;
         p[i] = tp.p;
     }
+    bool dup = false;
 #pragma unroll
     for (int i = 0; i < kBuildItems; ++i) {
         if (v[i] && LY::null_key(k[i])) {   // wide only: INT64_MIN keys -> side list
             const unsigned long long idx = atomicAdd(&t.meta[0], 1ull);
             t.side[idx] = p[i];
+            dup |= idx != 0ull;             // a second INT64_MIN row repeats a key like any other
             v[i] = false;
         }
         h[i] = slot_of(k[i], t.shift);
         o[i] = v[i] ? atomicCAS(LY::word(sl, h[i]), LY::kEmptyWord, LY::cas_val(k[i], p[i]))
                     : LY::kEmptyWord;
     }
-    bool dup = false;
 #pragma unroll
     for (int i = 0; i < kBuildItems; ++i) {
         if (!v[i]) continue;

@@ -86,6 +86,9 @@ def assert_radix(hj):
 
 
 # ------------------------------------------------------------------ global
+# (ns = 2 * 2048 + 77 is three tiles, one per workgroup: k_probe_asof never
+# strides here, so its load-ahead and hand-over stay idle.  The shape with
+# more tiles than workgroups is test_gpu_positional_tiles.py's.)
 @pytest.mark.parametrize("nr", [1, 2048, 3000])   # 2048: the last LDS-resident table
 def test_global_i64(glob_hj, oracle, nr):
     ns = 2 * 2048 + 77   # a ragged third tile

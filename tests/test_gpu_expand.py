@@ -98,6 +98,9 @@ class radix:
 
 
 # ------------------------------------------------------------------ global
+# (ns = 2 * 2048 + 77 is three tiles, one per workgroup: k_probe_lookup's count
+# stage and k_probe_expand never stride here.  The shape with more tiles than
+# workgroups, and a cap that cuts a later tile, is test_gpu_positional_tiles.py's.)
 @pytest.mark.parametrize("nr", [1, 2048, 3000])   # 2048: the last LDS-resident table
 def test_global_i64(glob_hj, oracle, nr):
     ns = 2 * 2048 + 77   # a ragged third tile

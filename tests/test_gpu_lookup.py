@@ -13,11 +13,12 @@ import torch
 
 import outer_cases as OC
 from hashjoin import HashJoin, _lib, lib
+from positional_cases import EXTRA, NULL, SENTINEL   # -9, -12345, 64: i32 payloads are row ids (>= 0)
+from positional_cases import lookup_expect as expect
 
 pytestmark = pytest.mark.gpu
 
 I64_MIN = OC.I64_MIN
-NULL, SENTINEL, EXTRA = -9, -12345, 64   # i32 payloads are row ids (>= 0)
 
 
 @pytest.fixture(scope="module")
@@ -45,16 +46,6 @@ def payloads(rk, seed=1):
     if rk.dtype == np.int32:
         return np.arange(n, dtype=np.int64)
     return (np.random.default_rng(seed).permutation(n).astype(np.int64) - n // 2) * 3 + 1
-
-
-def expect(rk, rp, sk):
-    """(payload column, count column) numpy says the lookup of sk in (rk, rp) gives."""
-    cnt = OC.Expect(rk, sk).cnt
-    if len(rk) == 0:
-        return np.full(len(sk), NULL, np.int64), cnt
-    o = np.lexsort((rp, rk))
-    lo = np.minimum(np.searchsorted(rk[o], sk, "left"), len(rk) - 1)
-    return np.where(cnt > 0, rp[o][lo], NULL).astype(np.int64), cnt
 
 
 def build(hj, rk, rp):
@@ -94,6 +85,9 @@ def assert_radix(hj):
 
 
 # ------------------------------------------------------------------ global
+# (ns = 2 * 2048 + 77 is three tiles, one per workgroup: k_probe_lookup never
+# strides here, so its load-ahead and hand-over stay idle.  The shape with
+# more tiles than workgroups is test_gpu_positional_tiles.py's.)
 @pytest.mark.parametrize("nr", [1, 2048, 3000])   # 2048: the last LDS-resident table
 def test_global_i64(glob_hj, oracle, nr):
     ns = 2 * 2048 + 77   # a ragged third tile
@@ -293,6 +287,30 @@ def test_empty_and_tiny(hj, strategy, wide):
             assert hj.strategy_used == strategy
             if len(rk) == 0:
                 assert (er == NULL).all() and (ec == 0).all()
+    finally:
+        hj.set_strategy("auto")
+
+
+@pytest.mark.parametrize("copies", [1, 2])
+@pytest.mark.parametrize("strategy", ["global", "radix"])
+def test_int64_min_build_rows_and_the_repeat_flag(hj, oracle, strategy, copies):
+    """INT64_MIN is a key like any other to has_duplicates() too: two build rows
+    that hold it (they sit beside the table, in no slot) are a repeated key,
+    one is not -- with no other key twice."""
+    rk, _, sk, _ = oracle.gen_pkfk_i64(5, 3000, 9001, 0.5)
+    rk, sk = rk.copy(), sk.copy()
+    rk[[7, 2900][:copies]] = I64_MIN
+    sk[::1777] = I64_MIN
+    assert len(np.unique(rk)) == 3000 - (copies - 1)
+    rp = payloads(rk, 5)
+    hj.set_strategy(strategy, radix_bits=5 if strategy == "radix" else 0)
+    try:
+        build(hj, rk, rp)
+        _, ec = check(hj, rk, rp, sk)
+        assert (ec[::1777] == copies).all() and ec.max() == copies
+        assert hj.strategy_used == strategy
+        assert hj.has_duplicates() == (copies == 2)
+        check(hj, rk, rp, sk)
     finally:
         hj.set_strategy("auto")
 

@@ -2,11 +2,14 @@
 <= 64 KiB: int64 builds of <= 2048 rows, i32 builds of <= 4096 rows) against
 the oracle: unique and repeated build keys, INT64_MIN probe keys (their
 tiles take the general path), count-only, i32 reference types, and the sizes
-either side of the LDS limit."""
+either side of the LDS limit.  The inner, exists, outer and full probes also
+run with more tiles than workgroups (several_tiles_case); the positional
+probes (lookup, as-of, expand) do so in test_gpu_positional_tiles.py."""
 import numpy as np
 import pytest
 import torch
 
+import positional_cases as PC
 from hashjoin import HashJoin
 
 pytestmark = pytest.mark.gpu
@@ -73,59 +76,19 @@ def test_small_table_i32(hj, oracle, nr):
     assert oracle.same_multiset(*o, *oracle.chained_join_i32(r, s, H=max(1, nr // 4)))
 
 
-I64_MIN = -(1 << 63)
-# 1026 tiles of 2048 rows, the last with 77: a 64-KiB table runs two
-# workgroups per CU (512 on 256 CUs), so every workgroup strides over two
-# tiles at least, workgroups 0 and 1 over three
-SEVERAL_NS = (1 << 21) + 2048 + 77
-# INT64_MIN probe keys: tile 3 (workgroup 3 hands on its first tile and keeps
-# its second), tile 512 + 7 (workgroup 7: the reverse), tiles 0 and 512
-# (workgroup 0 keeps only its third) and the ragged last tile
-NULL_ROWS = (3 * 2048 + 5, (512 + 7) * 2048 + 100, 1, 512 * 2048 + 2047, 1025 * 2048 + 10)
+I64_MIN = PC.I64_MIN
+# 1026 tiles of 2048 rows, the last with 77, and the rows of S that hold
+# INT64_MIN: see positional_cases, which builds the relation
+SEVERAL_NS, NULL_ROWS = PC.SEVERAL_NS, PC.NULL_ROWS
 
 
 def several_tiles_case(wide, hits=slice(None), s_nulls=True):
-    """Build and probe columns, and what numpy says they join to: a table of
-    exactly 64 KiB with five repeated keys (wide: and one INT64_MIN key), a
-    probe side a quarter of which hits it, forty rows of it a repeated key.
-    hits: the slice of the plain build rows that the hits are drawn from (the
-    rest, like four of the repeated keys, then have no partner in S);
-    s_nulls=False leaves NULL_ROWS as misses, so S holds no INT64_MIN key."""
-    nr, ns = (2048, SEVERAL_NS) if wide else (4096, SEVERAL_NS)
-    dt, top = (np.int64, 1 << 40) if wide else (np.int32, 1 << 29)
-    rng = np.random.default_rng(2048 if wide else 4096)
-    rk = rng.permutation(np.unique(rng.integers(1, top, 2 * nr)))[:nr].astype(dt)
-    assert len(rk) == nr
-    rk[nr - 5:] = rk[:5]                                    # five keys twice
-    plain = np.arange(5, nr - 5)                            # build rows whose key is neither repeated nor null
-    if wide:
-        rk[100] = I64_MIN
-        plain = plain[plain != 100]
-    rp = np.arange(nr, dtype=np.int64) + (7000 if wide else 0)   # (i32: the row id)
-    sk = rng.integers(2 * top, 4 * top - 1, ns).astype(dt)       # misses
-    hit = rng.permutation(ns)[:ns // 4]
-    sk[hit] = rk[rng.choice(plain[hits], len(hit))]         # a quarter of S hits R once
-    sk[rng.permutation(ns)[:40]] = rk[0]                    # forty rows meet a repeated key
-    if wide and s_nulls:
-        sk[list(NULL_ROWS)] = I64_MIN
-    sp = np.arange(ns, dtype=np.int64) + (1 << 32 if wide else 0)
-    # sort + searchsorted: build rows lo[j] .. hi[j] of the sorted side match probe row j
-    order = np.argsort(rk, kind="stable")
-    lo, hi = np.searchsorted(rk[order], sk, "left"), np.searchsorted(rk[order], sk, "right")
-    cnt = hi - lo
-    first = np.cumsum(cnt) - cnt
-    within = np.arange(int(cnt.sum())) - np.repeat(first, cnt)
-    exp_r = rp[order[np.repeat(lo, cnt) + within]]
-    exp_s = np.repeat(sp, cnt)
-    assert int((cnt == 2).sum()) >= 40 and int((cnt > 0).sum()) >= ns // 4
-    # the rows without a partner: S's by the counts, R's by np.isin (every copy of a key no S row holds)
-    r_un = ~np.isin(rk, sk)
-    pairs, n_s, n_r = len(exp_r), int((cnt == 0).sum()), int(r_un.sum())
-    assert pairs > 0 and n_s > 0 and n_r > (0 if hits == slice(None) else 1000)
-    assert r_un[[1, 2, 3, 4]].all() and r_un[nr - 4:].all() and not r_un[0] and not r_un[nr - 5]
-    return dict(rk=rk, rp=rp, sk=sk, sp=sp, cnt=cnt, exp_r=exp_r, exp_s=exp_s, null_s_rows=sp[cnt == 0],
-                null_r_rows=rp[r_un],
-                d_rk=dev(rk), d_rp=dev(rp) if wide else None, d_sk=dev(sk), d_sp=dev(sp) if wide else None)
+    """positional_cases.several_tiles_arrays (a table of exactly 64 KiB, a
+    probe side of 1026 tiles a quarter of which hits it, and what numpy says
+    they join to) with its four columns on the device as well."""
+    c = PC.several_tiles_arrays(wide, hits, s_nulls)
+    return dict(c, d_rk=dev(c["rk"]), d_rp=dev(c["rp"]) if wide else None, d_sk=dev(c["sk"]),
+                d_sp=dev(c["sp"]) if wide else None)
 
 
 @pytest.fixture(scope="module")
