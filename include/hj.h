@@ -811,6 +811,107 @@ int hj_dev_filter_apply_tuples_i64(hj_filter *f, int kind, const int64_t *tuples
 int hj_dev_filter_apply_i32(hj_filter *f, int kind, const int32_t *skey, int64_t n, int64_t row_base,
                             int32_t *out_key, int32_t *out_row, int64_t out_cap, uint64_t *d_count, void *stream);
 
+/* --------------------------------------------------------------- Star probe
+ * One pass of n probe rows (a fact table) over 1..HJ_STAR_MAX_DIMS built
+ * relations (its dimensions): per dimension d a key column skeys[d] of the
+ * probe rows and a context dims[d] holding an ordinary build in its GLOBAL
+ * table.  The rows that qualify under EVERY dimension are returned in input
+ * order with each dimension's payload beside them.  The key columns are read
+ * once for the decision, the tables are walked in one kernel, and only the M
+ * surviving rows are written.  An object of its own, like hj_filter: it owns
+ * the compaction workspace and only reads the contexts.
+ *
+ * For dimension d let R_d be the relation built in dims[d], c_d(j) the number
+ * of R_d rows whose key equals skeys[d][j] and p_d(j) the smallest signed
+ * payload among them (i32: the smallest row id) -- exactly hj_dev_lookup_*'s
+ * out_cnt and out_r.  Kinds, per dimension:
+ *   HJ_STAR_INNER  row j needs c_d(j) > 0.  With out_pay[d] == NULL this is
+ *                  the semi-join form.
+ *   HJ_STAR_LEFT   row j always stays; its payload is p_d(j), or null_pay[d]
+ *                  written verbatim when c_d(j) == 0.
+ *   HJ_STAR_ANTI   row j needs c_d(j) == 0.  It has no payload column: a
+ *                  non-null out_pay[d] is HJ_ERR_ARG.
+ * Row j qualifies iff every dimension admits it.  With o the number of
+ * qualifying rows before j:
+ *     out_row[o]    = j                        (i32: row_base + j)
+ *     out_pay[d][o] = p_d(j), or null_pay[d] when c_d(j) == 0
+ *     *d_count      = M, the number of qualifying rows, exactly, even when M >
+ *                     out_cap.
+ * Nothing is written at or past out_cap in any column, and every position
+ * below min(M, out_cap) holds its defined value.  Every output is optional
+ * (out_pay itself may be NULL: no payload column).  out_cap == 0 with every
+ * output NULL is the count form; out_cap > 0 with every output NULL, or
+ * out_cap == 0 with any output, is HJ_ERR_ARG.
+ * The result is a function of the data alone: bit-equal across runs and
+ * across the table placements below.
+ *   - INT64_MIN is a key like any other on both sides (the wide layout answers
+ *     it from the side list, as the lookup does).
+ *   - An empty R_d: INNER gives M = 0, LEFT all nulls, ANTI admits every row.
+ *   - n == 0 writes nothing but the counter.
+ *   - The same context may appear in two dimensions.
+ * The contexts are only read: the table, the side list, the mark bitmap, the
+ * state words, the strategy of the last probe, the timing sets and the "build
+ * keys repeat" flag are left untouched, and every other probe of those builds
+ * returns afterwards what it returned before.
+ *
+ * dims, kinds, skeys, null_pay (null_row) and out_pay are HOST arrays of ndims
+ * entries read at call time; their values travel in the kernel arguments.  All
+ * dimensions of one call share a layout: int64 builds for hj_dev_star_i64,
+ * hj_dev_build_i32 builds for hj_dev_star_i32.
+ * The dimensions are walked in the caller's order and a row that one of them
+ * dropped is looked up in no further one: put the most selective first.
+ * There is no radix form: it would have to partition the probe rows once per
+ * key column.  A radix-only build (HJ_STRATEGY_RADIX, or AUTO from 2^21 rows)
+ * is HJ_ERR_STATE; AUTO's dual build (2^18..2^21 rows) is valid, its global
+ * table exists.
+ *
+ * Errors, in this order: a null star (HJ_ERR_ARG, "null star", before any
+ * device is touched); ndims outside 1..HJ_STAR_MAX_DIMS or a null dims, kinds,
+ * skeys or null-value array (HJ_ERR_ARG); per dimension in index order a null
+ * context, a kind outside the three, a context of another device (HJ_ERR_ARG),
+ * no build of that layout, a build with no global table (HJ_ERR_STATE, the
+ * message names the dimension); a null count pointer; n < 0 or a null key
+ * column with n > 0; bad outputs as above; for i32 row ids past 2^31 - 1 (all
+ * HJ_ERR_ARG); HJ_ERR_NOMEM when the workspace does not fit.
+ *
+ * Launches.  Asynchronous on the stream (NULL = default stream).  Two kernels
+ * around a scan: the decision launch leaves one result byte per lane and a
+ * count per 2048-row tile, exclusive_scan turns the counts into offsets, the
+ * write launch stores the survivors (the count form stores the counter alone).
+ * When no dimension can drop a row (every kind LEFT) a row's position is its
+ * index: ONE probe launch stores everything positionally, clipped at out_cap,
+ * and M = n.  The probe launch (the decision, or the keep-all launch) sees
+ * every row: the tables it walks go to LDS in ascending size while their sum
+ * stays <= 128 KiB and each is <= 64 KiB, and the others are read from global
+ * memory in the same kernel; the plan is a function of the tables' capacities
+ * at call time.  The write launch sees the survivors alone and reads every
+ * table from global memory.
+ * hj_star_reserve sizes the workspace for max_rows probe rows (grow-only);
+ * after it the calls launch kernels only -- the counter is written by a
+ * kernel, never a memset -- and the dimensions' builds followed by the star
+ * probe capture as a LINEAR graph that, replayed, follows new data in the same
+ * buffers.  A call of more rows than reserved grows the workspace first (it
+ * waits for the device and cannot be captured).
+ * hj_star_last_plan: host facts of the last hj_dev_star_* call, no
+ * synchronisation: the kernel launches, the grid of the probe launch (the
+ * decision, or the keep-all launch), its tiles, bit d of lds_dims set =
+ * dimension d's table was probed from LDS, the LDS bytes of those tables. */
+#define HJ_STAR_MAX_DIMS 4
+#define HJ_STAR_INNER 0 /* the row needs a partner in this dimension */
+#define HJ_STAR_LEFT 1  /* the row stays; null_pay[d] where it has none */
+#define HJ_STAR_ANTI 2  /* the row needs to have no partner; no payload column */
+typedef struct hj_star hj_star;
+hj_star *hj_star_create(int device);
+void hj_star_destroy(hj_star *s);
+int hj_star_reserve(hj_star *s, int64_t max_rows);
+int hj_star_last_plan(const hj_star *s, int *launches, int *grid, int64_t *tiles, int *lds_dims, int64_t *lds_bytes);
+int hj_dev_star_i64(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[], const int64_t *const skeys[],
+                    const int64_t null_pay[], int64_t n, int64_t *const out_pay[], int64_t *out_row,
+                    int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_star_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[], const int32_t *const skeys[],
+                    const int32_t null_row[], int64_t n, int64_t row_base, int32_t *const out_pay[], int32_t *out_row,
+                    int64_t out_cap, uint64_t *d_count, void *stream);
+
 /* Radix partition of rows into nparts (1..8192) groups by a key hash independent of
  * the table's slot hash: out_tuples (2*n int64) receives packed {key, pay}
  * tuples grouped by partition in order 0..nparts-1, d_counts (nparts uint64)

@@ -3011,6 +3011,168 @@ int hj_dev_filter_apply_i32(hj_filter *f, int kind, const int32_t *skey, int64_t
 
 }  // extern "C"
 
+// -------------------------------------------------------------- star probe
+// A star probe object: the compaction workspace (tile counts, scan sums, one
+// result byte per lane: the key filter's shape) in ONE grow-only allocation,
+// and the host facts of the last call.  The contexts it probes are only read.
+struct hj_star {
+    int device = 0;
+    void *work = nullptr;        // device
+    int64_t work_rows = -1;      // rows the workspace admits
+    hj::FilterWork ws{nullptr, nullptr, nullptr};
+    hj::StarPlan plan{0, 0u, 0, 0, 0};
+};
+
+namespace {
+
+static_assert(HJ_STAR_INNER == hj::kStarInner && HJ_STAR_LEFT == hj::kStarLeft && HJ_STAR_ANTI == hj::kStarAnti &&
+                  HJ_STAR_MAX_DIMS == hj::kStarMaxDims,
+              "hj.h's star constants are the kernels'");
+
+int star_work(hj_star *s, int64_t rows) {
+    if (rows <= s->work_rows) return HJ_OK;
+    const size_t nt = hj::filter_tiles(rows) + 1;
+    const size_t tiles_b = (nt * 8 + 15) & ~size_t(15), sums_b = (hj::exclusive_scan_sums(nt) * 8 + 15) & ~size_t(15);
+    const size_t map_b = hj::filter_tiles(rows) * hj::kFilterBlock + 16;
+    HJ_HIP(hipSetDevice(s->device));
+    if (s->work) HJ_HIP(hipFree(s->work));   // (waits for the device: nothing in flight reads the old one)
+    s->work = nullptr;
+    s->work_rows = -1;
+    if (hipMalloc(&s->work, tiles_b + sums_b + map_b) != hipSuccess) {
+        (void)hipGetLastError();
+        HJ_FAIL(HJ_ERR_NOMEM, "star probe: hipMalloc of the workspace for " + std::to_string(rows) + " rows");
+    }
+    s->ws.tiles = (unsigned long long *)s->work;
+    s->ws.sums = (unsigned long long *)((char *)s->work + tiles_b);
+    s->ws.bitmap = (unsigned char *)s->work + tiles_b + sums_b;
+    s->work_rows = rows;
+    return HJ_OK;
+}
+
+// Both entry points behind their casts: the checks in hj.h's order, then the launches.
+int do_star(hj_star *s, int layout, int ndims, hj_ctx *const dims[], const int kinds[], const void *const skeys[],
+            const unsigned long long null_pay[], int64_t n, int64_t row_base, void *const out_pay[], void *out_row,
+            int64_t cap, uint64_t *d_count, void *stream) {
+    if (!s) HJ_FAIL(HJ_ERR_ARG, "null star");
+    if (ndims < 1 || ndims > HJ_STAR_MAX_DIMS)
+        HJ_FAIL(HJ_ERR_ARG, "star probe: ndims must be in 1.." + std::to_string(HJ_STAR_MAX_DIMS));
+    if (!dims || !kinds || !skeys || !null_pay) HJ_FAIL(HJ_ERR_ARG, "star probe: null dims, kinds, skeys or null-value array");
+    for (int d = 0; d < ndims; ++d) {
+        const std::string who = "star probe: dimension " + std::to_string(d);
+        const hj_ctx *c = dims[d];
+        if (!c) HJ_FAIL(HJ_ERR_ARG, who + ": null context");
+        if (kinds[d] != HJ_STAR_INNER && kinds[d] != HJ_STAR_LEFT && kinds[d] != HJ_STAR_ANTI)
+            HJ_FAIL(HJ_ERR_ARG, who + ": kind must be HJ_STAR_INNER, HJ_STAR_LEFT or HJ_STAR_ANTI");
+        if (c->device != s->device) HJ_FAIL(HJ_ERR_ARG, who + ": a context of another device");
+        if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, who + ": no build of this layout");
+        if (c->used != HJ_STRATEGY_GLOBAL && !c->dual)
+            HJ_FAIL(HJ_ERR_STATE, who + ": a radix-only build has no global table (build it under HJ_STRATEGY_GLOBAL)");
+    }
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (n < 0) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: a negative row count");
+    bool any_out = out_row != nullptr;
+    for (int d = 0; d < ndims; ++d)
+        if (n > 0 && !skeys[d]) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: dimension " + std::to_string(d) + " has null keys");
+    for (int d = 0; d < ndims; ++d) {
+        void *o = out_pay ? out_pay[d] : nullptr;
+        if (o && kinds[d] == HJ_STAR_ANTI)
+            HJ_FAIL(HJ_ERR_ARG, "star probe: dimension " + std::to_string(d) + ": an ANTI dimension has no payload column");
+        any_out |= o != nullptr;
+    }
+    if (cap < 0) HJ_FAIL(HJ_ERR_ARG, "negative output capacity");
+    if (cap > 0 && !any_out) HJ_FAIL(HJ_ERR_ARG, "out_cap > 0 with every output null (the count form is out_cap == 0)");
+    if (cap == 0 && any_out) HJ_FAIL(HJ_ERR_ARG, "out_cap == 0 with an output (the count form takes none)");
+    if (layout == kNarrow && (row_base < 0 || row_base > INT32_MAX - n)) HJ_FAIL(HJ_ERR_ARG, "row ids past 2^31 - 1");
+    HJ_TRY(star_work(s, n));
+    HJ_HIP(hipSetDevice(s->device));
+    hj::StarArgs a{};
+    for (int d = 0; d < ndims; ++d) {
+        a.d[d].t = table_dev(dims[d]);
+        a.d[d].key = skeys[d];
+        a.d[d].out = out_pay ? out_pay[d] : nullptr;
+        a.d[d].null_pay = null_pay[d];
+        a.d[d].kind = kinds[d];
+        a.d[d].lds_off = -1;
+    }
+    a.n = n;
+    a.row_base = row_base;
+    a.cap = cap;
+    a.out_row = out_row;
+    a.count = (unsigned long long *)d_count;
+    HJ_HIP(hj::launch_star(layout, ndims, a, s->ws, &s->plan, (hipStream_t)stream));
+    return HJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+hj_star *hj_star_create(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        fail(HJ_ERR_HIP, __FILE__, __LINE__, "no HIP device visible");
+        return nullptr;
+    }
+    if (device < 0 || device >= n) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "device index out of range");
+        return nullptr;
+    }
+    // (here, not in a call: a launch above 64 KiB of dynamic LDS needs the attribute, and a call may be under capture)
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hj::star_prepare();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        fail(HJ_ERR_HIP, __FILE__, __LINE__, std::string("star probe: ") + hipGetErrorString(e));
+        return nullptr;
+    }
+    hj_star *s = new hj_star();
+    s->device = device;
+    return s;
+}
+
+void hj_star_destroy(hj_star *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)hipDeviceSynchronize();
+    if (s->work) (void)hipFree(s->work);
+    delete s;
+}
+
+int hj_star_reserve(hj_star *s, int64_t max_rows) {
+    if (!s) HJ_FAIL(HJ_ERR_ARG, "null star");
+    if (max_rows < 0) HJ_FAIL(HJ_ERR_ARG, "negative row count");
+    return star_work(s, max_rows);
+}
+
+int hj_star_last_plan(const hj_star *s, int *launches, int *grid, int64_t *tiles, int *lds_dims, int64_t *lds_bytes) {
+    if (!s) HJ_FAIL(HJ_ERR_ARG, "null star");
+    if (launches) *launches = s->plan.launches;
+    if (grid) *grid = (int)s->plan.grid;
+    if (tiles) *tiles = s->plan.tiles;
+    if (lds_dims) *lds_dims = s->plan.lds_dims;
+    if (lds_bytes) *lds_bytes = s->plan.lds_bytes;
+    return HJ_OK;
+}
+
+int hj_dev_star_i64(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[], const int64_t *const skeys[],
+                    const int64_t null_pay[], int64_t n, int64_t *const out_pay[], int64_t *out_row, int64_t out_cap,
+                    uint64_t *d_count, void *stream) {
+    return do_star(s, kWide, ndims, dims, kinds, (const void *const *)skeys, (const unsigned long long *)null_pay, n, 0,
+                   (void *const *)out_pay, out_row, out_cap, d_count, stream);
+}
+
+int hj_dev_star_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[], const int32_t *const skeys[],
+                    const int32_t null_row[], int64_t n, int64_t row_base, int32_t *const out_pay[], int32_t *out_row,
+                    int64_t out_cap, uint64_t *d_count, void *stream) {
+    unsigned long long nulls[HJ_STAR_MAX_DIMS] = {};
+    if (null_row && ndims >= 1 && ndims <= HJ_STAR_MAX_DIMS)
+        for (int d = 0; d < ndims; ++d) nulls[d] = (unsigned long long)(long long)null_row[d];
+    return do_star(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys, null_row ? nulls : nullptr, n, row_base,
+                   (void *const *)out_pay, out_row, out_cap, d_count, stream);
+}
+
+}  // extern "C"
+
 void hj_placement_stats(long long *probes, long long *rejected, double *last_kept, double *worst_kept) {
     std::lock_guard<std::mutex> lk(g_place_mu);
     if (probes) *probes = g_place.probes;

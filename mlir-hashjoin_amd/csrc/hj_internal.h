@@ -551,6 +551,49 @@ hipError_t filter_apply(const unsigned *words, long long nblocks, int form, int 
                         void *out_row, long long cap, unsigned long long *count, const FilterWork &ws,
                         hipStream_t st);
 
+// ---------------------------------------------------------------- star probe
+// (hj_kernels.hip, k_star) n probe rows against up to kStarMaxDims global
+// tables of one layout in one kernel (hj.h "Star probe").  Kinds = HJ_STAR_*.
+constexpr int kStarMaxDims = 4;
+enum StarKind : int { kStarInner = 0, kStarLeft = 1, kStarAnti = 2 };
+struct StarDim {
+    TableDev t;
+    const void *key;                 // this dimension's key column of the probe rows (int64 / int32 by layout)
+    void *out;                       // its payload column (int64 / int32; null: not asked for)
+    unsigned long long null_pay;     // LEFT: the payload of a row without a partner
+    int kind;
+    int lds_off;                     // set by launch_star: byte offset of the table's copy in dynamic LDS, < 0: global
+};
+struct StarArgs {                    // by value in the kernel arguments
+    StarDim d[kStarMaxDims];
+    long long n, row_base, cap;
+    void *out_row;                   // int64 positions / int32 row ids (null: not asked for)
+    unsigned long long *count;
+    unsigned long long *tiles;       // the workspace's tile counts, then offsets
+    unsigned char *bitmap;           // the workspace's result bytes
+    int first;                       // set by launch_star: the first dimension the launch walks (-1: none)
+};
+struct StarPlan {                    // host facts of one launch_star
+    int launches;
+    unsigned grid;                   // of the probe launch (decision, or the keep-all launch)
+    long long tiles;
+    int lds_dims;                    // bit d: the probe launch reads dimension d's table from LDS
+    long long lds_bytes;             // those tables together: its dynamic LDS
+};
+// Raises the maximum dynamic LDS of every k_star instantiation on the current
+// device to kLdsPerCu (a launch above 64 KiB needs it; never under capture).
+hipError_t star_prepare();
+// Kernels only.  ws: >= filter_tiles(n) + 1 tile words, exclusive_scan_sums of
+// that, filter_tiles(n) * kFilterBlock bitmap bytes (the key filter's shape).
+// Placement (the probe launch: the decision, or the keep-all launch): the
+// tables it walks in ascending size while their sum stays <= kLdsPerCu and
+// each is <= kLdsTableBytes; then a persistent grid of as many workgroups as
+// that LDS lets a CU hold, else one workgroup per tile.  The write launch walks
+// the survivors alone: global tables, one workgroup per tile.
+hipError_t launch_star(int layout, int ndims, StarArgs a, const FilterWork &ws, StarPlan *plan, hipStream_t st);
+// launches of exclusive_scan_u64 over len words (hj_radix.hip)
+int exclusive_scan_launches(unsigned long long len);
+
 hipError_t launch_gen_pkfk(unsigned long long seed, long long NR, unsigned long long hit_thr,
                            long long r0, long long nr, long long *rkey, long long *rpay,
                            long long s0, long long ns, long long *skey, long long *spay,

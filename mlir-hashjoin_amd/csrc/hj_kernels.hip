@@ -9,7 +9,8 @@
 //                                          reads, ballot-compacted output,
 //                                          one global cursor add per block
 // plus the exists probes (k_probe_exists), the positional lookup probe
-// (k_probe_lookup), the as-of probe (k_probe_asof), the expand probe's scan and global-table fill
+// (k_probe_lookup), the star probe (k_star: up to four tables per probe row),
+// the as-of probe (k_probe_asof), the expand probe's scan and global-table fill
 // (k_expand_sums, k_expand_scan_sums, k_expand_offsets, k_probe_expand),
 // the outer probe (k_probe_outer),
 // the build-side outer stages (k_probe_mark, k_emit_unmatched),
@@ -839,6 +840,332 @@ __global__ __launch_bounds__(kBlock) void k_probe_lookup(TableDev t, SrcDev src,
         for (int w = 0; w < NW; ++w) sum += s_hits[w];
         if (sum) atomicAdd(out.counter, sum);
     }
+}
+
+// ------------------------------------------------------------------ star probe
+// Star probe (hj.h "Star probe"): n probe rows against up to four built tables
+// in ONE kernel; the rows every dimension admits are kept in input order with
+// each dimension's smallest payload beside them.  k_probe_lookup's tile shape
+// -- 2048-row tiles, row slot i of thread x is row q * 2048 + i * 256 + x,
+// every row's first slot load of a dimension issued before any is resolved --
+// with the dimension loop unrolled (ND) around it.  Each table is read from its
+// copy in dynamic LDS (StarDim::lds_off >= 0, made once per workgroup) or from
+// global memory: a wave-uniform branch per dimension and tile.  A persistent grid
+// strides over the tiles; the next tile's first key column (kStarWrite: its
+// result byte) is loaded ahead, as k_probe_lookup's LDS variant does.
+//
+// MODE kStarDecide: walks the dimensions that can drop a row (INNER, ANTI) in
+//   the caller's order.  A row that failed one loads no further key and walks
+//   no further table; existence alone decides, so a walk ends at the first
+//   equal key whatever the repeat flag says.  Leaves each lane's eight result
+//   bits as one byte (bitmap[q * 256 + x], bit i) and the tile's count: the
+//   key filter's workspace shape, scanned by exclusive_scan_u64.
+// MODE kStarWrite: reads the byte, places the survivors in row order (per-slot
+//   wave prefix sums, one (slot, wave) scan per tile) and, for them alone and
+//   only for the dimensions whose payload column was passed, loads the key,
+//   walks again for the smallest payload (to the first equal key when the
+//   table's meta[1] is clear, else on to EMPTY) and stores below cap.  It is
+//   launched with one workgroup per tile and no table copy (launch_star).
+// kStarWrite and kStarAll drop no row, so they load every walked dimension's
+// keys of a tile before the first walk.
+// MODE kStarAll: no dimension can drop a row (every kind LEFT), so row j's
+//   position is j: one launch stores payloads and row ids positionally below
+//   cap and the count n.
+// A wide INT64_MIN probe key answers from the side list: it exists when
+// meta[0] != 0, and its minimum is taken once per workgroup and dimension.
+// Reads the tables, the side lists and meta[0..1]; writes no build state.
+enum StarMode : int { kStarDecide = 0, kStarWrite = 1, kStarAll = 2 };
+// Teams of kBlock threads per workgroup at most.  A persistent launch runs
+// kStarTeams: its table copies fill the LDS, so the workgroups per CU are few,
+// and a second team doubles the waves that hide each other's load latency
+// behind the same copies.  The write launch runs one (launch_star).
+constexpr int kStarTeams = 2;
+
+// A probe key in registers: 64 bits, or the 32 of an i32 column (zero-extended where it meets a slot's key).
+template <int L>
+using star_key_t = std::conditional_t<L == kWide, unsigned long long, unsigned>;
+template <int L>
+__device__ __forceinline__ star_key_t<L> star_key(const void *col, long long row) {
+    if constexpr (L == kWide) return ((const unsigned long long *)col)[row];
+    else return (unsigned)((const int *)col)[row];
+}
+
+// One dimension's walk for the rows in `rows` (bits over the lane's row slots)
+// whose keys are K: found = the rows with a partner and, MIN, RP = their
+// smallest payload.  LDS: the table's copy at dm.lds_off in s_tab is read, else
+// dm.t.slots -- a template argument, so that the slot loads are LDS reads and
+// global loads (one walk with the pointer selected at run time compiled to
+// flat loads); star_walk below takes the wave-uniform branch between the two.
+template <int L, bool MIN, bool LDS>
+__device__ __forceinline__ unsigned star_walk_t(const StarDim &dm, unsigned rows,
+                                                const star_key_t<L> (&K)[kProbeItems], unsigned long long side_n,
+                                                long long side_min, bool unique, long long (&RP)[kProbeItems]) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    extern __shared__ ulonglong2 s_tab[];
+    const slot_t *sl = LDS ? (const slot_t *)(s_tab + (dm.lds_off >> 4)) : (const slot_t *)dm.t.slots;
+    auto at = [&](unsigned long long h) -> slot_t { return sl[h]; };
+    unsigned walk = 0, found = 0;
+#pragma unroll
+    for (int i = 0; i < kProbeItems; ++i) {
+        if (!((rows >> i) & 1u)) continue;
+        if (LY::null_key(K[i])) {
+            if (side_n != 0ull) {
+                found |= 1u << i;
+                RP[i] = side_min;
+            }
+        } else {
+            walk |= 1u << i;
+        }
+    }
+    slot_t S[kProbeItems];
+    unsigned long long H[kProbeItems];
+#pragma unroll
+    for (int i = 0; i < kProbeItems; ++i) {
+        H[i] = slot_of(K[i], dm.t.shift);
+        if ((walk >> i) & 1u) S[i] = at(H[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < kProbeItems; ++i) {
+        if (!((walk >> i) & 1u)) continue;
+        slot_t sv = S[i];
+        unsigned long long hh = H[i];
+        long long best = 0x7fffffffffffffffll;
+        bool f = false;
+        while (!LY::empty(sv)) {
+            if (LY::key(sv) == K[i]) {
+                f = true;
+                if (MIN) {
+                    const long long p = (long long)LY::pay(sv);
+                    best = p < best ? p : best;
+                }
+                if (!MIN || unique) break;
+            }
+            hh = (hh + 1) & dm.t.mask;
+            sv = at(hh);
+        }
+        if (f) {
+            found |= 1u << i;
+            RP[i] = best;
+        }
+    }
+    return found;
+}
+template <int L, bool MIN>
+__device__ __forceinline__ unsigned star_walk(const StarDim &dm, unsigned rows,
+                                              const star_key_t<L> (&K)[kProbeItems], unsigned long long side_n,
+                                              long long side_min, bool unique, long long (&RP)[kProbeItems]) {
+    if (dm.lds_off >= 0) return star_walk_t<L, MIN, true>(dm, rows, K, side_n, side_min, unique, RP);   // (uniform)
+    return star_walk_t<L, MIN, false>(dm, rows, K, side_n, side_min, unique, RP);
+}
+
+template <int L, int ND, int MODE>
+__global__ __launch_bounds__(kBlock * kStarTeams) void k_star(StarArgs a) {
+    using LY = Lay<L>;
+    using slot_t = typename LY::slot_t;
+    using out_t = typename LY::out_t;
+    constexpr int NW = kBlock / 64;
+    constexpr long long kMaxPay = 0x7fffffffffffffffll;
+    __shared__ long long s_side_min[kStarMaxDims];
+    __shared__ unsigned s_cw[kProbeItems * NW];
+    extern __shared__ ulonglong2 s_tab[];
+
+    // the dimensions this launch walks, their tables' copies and side lists
+    bool walks[ND], unique[ND];
+    unsigned long long side_n[ND];
+    long long side_min[ND];
+    // a team = kBlock threads = one tile at a time; the teams of a workgroup share the table copies
+    const int tid = threadIdx.x & (kBlock - 1), team = threadIdx.x / kBlock, teams = blockDim.x / kBlock;
+    if (threadIdx.x < kStarMaxDims) s_side_min[threadIdx.x] = kMaxPay;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const StarDim &dm = a.d[d];
+        walks[d] = MODE == kStarDecide ? dm.kind != kStarLeft : dm.out != nullptr;
+        if (dm.lds_off >= 0) {   // (the host plans a copy only for a dimension this launch walks)
+            ulonglong2 *dst = s_tab + (dm.lds_off >> 4);
+            const unsigned long long n16 = (dm.t.mask + 1) * sizeof(slot_t) / 16;
+            const ulonglong2 *g16 = (const ulonglong2 *)dm.t.slots;
+            for (unsigned long long j = threadIdx.x; j < n16; j += blockDim.x) dst[j] = g16[j];
+        }
+        unique[d] = true;
+        side_n[d] = 0ull;
+        if (walks[d]) {
+            if (MODE != kStarDecide)
+                unique[d] = __hip_atomic_load(&dm.t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull;
+            if (L == kWide) side_n[d] = dm.t.meta[0];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        side_min[d] = kMaxPay;
+        if (MODE == kStarDecide || side_n[d] == 0ull) continue;   // (uniform)
+        long long m = kMaxPay;
+        for (unsigned long long j = threadIdx.x; j < side_n[d]; j += blockDim.x) {
+            const long long p = (long long)a.d[d].t.side[j];
+            m = p < m ? p : m;
+        }
+        atomicMin(&s_side_min[d], m);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+        if (MODE != kStarDecide && side_n[d] != 0ull) side_min[d] = s_side_min[d];
+
+    const int lane = tid & 63, wv = tid >> 6;
+    const unsigned long long nt = (unsigned long long)((a.n + kProbeTile - 1) / kProbeTile);
+    auto row_of = [&](unsigned long long q, int i) { return (long long)q * kProbeTile + (long long)i * kBlock + tid; };
+    auto valid_of = [&](unsigned long long q) {
+        unsigned v = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) v |= row_of(q, i) < a.n ? 1u << i : 0u;
+        return v;
+    };
+    // dimension d's keys of tile q for the rows in `rows`
+    auto load_keys = [&](int d, unsigned long long q, unsigned rows, star_key_t<L> (&K)[kProbeItems]) {
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) K[i] = (rows >> i) & 1u ? star_key<L>(a.d[d].key, row_of(q, i)) : star_key_t<L>(0);
+    };
+    // loaded ahead: the first walked dimension's keys of the next tile (kStarWrite: the next tile's result byte)
+    [[maybe_unused]] star_key_t<L> KN[kProbeItems] = {};
+    [[maybe_unused]] unsigned byte_n = 0;
+    // the workgroup's teams take tiles qb .. qb + teams - 1 together and step by the grid's teams: every team
+    // of a workgroup runs the same number of steps (the decision's barrier), a team past the last tile an empty one
+    const unsigned long long step = (unsigned long long)gridDim.x * teams, q0 = (unsigned long long)blockIdx.x * teams + team;
+    if (q0 < nt) {
+        if constexpr (MODE == kStarWrite) {
+            byte_n = a.bitmap[q0 * kBlock + tid];
+        } else {
+#pragma unroll
+            for (int d = 0; d < ND; ++d)
+                if (d == a.first) load_keys(d, q0, valid_of(q0), KN);
+        }
+    }
+    [[maybe_unused]] unsigned par = 0;
+    for (unsigned long long qb = (unsigned long long)blockIdx.x * teams; qb < nt; qb += step) {
+        const unsigned long long q = qb + team, qn = q + step;
+        const bool active = q < nt;
+        unsigned alive;
+        [[maybe_unused]] star_key_t<L> KF[kProbeItems];
+        if constexpr (MODE == kStarWrite) {
+            alive = active ? byte_n : 0u;
+            if (qn < nt) byte_n = a.bitmap[qn * kBlock + tid];
+        } else {
+            alive = active ? valid_of(q) : 0u;
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i) KF[i] = KN[i];
+            if (qn < nt) {
+#pragma unroll
+                for (int d = 0; d < ND; ++d)
+                    if (d == a.first) load_keys(d, qn, valid_of(qn), KN);
+            }
+        }
+        if constexpr (MODE == kStarDecide) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                if (!walks[d]) continue;   // (uniform)
+                star_key_t<L> K[kProbeItems];
+                long long RP[kProbeItems];
+                if (d == a.first) {
+#pragma unroll
+                    for (int i = 0; i < kProbeItems; ++i) K[i] = KF[i];
+                } else {
+                    load_keys(d, q, alive, K);
+                }
+                const unsigned found = star_walk<L, false>(a.d[d], alive, K, side_n[d], kMaxPay, true, RP);
+                alive &= a.d[d].kind == kStarInner ? found : ~found;
+            }
+            if (active) a.bitmap[q * kBlock + tid] = (unsigned char)alive;
+            unsigned c = (unsigned)__popc(alive);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+            // one barrier per step: the wave counts alternate between two sets, and nobody reaches the set's
+            // next writes (two steps on) before everybody has passed the barrier in between
+            unsigned *cw = s_cw + (par * kStarTeams + team) * NW;
+            par ^= 1u;
+            if (lane == 0) cw[wv] = c;
+            __syncthreads();
+            if (tid == 0 && active) {
+                unsigned s = 0;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) s += cw[w];
+                a.tiles[q] = s;
+            }
+        } else {
+            // the rows' output positions: row order = (slot, wave, lane)
+            unsigned long long O[kProbeItems];
+            if constexpr (MODE == kStarWrite) {
+                const unsigned long long tb = a.tiles[q];
+                if (tb >= (unsigned long long)a.cap || a.tiles[q + 1] == tb) continue;   // (uniform) nothing of this tile is stored
+                unsigned lpre[kProbeItems];
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i) {
+                    const unsigned c = (alive >> i) & 1u;
+                    const unsigned xs = wave_incl_add(c);
+                    lpre[i] = xs - c;
+                    if (lane == 63) s_cw[i * NW + wv] = xs;
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    unsigned run = 0;
+#pragma unroll
+                    for (int j = 0; j < kProbeItems * NW; ++j) {
+                        const unsigned v = s_cw[j];
+                        s_cw[j] = run;
+                        run += v;
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i) O[i] = tb + s_cw[i * NW + wv] + lpre[i];
+                __syncthreads();   // s_cw is the next tile's too
+            } else {
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i) O[i] = (unsigned long long)row_of(q, i);
+            }
+#pragma unroll
+            for (int i = 0; i < kProbeItems; ++i)
+                if (O[i] >= (unsigned long long)a.cap) alive &= ~(1u << i);
+            if (a.out_row) {
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i)
+                    if ((alive >> i) & 1u) ((out_t *)a.out_row)[O[i]] = (out_t)(a.row_base + row_of(q, i));
+            }
+            // no row is dropped from here on: every dimension's keys are loaded before the first walk
+            star_key_t<L> KA[ND][kProbeItems];
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                if (!walks[d]) continue;   // (uniform)
+                if (MODE == kStarAll && d == a.first) {
+#pragma unroll
+                    for (int i = 0; i < kProbeItems; ++i) KA[d][i] = KF[i];
+                } else {
+                    load_keys(d, q, alive, KA[d]);
+                }
+            }
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                if (!walks[d]) continue;   // (uniform)
+                long long RP[kProbeItems];
+                const unsigned found = star_walk<L, true>(a.d[d], alive, KA[d], side_n[d], side_min[d], unique[d], RP);
+                out_t *o = (out_t *)a.d[d].out;
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i)
+                    if ((alive >> i) & 1u) o[O[i]] = (out_t)((found >> i) & 1u ? RP[i] : (long long)a.d[d].null_pay);
+            }
+        }
+    }
+    if (MODE != kStarDecide && blockIdx.x == 0 && threadIdx.x == 0)
+        *a.count = MODE == kStarWrite ? a.tiles[nt] : (unsigned long long)a.n;
+    if (MODE == kStarDecide && blockIdx.x == 0 && threadIdx.x == 0) a.tiles[nt] = 0ull;
+}
+
+// The star probe's counter without a write launch: the count form (*src, the
+// scan's total), n == 0 and the keep-all count form (imm).  A kernel, not a
+// memset: see k_counter_clear below.
+__global__ __launch_bounds__(64) void k_star_total(const unsigned long long *src, unsigned long long imm,
+                                                   unsigned long long *count) {
+    if (threadIdx.x == 0) *count = src ? *src : imm;
 }
 
 // ------------------------------------------------------------------ as-of probe
@@ -2454,6 +2781,126 @@ hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src,
     if (layout == kWide && src.form == kCols64) return launch(int_c<kWide>{}, int_c<kCols64>{});
     if (layout == kNarrow && src.form == kCol32) return launch(int_c<kNarrow>{}, int_c<kCol32>{});
     return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------- star probe
+namespace {
+static_assert(kFilterTile == kProbeTile && kFilterBlock == kBlock, "the star probe shares the key filter's workspace shape");
+typedef void (*star_kernel_t)(StarArgs);
+template <int L, int MODE>
+star_kernel_t star_kernel_nd(int ndims) {
+    switch (ndims) {
+    case 1: return k_star<L, 1, MODE>;
+    case 2: return k_star<L, 2, MODE>;
+    case 3: return k_star<L, 3, MODE>;
+    case 4: return k_star<L, 4, MODE>;
+    default: return nullptr;
+    }
+}
+star_kernel_t star_kernel(int layout, int ndims, int mode) {
+    if (layout != kWide && layout != kNarrow) return nullptr;
+    const bool w = layout == kWide;
+    switch (mode) {
+    case kStarDecide: return w ? star_kernel_nd<kWide, kStarDecide>(ndims) : star_kernel_nd<kNarrow, kStarDecide>(ndims);
+    case kStarWrite: return w ? star_kernel_nd<kWide, kStarWrite>(ndims) : star_kernel_nd<kNarrow, kStarWrite>(ndims);
+    case kStarAll: return w ? star_kernel_nd<kWide, kStarAll>(ndims) : star_kernel_nd<kNarrow, kStarAll>(ndims);
+    default: return nullptr;
+    }
+}
+}  // namespace
+
+hipError_t star_prepare() {
+    for (int layout : {(int)kWide, (int)kNarrow})
+        for (int nd = 1; nd <= kStarMaxDims; ++nd)
+            for (int mode : {(int)kStarDecide, (int)kStarWrite, (int)kStarAll}) {
+                const hipError_t e = hipFuncSetAttribute((const void *)star_kernel(layout, nd, mode),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
+                if (e != hipSuccess) return e;
+            }
+    return hipSuccess;
+}
+
+hipError_t launch_star(int layout, int ndims, StarArgs a, const FilterWork &ws, StarPlan *plan, hipStream_t st) {
+    if (ndims < 1 || ndims > kStarMaxDims || (layout != kWide && layout != kNarrow)) return hipErrorInvalidValue;
+    a.tiles = ws.tiles;
+    a.bitmap = ws.bitmap;
+    *plan = StarPlan{1, 0u, 0, 0, 0};
+    bool drops = false;
+    for (int d = 0; d < ndims; ++d) drops |= a.d[d].kind != kStarLeft;
+    // no tile to walk: the counter alone (keep-all: M = n whatever the tables hold)
+    if (a.n <= 0 || (!drops && a.cap <= 0)) {
+        hipLaunchKernelGGL(k_star_total, dim3(1), dim3(64), 0, st, (const unsigned long long *)nullptr,
+                           (unsigned long long)(a.n > 0 ? a.n : 0), a.count);
+        return hipGetLastError();
+    }
+    // placement: the tables the probe launch walks (the decision's INNER and
+    // ANTI dimensions; keep-all: the ones with a payload column), ascending,
+    // while they fit
+    const size_t sb = layout == kWide ? 16 : 8;
+    size_t bytes[kStarMaxDims];
+    int order[kStarMaxDims], no = 0;
+    for (int d = 0; d < ndims; ++d) {
+        bytes[d] = (size_t)(a.d[d].t.mask + 1) * sb;
+        if (drops ? a.d[d].kind == kStarLeft : !a.d[d].out) continue;   // the probe launch does not walk it
+        int j = no++;
+        for (; j > 0 && bytes[order[j - 1]] > bytes[d]; --j) order[j] = order[j - 1];
+        order[j] = d;
+    }
+    int lds_dims = 0;
+    size_t lds_bytes = 0;
+    for (int j = 0; j < no; ++j) {
+        const size_t b = bytes[order[j]];
+        if (b > (size_t)kLdsTableBytes || lds_bytes + b > (size_t)kLdsPerCu) break;
+        lds_dims |= 1 << order[j];
+        lds_bytes += b;
+    }
+    // the probe launch: as many workgroups of kStarTeams teams as its table
+    // copies let a CU hold stride over the tiles; without a copy, one workgroup
+    // of one team per tile.  The write
+    // launch walks the survivors alone: no copies (a copy per workgroup costs
+    // what the walks of a few rows do not give back) and one workgroup per tile.
+    const unsigned tiles = grid_for(a.n, kProbeTile);
+    unsigned grid = tiles, teams = 1;
+    if (lds_bytes) {
+        unsigned per_cu = (unsigned)(kLdsPerCu / lds_bytes);
+        per_cu = per_cu > 8 ? 8 : per_cu;
+        teams = kStarTeams;   // (per_cu <= 8 / teams would do for the wave slots: 8 x 2 x 4 waves are a CU's 32)
+        if (per_cu * teams > 8) per_cu = 8 / teams;
+        const unsigned most = (unsigned)cu_count() * per_cu, want = (tiles + teams - 1) / teams;
+        grid = most < want ? most : want;
+    }
+    *plan = StarPlan{0, grid, (long long)tiles, lds_dims, (long long)lds_bytes};
+    auto launch = [&](int mode) {
+        StarArgs b = a;
+        size_t off = 0;
+        b.first = -1;
+        for (int d = 0; d < ndims; ++d) {
+            const bool walks = mode == kStarDecide ? b.d[d].kind != kStarLeft : b.d[d].out != nullptr;
+            b.d[d].lds_off = -1;
+            if (!walks) continue;
+            if (b.first < 0) b.first = d;
+            if (mode != kStarWrite && ((lds_dims >> d) & 1)) {
+                b.d[d].lds_off = (int)off;
+                off += bytes[d];
+            }
+        }
+        const bool write = mode == kStarWrite;
+        hipLaunchKernelGGL(star_kernel(layout, ndims, mode), dim3(write ? tiles : grid),
+                           dim3(kBlock * (write ? 1u : teams)), off, st, b);
+        ++plan->launches;
+        return hipGetLastError();
+    };
+    if (!drops) return launch(kStarAll);
+    hipError_t e = launch(kStarDecide);
+    if (e != hipSuccess) return e;
+    e = exclusive_scan_u64(ws.tiles, (unsigned long long)tiles + 1, ws.sums, st);
+    if (e != hipSuccess) return e;
+    plan->launches += exclusive_scan_launches((unsigned long long)tiles + 1);
+    if (a.cap > 0) return launch(kStarWrite);
+    hipLaunchKernelGGL(k_star_total, dim3(1), dim3(64), 0, st, (const unsigned long long *)(ws.tiles + tiles), 0ull,
+                       a.count);
+    ++plan->launches;
+    return hipGetLastError();
 }
 
 hipError_t launch_probe_asof(const TableDev &t, int layout, int kind, const SrcDev &src, const void *bound,

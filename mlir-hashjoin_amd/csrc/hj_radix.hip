@@ -4426,6 +4426,8 @@ hipError_t exclusive_scan_u64(unsigned long long *v, unsigned long long len, uns
 
 size_t exclusive_scan_sums(unsigned long long len) { return (size_t)(len / kScanBlock + 2); }
 
+int exclusive_scan_launches(unsigned long long len) { return len == 0 ? 0 : (blocks_for(len, kScanBlock) > 1 ? 2 : 1); }
+
 unsigned long long radix_join_items(const RadixPlan &pl, unsigned long long s_runs) {
     // the smallest item of any shape (work_map sizes items by its kernel's sub-chunk)
     constexpr u64 sub = (u64)kFastNT * kFastSI;

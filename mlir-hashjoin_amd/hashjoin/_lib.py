@@ -55,6 +55,15 @@ HJ_FILTER_REJECT = 1
 FILTER_BLOCK = 256
 FILTER_TILE = 2048
 FILTER_GRID_PER_CU = 8
+# the star probe (hj_kernels.hip, k_star: 2048-row tiles; a table of <= STAR_LDS_TABLE_BYTES is probed from LDS while
+# the LDS-resident tables together stay <= STAR_LDS_BUDGET_BYTES)
+HJ_STAR_MAX_DIMS = 4
+HJ_STAR_INNER = 0
+HJ_STAR_LEFT = 1
+HJ_STAR_ANTI = 2
+STAR_TILE = 2048
+STAR_LDS_TABLE_BYTES = 64 * 1024
+STAR_LDS_BUDGET_BYTES = 128 * 1024
 HJ_GROUP_MATCHED = 0
 HJ_GROUP_ALL = 1
 HJ_OUTER_BUILD = 1
@@ -161,6 +170,15 @@ def _load():
         "hj_dev_filter_apply_i64": (_int, [_vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_filter_apply_tuples_i64": (_int, [_vp, _int, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_filter_apply_i32": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+        "hj_star_create": (_vp, [_int]),
+        "hj_star_destroy": (None, [_vp]),
+        "hj_star_reserve": (_int, [_vp, _i64]),
+        "hj_star_last_plan": (_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(C.c_int),
+                                     C.POINTER(_i64)]),
+        "hj_dev_star_i64": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(_vp), C.POINTER(_i64), _i64,
+                                   C.POINTER(_vp), _vp, _i64, _vp, _vp]),
+        "hj_dev_star_i32": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(_vp), C.POINTER(C.c_int32),
+                                   _i64, _i64, C.POINTER(_vp), _vp, _i64, _vp, _vp]),
         "hj_dev_partition_i64": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_dev_partition_tuples_i64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_partition_of": (_int, [_i64, _int]),

@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from ._lib import (HJ_ASOF_BACKWARD, HJ_ASOF_FORWARD, HJ_ASOF_STRICT, HJ_ERR_RANGE, HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_FILTER_PASS, HJ_FILTER_REJECT, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_KEYS_MAX_COLS, HJ_OK, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STRATEGY_AUTO,
+from ._lib import (HJ_ASOF_BACKWARD, HJ_ASOF_FORWARD, HJ_ASOF_STRICT, HJ_ERR_RANGE, HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_FILTER_PASS, HJ_FILTER_REJECT, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_KEYS_MAX_COLS, HJ_OK, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STAR_ANTI, HJ_STAR_INNER, HJ_STAR_LEFT, HJ_STAR_MAX_DIMS, HJ_STRATEGY_AUTO,
                    HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, HJError, check, lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
@@ -32,6 +32,7 @@ GROUP_AGGS = ("count", "sum", "min", "max")
 EXPAND_KINDS = {"inner": HJ_EXPAND_INNER, "outer": HJ_EXPAND_OUTER}
 FILTER_KINDS = {"pass": HJ_FILTER_PASS, "reject": HJ_FILTER_REJECT}
 ASOF_DIRECTIONS = {"backward": HJ_ASOF_BACKWARD, "forward": HJ_ASOF_FORWARD}
+STAR_KINDS = {"inner": HJ_STAR_INNER, "left": HJ_STAR_LEFT, "anti": HJ_STAR_ANTI}
 
 
 def _ptr(t):
@@ -337,6 +338,138 @@ class KeyFilter:
     def count(self, skey, kind="pass", stream=None, sync=True):
         """How many rows of S pass ('pass') / fail ('reject')."""
         cnt = self.apply_into(skey, kind=kind, stream=stream)
+        return int(cnt.item()) if sync else cnt
+
+
+class StarProbe:
+    """A star probe (hj.h "Star probe"): one pass of n probe rows (a fact
+    table) over up to four built dimensions; the rows every dimension admits
+    come back in input order with each dimension's payload beside them.
+
+        star = StarProbe(0)
+        rows, (d_pay, p_pay) = star.probe([(date_hj, f_date, "inner"), (part_hj, f_part, "left", -1)])
+
+    A dimension is (HashJoin, skey, how[, null]): a context holding a build
+    under the global strategy, this dimension's key column of the probe rows,
+    how in "inner" | "left" | "anti", and for "left" the payload of a row
+    without a partner (default -1).  The dimensions are walked in the order
+    given: put the most selective first.  All key columns share a dtype (int64,
+    or int32 for hj_dev_build_i32 builds) and a length."""
+
+    def __init__(self, device=0):
+        if not torch.cuda.is_available():
+            raise RuntimeError("StarProbe needs a HIP device (no CPU fallback)")
+        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        self._count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._s = lib.hj_star_create(self.device.index)
+        if not self._s:
+            raise HJError("hj_star_create failed: " + lib.hj_last_error().decode())
+
+    def close(self):
+        if getattr(self, "_s", None):
+            lib.hj_star_destroy(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reserve(self, rows):
+        """Size the workspace for `rows` probe rows (grow-only); after it the
+        probes launch kernels only and can be captured in a graph."""
+        check(lib.hj_star_reserve(self._s, int(rows)), "hj_star_reserve")
+
+    @property
+    def last_plan(self):
+        """Host facts of the last probe: kernel launches, the probe launch's
+        grid and tiles, the dimensions probed from LDS (a list of booleans up
+        to the highest one set; lds_mask the bits) and their tables' bytes."""
+        la, g, ld = C.c_int(0), C.c_int(0), C.c_int(0)
+        t, b = C.c_int64(0), C.c_int64(0)
+        check(lib.hj_star_last_plan(self._s, C.byref(la), C.byref(g), C.byref(t), C.byref(ld), C.byref(b)),
+              "hj_star_last_plan")
+        return dict(launches=la.value, grid=g.value, tiles=t.value, lds_mask=ld.value,
+                    lds_dims=[bool((ld.value >> d) & 1) for d in range(HJ_STAR_MAX_DIMS)], lds_bytes=b.value)
+
+    @staticmethod
+    def _dims(dims):
+        """(contexts, key columns, kinds, nulls) of a dimension list; raises on a malformed one."""
+        if not 1 <= len(dims) <= HJ_STAR_MAX_DIMS:
+            raise ValueError(f"a star probe takes 1..{HJ_STAR_MAX_DIMS} dimensions")
+        hjs, keys, kinds, nulls = [], [], [], []
+        for d in dims:
+            if len(d) not in (3, 4):
+                raise ValueError("a dimension is (HashJoin, skey, how[, null])")
+            hj, skey, how = d[:3]
+            if not isinstance(hj, HashJoin):
+                raise TypeError("a dimension's first element is the HashJoin holding its build")
+            if not isinstance(skey, torch.Tensor) or skey.dim() != 1 or skey.dtype not in (torch.int64, torch.int32):
+                raise TypeError("a dimension's key column must be a 1-D int64 / int32 tensor")
+            _need_cuda(skey)
+            hjs.append(hj)
+            keys.append(skey)
+            kinds.append(STAR_KINDS[how])
+            nulls.append(int(d[3]) if len(d) == 4 and d[3] is not None else -1)
+        if any(k.dtype != keys[0].dtype or k.numel() != keys[0].numel() for k in keys):
+            raise ValueError("the dimensions' key columns must share a dtype and a length")
+        return hjs, keys, kinds, nulls
+
+    def probe_into(self, dims, out_pay=None, out_row=None, count=None, row_base=0, stream=None):
+        """The raw call: writes min(M, cap) qualifying rows, in input order,
+        into the outputs given -- out_pay a list with one column or None per
+        dimension, out_row the source positions (i32: row ids) -- cap being
+        their common length (none: the count form); `count` (int64 device
+        tensor) receives M.  Returns count."""
+        hjs, keys, kinds, nulls = self._dims(dims)
+        nd, dt, n = len(dims), keys[0].dtype, keys[0].numel()
+        out_pay = [None] * nd if out_pay is None else list(out_pay)
+        if len(out_pay) != nd:
+            raise ValueError("out_pay needs one entry (a column or None) per dimension")
+        outs = [o for o in out_pay + [out_row] if o is not None]
+        _need_cuda(*outs)
+        if any(o.dtype != dt or o.dim() != 1 for o in outs):
+            raise ValueError("output columns take the key columns' dtype")
+        cap = outs[0].shape[0] if outs else 0
+        if any(o.shape[0] != cap for o in outs):
+            raise ValueError("output columns differ in length")
+        count = self._count if count is None else count
+        a_ctx = (C.c_void_p * nd)(*[h._ctx for h in hjs])
+        a_kind = (C.c_int * nd)(*kinds)
+        a_key = (C.c_void_p * nd)(*[k.data_ptr() for k in keys])
+        a_out = (C.c_void_p * nd)(*[None if o is None else o.data_ptr() for o in out_pay])
+        st = _stream(self.device, stream)
+        if dt == torch.int64:
+            a_null = (C.c_int64 * nd)(*nulls)
+            check(lib.hj_dev_star_i64(self._s, nd, a_ctx, a_kind, a_key, a_null, n, a_out, _ptr(out_row), cap,
+                                      _ptr(count), st), "hj_dev_star_i64")
+        else:
+            a_null = (C.c_int32 * nd)(*nulls)
+            check(lib.hj_dev_star_i32(self._s, nd, a_ctx, a_kind, a_key, a_null, n, int(row_base), a_out,
+                                      _ptr(out_row), cap, _ptr(count), st), "hj_dev_star_i32")
+        return count
+
+    def probe(self, dims, capacity=None, row_base=0, stream=None):
+        """(rows, [payload columns]): the source positions (i32: row ids) of
+        the qualifying rows in input order and, per dimension, its payload
+        column (None for an "anti" dimension).  Outputs are sized |S| rows, or
+        `capacity` with one more call at the exact M.  Synchronises to read M."""
+        _, keys, kinds, _ = self._dims(dims)
+        n, dt = keys[0].numel(), keys[0].dtype
+        cap = max(1, n if capacity is None else int(capacity))
+        for _ in range(2):
+            rows = torch.empty(cap, dtype=dt, device=self.device)
+            pays = [None if k == HJ_STAR_ANTI else torch.empty(cap, dtype=dt, device=self.device) for k in kinds]
+            m = int(self.probe_into(dims, pays, rows, row_base=row_base, stream=stream).item())
+            if m <= cap:
+                return rows[:m], [None if p is None else p[:m] for p in pays]
+            cap = m
+        raise RuntimeError("star probe output did not fit after resizing")
+
+    def count(self, dims, stream=None, sync=True):
+        """How many rows qualify under every dimension."""
+        cnt = self.probe_into(dims, stream=stream)
         return int(cnt.item()) if sync else cnt
 
 
@@ -1439,6 +1572,37 @@ class HashJoin:
 
 
 # ------------------------------------------------------------------ datagen
+def star_join(dims, device=None, stream=None):
+    """A star join in one call: dims = [(rkey, rpay, skey, how[, null]), ...],
+    one entry per dimension -- its build columns (rpay None for int32 keys:
+    row ids), this dimension's key column of the fact rows, how in "inner" |
+    "left" | "anti" and for "left" the payload of a row without a partner
+    (default -1).  Builds one HashJoin per dimension under the global strategy,
+    probes them with one StarProbe and returns (rows, [payload columns]): the
+    qualifying fact rows' positions in input order and per dimension its
+    payload column (None for "anti").  Synchronises to read M."""
+    if not dims:
+        raise ValueError("star_join needs at least one dimension")
+    dev = dims[0][2].device.index if device is None else device
+    hjs, star = [], StarProbe(dev)
+    try:
+        probe_dims = []
+        for d in dims:
+            if len(d) not in (4, 5):
+                raise ValueError("a dimension is (rkey, rpay, skey, how[, null])")
+            rkey, rpay, skey, how = d[:4]
+            hj = HashJoin(dev)
+            hjs.append(hj)
+            hj.set_strategy("global")
+            hj.build_table(rkey, rpay, stream=stream)
+            probe_dims.append((hj, skey, how, d[4] if len(d) == 5 else -1))
+        return star.probe(probe_dims, stream=stream)
+    finally:
+        star.close()   # (waits for the device before the contexts go)
+        for hj in hjs:
+            hj.close()
+
+
 U64_MAX = (1 << 64) - 1
 
 
