@@ -912,6 +912,95 @@ int hj_dev_star_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds
                     const int32_t null_row[], int64_t n, int64_t row_base, int32_t *const out_pay[], int32_t *out_row,
                     int64_t out_cap, uint64_t *d_count, void *stream);
 
+/* ------------------------------------------------------------ Star aggregate
+ * GROUP BY over a star probe's qualifying rows in ONE pass of the fact table:
+ * the rows every dimension admits are grouped by dimension payloads and one
+ * fact column is aggregated per group.  No per-row result reaches memory: the
+ * key columns are read once, the value column for the qualifying rows only,
+ * and the group table is all that is written.
+ *
+ * dims, kinds, skeys, the null array, c_d(j), p_d(j), the three kinds, which
+ * rows qualify, INT64_MIN keys, empty builds, the same context passed twice,
+ * radix-only builds (HJ_ERR_STATE) and the contexts being only read: all as
+ * "Star probe" above.
+ *
+ * Group key.  Let P_d(j) be p_d(j) when c_d(j) > 0, else (LEFT only) the
+ * dimension's null value; i32: both sign-extended to int64.  A qualifying row
+ * j has the group key
+ *     g(j) = sum over the dimensions with gshift[d] >= 0 of
+ *            ((uint64)(P_d(j) - gbase[d]) << gshift[d])          (mod 2^64)
+ * gshift[d] is -1 (the dimension takes no part in the key) or 0..63; gbase ==
+ * NULL means all zeros.  This is the composite keys' pack formula with lo =
+ * gbase and shift = gshift: a sealed codec over the grouped payload columns
+ * supplies both arrays and its unpack turns out_key back into the columns.
+ * The arithmetic wraps, so g is defined for every input; keeping the fields
+ * apart is the caller's business.  With every gshift at -1 all qualifying rows
+ * form one group with key 0.  With no qualifying row there is no group (M =
+ * 0): GROUP BY semantics, not a scalar aggregate's one row.
+ *
+ * Result.  One row (key, cnt, sum, min, max) per distinct g over the
+ * qualifying rows, every column int64 in both forms: exactly what
+ * hj_dev_aggregate_i64 returns over the columns (g(j), sval[j]) of the
+ * qualifying rows.  sum wraps, min / max are signed extremes, i32 sval is
+ * sign-extended; INT64_MIN and INT64_MAX are values like any other, and a
+ * group key that comes out as the INT64_MIN word is a key like any other.  Row
+ * order is unspecified; the rest is a function of the data alone, bit-equal
+ * across runs and table placements.
+ * Any output may be NULL and is then neither computed nor stored.  sval may be
+ * NULL when none of sum / min / max is passed; sval == NULL with one of them is
+ * HJ_ERR_ARG.  n == 0 takes null columns.  out_cap == 0 with all five outputs
+ * NULL is the count form; out_cap > 0 with all five NULL, or out_cap == 0 with
+ * any of them, is HJ_ERR_ARG.  *d_count = G, the number of distinct groups,
+ * exactly, even when G > out_cap; nothing is written at or past out_cap.
+ *
+ * Group table.  The star object owns it: a wide (int64-key) table with the
+ * group probe's accumulators beside it, for both forms.
+ * hj_star_reserve_groups sizes it (grow-only) to the smallest power of two >=
+ * max(2 * max_groups, 2048) slots; hj_star_group_capacity returns that (0
+ * before the first reserve).  A call before any reserve is HJ_ERR_STATE.
+ * G <= max_groups never overflows.  G > max_groups gives either the exact
+ * result or bit 63 of *d_count with the result invalid (nothing is stored) --
+ * never a wrong result without the bit, and never an unbounded walk: the
+ * insert-or-find is a counted loop of at most `capacity` steps, and the flag it
+ * sets is read at the start of every tile and ends the pass.
+ *
+ * Errors, in this order: a null star (HJ_ERR_ARG, "null star", before any
+ * device is touched); ndims outside 1..HJ_STAR_MAX_DIMS or a null dims, kinds,
+ * skeys, null-value array or gshift (HJ_ERR_ARG); per dimension in index order
+ * a null context, a kind outside the three, a context of another device, a
+ * gshift outside -1..63, an ANTI dimension with gshift >= 0 (it has no
+ * payload) (all HJ_ERR_ARG), then no build of that layout, or no global table
+ * (HJ_ERR_STATE naming the dimension); no group reserve (HJ_ERR_STATE); a null
+ * count pointer; n < 0 or a null key column with n > 0; the sval rule; the
+ * output rules (HJ_ERR_ARG); HJ_ERR_NOMEM (hj_star_reserve_groups).
+ *
+ * Launches.  Asynchronous on the stream and, after hj_star_reserve_groups,
+ * kernels only -- no memset, no allocation, no synchronisation: the group
+ * table's fill, the accumulators' fill (it zeroes the counter), one pass over
+ * the fact rows (n > 0) and the emit.  The dimensions' builds followed by this
+ * call capture as a LINEAR graph that, replayed, follows new data in the same
+ * buffers.  There is no per-row workspace: hj_star_reserve is not needed.
+ * The pass walks the dimensions that can drop a row (INNER, ANTI) in the
+ * caller's order -- a grouped one once, for its smallest payload -- then, for
+ * the surviving rows alone, the grouped LEFT ones; a LEFT dimension with
+ * gshift -1 is never read.  The tables it walks go to LDS in ascending size
+ * as the star probe's do, into what a CU's 160 KiB leave beside the kernel's
+ * own 18 KiB collapse table and into no more than 128 KiB.
+ * hj_star_last_plan reports this call like a star probe: the launches, the
+ * pass's grid and tiles, the LDS-resident dimensions and their bytes. */
+int hj_star_reserve_groups(hj_star *s, int64_t max_groups);
+int64_t hj_star_group_capacity(const hj_star *s);
+int hj_dev_star_aggregate_i64(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
+                              const int64_t *const skeys[], const int64_t null_pay[], const int gshift[],
+                              const int64_t gbase[], const int64_t *sval, int64_t n, int64_t *out_key, int64_t *out_cnt,
+                              int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap, uint64_t *d_count,
+                              void *stream);
+int hj_dev_star_aggregate_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
+                              const int32_t *const skeys[], const int32_t null_row[], const int gshift[],
+                              const int64_t gbase[], const int32_t *sval, int64_t n, int64_t *out_key, int64_t *out_cnt,
+                              int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap, uint64_t *d_count,
+                              void *stream);
+
 /* Radix partition of rows into nparts (1..8192) groups by a key hash independent of
  * the table's slot hash: out_tuples (2*n int64) receives packed {key, pay}
  * tuples grouped by partition in order 0..nparts-1, d_counts (nparts uint64)

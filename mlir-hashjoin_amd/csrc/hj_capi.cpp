@@ -3021,6 +3021,9 @@ struct hj_star {
     int64_t work_rows = -1;      // rows the workspace admits
     hj::FilterWork ws{nullptr, nullptr, nullptr};
     hj::StarPlan plan{0, 0u, 0, 0, 0};
+    // the star aggregate's group table (wide) with its accumulators and two meta words, ONE grow-only allocation
+    void *groups = nullptr;      // device
+    int group_bits = 0;          // capacity 2^group_bits (0: no reserve yet)
 };
 
 namespace {
@@ -3103,6 +3106,90 @@ int do_star(hj_star *s, int layout, int ndims, hj_ctx *const dims[], const int k
     return HJ_OK;
 }
 
+// The group table's parts inside hj_star::groups: slots, then count, sum, min and max of slots + 1 entries, then meta.
+struct StarGroups {
+    hj::TableDev t;
+    hj::GroupAcc acc;
+};
+size_t star_groups_bytes(int bits) {
+    const size_t cap = size_t(1) << bits;
+    return cap * 16 + 4 * (cap + 1) * 8 + 64;
+}
+StarGroups star_groups(const hj_star *s) {
+    const size_t cap = size_t(1) << s->group_bits, col = (cap + 1) * 8;
+    char *p = (char *)s->groups;
+    StarGroups g;
+    g.t.slots = p;
+    g.t.mask = cap - 1;
+    g.t.shift = 64 - s->group_bits;
+    g.t.side = nullptr;
+    g.acc.cnt = p + cap * 16;
+    g.acc.sum = (unsigned long long *)(p + cap * 16 + col);
+    g.acc.mn = p + cap * 16 + 2 * col;
+    g.acc.mx = p + cap * 16 + 3 * col;
+    g.t.meta = (unsigned long long *)(p + cap * 16 + 4 * col);
+    return g;
+}
+
+// Both star aggregate entry points behind their casts: the checks in hj.h's order, then the launches.
+int do_star_aggregate(hj_star *s, int layout, int ndims, hj_ctx *const dims[], const int kinds[],
+                      const void *const skeys[], const unsigned long long null_pay[], const int gshift[],
+                      const int64_t gbase[], const void *sval, int64_t n, void *out_key, void *out_cnt, void *out_sum,
+                      void *out_min, void *out_max, int64_t cap, uint64_t *d_count, void *stream) {
+    if (!s) HJ_FAIL(HJ_ERR_ARG, "null star");
+    if (ndims < 1 || ndims > HJ_STAR_MAX_DIMS)
+        HJ_FAIL(HJ_ERR_ARG, "star aggregate: ndims must be in 1.." + std::to_string(HJ_STAR_MAX_DIMS));
+    if (!dims || !kinds || !skeys || !null_pay || !gshift)
+        HJ_FAIL(HJ_ERR_ARG, "star aggregate: null dims, kinds, skeys, null-value or gshift array");
+    for (int d = 0; d < ndims; ++d) {
+        const std::string who = "star aggregate: dimension " + std::to_string(d);
+        const hj_ctx *c = dims[d];
+        if (!c) HJ_FAIL(HJ_ERR_ARG, who + ": null context");
+        if (kinds[d] != HJ_STAR_INNER && kinds[d] != HJ_STAR_LEFT && kinds[d] != HJ_STAR_ANTI)
+            HJ_FAIL(HJ_ERR_ARG, who + ": kind must be HJ_STAR_INNER, HJ_STAR_LEFT or HJ_STAR_ANTI");
+        if (c->device != s->device) HJ_FAIL(HJ_ERR_ARG, who + ": a context of another device");
+        if (gshift[d] < -1 || gshift[d] > 63) HJ_FAIL(HJ_ERR_ARG, who + ": gshift must be -1 or in 0..63");
+        if (kinds[d] == HJ_STAR_ANTI && gshift[d] >= 0)
+            HJ_FAIL(HJ_ERR_ARG, who + ": an ANTI dimension has no payload to group by");
+        if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, who + ": no build of this layout");
+        if (c->used != HJ_STRATEGY_GLOBAL && !c->dual)
+            HJ_FAIL(HJ_ERR_STATE, who + ": a radix-only build has no global table (build it under HJ_STRATEGY_GLOBAL)");
+    }
+    if (!s->groups) HJ_FAIL(HJ_ERR_STATE, "star aggregate: no group table (call hj_star_reserve_groups first)");
+    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
+    if (n < 0) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: a negative row count");
+    for (int d = 0; d < ndims; ++d)
+        if (n > 0 && !skeys[d]) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: dimension " + std::to_string(d) + " has null keys");
+    const bool vals = out_sum || out_min || out_max;
+    if (vals && !sval && n > 0) HJ_FAIL(HJ_ERR_ARG, "star aggregate: sum, min or max without a value column");
+    const bool any = out_key || out_cnt || vals;
+    if (cap < 0) HJ_FAIL(HJ_ERR_ARG, "negative output capacity");
+    if (cap > 0 && !any) HJ_FAIL(HJ_ERR_ARG, "out_cap > 0 with every output null (the count form is out_cap == 0)");
+    if (cap == 0 && any) HJ_FAIL(HJ_ERR_ARG, "out_cap == 0 with an output (the count form takes none)");
+    HJ_HIP(hipSetDevice(s->device));
+    const StarGroups g = star_groups(s);
+    hj::StarAggArgs a{};
+    for (int d = 0; d < ndims; ++d) {
+        a.d[d].t = table_dev(dims[d]);
+        a.d[d].key = skeys[d];
+        a.d[d].out = nullptr;
+        a.d[d].null_pay = null_pay[d];
+        a.d[d].kind = kinds[d];
+        a.d[d].lds_off = -1;
+        a.gshift[d] = gshift[d];
+        a.gbase[d] = gbase ? gbase[d] : 0;
+    }
+    for (int d = ndims; d < HJ_STAR_MAX_DIMS; ++d) a.gshift[d] = -1;
+    a.sval = vals ? sval : nullptr;
+    a.n = n;
+    a.gt = g.t;
+    a.acc = hj::GroupAcc{g.acc.cnt, out_sum ? g.acc.sum : nullptr, out_min ? g.acc.mn : nullptr,
+                         out_max ? g.acc.mx : nullptr};
+    const hj::GroupOut out{out_key, out_cnt, out_sum, out_min, out_max, cap, (unsigned long long *)d_count, 0ull, 0};
+    HJ_HIP(hj::launch_star_aggregate(layout, ndims, a, out, &s->plan, (hipStream_t)stream));
+    return HJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3135,7 +3222,57 @@ void hj_star_destroy(hj_star *s) {
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
     if (s->work) (void)hipFree(s->work);
+    if (s->groups) (void)hipFree(s->groups);
     delete s;
+}
+
+int hj_star_reserve_groups(hj_star *s, int64_t max_groups) {
+    if (!s) HJ_FAIL(HJ_ERR_ARG, "null star");
+    if (max_groups < 0 || max_groups > (int64_t(1) << 40)) HJ_FAIL(HJ_ERR_ARG, "bad group count");
+    int bits = ceil_log2(2ull * (unsigned long long)max_groups);
+    if (bits < 11) bits = 11;   // at least one emit tile of slots
+    if (bits <= s->group_bits) return HJ_OK;
+    HJ_HIP(hipSetDevice(s->device));
+    if (s->groups) HJ_HIP(hipFree(s->groups));   // (waits for the device: nothing in flight reads the old one)
+    s->groups = nullptr;
+    s->group_bits = 0;
+    if (hipMalloc(&s->groups, star_groups_bytes(bits)) != hipSuccess) {
+        (void)hipGetLastError();
+        HJ_FAIL(HJ_ERR_NOMEM, "star aggregate: hipMalloc of the group table for " + std::to_string(max_groups) + " groups");
+    }
+    s->group_bits = bits;
+    return HJ_OK;
+}
+
+int64_t hj_star_group_capacity(const hj_star *s) {
+    if (!s) {
+        fail(HJ_ERR_ARG, __FILE__, __LINE__, "null star");
+        return HJ_ERR_ARG;
+    }
+    return s->groups ? int64_t(1) << s->group_bits : 0;
+}
+
+int hj_dev_star_aggregate_i64(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
+                              const int64_t *const skeys[], const int64_t null_pay[], const int gshift[],
+                              const int64_t gbase[], const int64_t *sval, int64_t n, int64_t *out_key, int64_t *out_cnt,
+                              int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap, uint64_t *d_count,
+                              void *stream) {
+    return do_star_aggregate(s, kWide, ndims, dims, kinds, (const void *const *)skeys,
+                             (const unsigned long long *)null_pay, gshift, gbase, sval, n, out_key, out_cnt, out_sum,
+                             out_min, out_max, out_cap, d_count, stream);
+}
+
+int hj_dev_star_aggregate_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
+                              const int32_t *const skeys[], const int32_t null_row[], const int gshift[],
+                              const int64_t gbase[], const int32_t *sval, int64_t n, int64_t *out_key, int64_t *out_cnt,
+                              int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap, uint64_t *d_count,
+                              void *stream) {
+    unsigned long long nulls[HJ_STAR_MAX_DIMS] = {};
+    if (null_row && ndims >= 1 && ndims <= HJ_STAR_MAX_DIMS)
+        for (int d = 0; d < ndims; ++d) nulls[d] = (unsigned long long)(long long)null_row[d];
+    return do_star_aggregate(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys, null_row ? nulls : nullptr,
+                             gshift, gbase, sval, n, out_key, out_cnt, out_sum, out_min, out_max, out_cap, d_count,
+                             stream);
 }
 
 int hj_star_reserve(hj_star *s, int64_t max_rows) {

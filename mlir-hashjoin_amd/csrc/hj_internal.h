@@ -591,6 +591,27 @@ hipError_t star_prepare();
 // that LDS lets a CU hold, else one workgroup per tile.  The write launch walks
 // the survivors alone: global tables, one workgroup per tile.
 hipError_t launch_star(int layout, int ndims, StarArgs a, const FilterWork &ws, StarPlan *plan, hipStream_t st);
+// Star aggregate (hj_kernels.hip, k_star_agg; hj.h "Star aggregate"): GROUP BY
+// over the star probe's qualifying rows in one pass.  d[].out is not read.
+struct StarAggArgs {                 // by value in the kernel arguments
+    StarDim d[kStarMaxDims];
+    long long gbase[kStarMaxDims];   // the group key's field of dimension d: (payload - gbase) << gshift
+    int gshift[kStarMaxDims];        // < 0: the dimension is not part of the key
+    int order[kStarMaxDims];         // set by launch_star_aggregate: the walk order, nwalk entries
+    int nwalk;
+    const void *sval;                // the value column (int64 / int32 by layout); null: none of sum / min / max
+    long long n;
+    TableDev gt;                     // the group table: wide, 2^k slots; side is not read
+    GroupAcc acc;                    // its accumulators (wide), slots + 1 entries
+    unsigned long long *counter;     // set by launch_star_aggregate: out.counter, whose bit 63 is the overflow flag
+};
+// Kernels only: the group table's fill, k_aggregate_init (it zeroes
+// out.counter), k_star_agg (n > 0) and k_emit_aggregate<kWide>.  Placement as
+// launch_star's over the tables the pass walks (INNER, ANTI, grouped LEFT), the
+// budget being min(kLdsPerCu, 160 KiB - the kernel's static LDS).  out.r is
+// the group key column; every out column is int64.  star_prepare covers it.
+hipError_t launch_star_aggregate(int layout, int ndims, StarAggArgs a, const GroupOut &out, StarPlan *plan,
+                                 hipStream_t st);
 // launches of exclusive_scan_u64 over len words (hj_radix.hip)
 int exclusive_scan_launches(unsigned long long len);
 

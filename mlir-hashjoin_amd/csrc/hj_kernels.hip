@@ -15,7 +15,8 @@
 // the outer probe (k_probe_outer),
 // the build-side outer stages (k_probe_mark, k_emit_unmatched),
 // the group probe (k_group_init, k_probe_group, k_emit_groups),
-// the hash aggregate (k_aggregate, k_emit_aggregate),
+// the hash aggregate (k_aggregate, k_emit_aggregate), the star aggregate
+// (k_star_agg: the star probe's walks in front of the aggregate's collapse),
 // the radix partition used by the
 // multi-GPU exchange, the selection, the counter-based generators of the
 // benchmark inputs and the copy floors.
@@ -218,6 +219,11 @@ constexpr int kProbeTile = kBlock * kProbeItems;
 // kLdsPerCu: the LDS the copies of one CU's workgroups may take together
 constexpr int kLdsTableBytes = HJ_LDS_TABLE_BYTES;
 constexpr int kLdsPerCu = 128 * 1024;
+// the LDS a CU has, and a bound on k_star_agg's static LDS (its collapse table
+// and a few words): its table copies are planned into what is left of the CU
+// beside that, and into no more than kLdsPerCu
+constexpr int kLdsCu = 160 * 1024;
+constexpr int kStarAggStaticLds = 19 * 1024;
 
 template <int L, int FORM>
 __device__ __forceinline__ bool probe_row(const SrcDev &src, unsigned long long q, int i, Tuple &tp) {
@@ -2047,6 +2053,93 @@ __device__ __forceinline__ void acc_add(const GroupAcc &acc, unsigned long long 
     if (acc.mx) atomicMax((typename GT::ext_t *)acc.mx + h, hi);
 }
 
+// One tile's collapse table in LDS, shared by k_aggregate and k_star_agg: keys,
+// counts and the partials asked for (AggWant), and the wide INT64_MIN key's
+// words of their own (n_*).  agg_tile_clear, a barrier, agg_tile_add per row, a
+// barrier, agg_tile_flush, a barrier.
+template <int L>
+struct AggTile {
+    using ext_t = typename GroupTypes<L>::ext_t;
+    static constexpr unsigned long long kE = L == kWide ? kEmptyKey64 : ~0ull;   // (a zero-extended i32 key is never all ones)
+    unsigned long long key[kAggSlots];
+    unsigned long long sum[kAggSlots];
+    ext_t mn[kAggSlots], mx[kAggSlots];
+    unsigned cnt[kAggSlots];
+    unsigned long long n_sum;
+    ext_t n_min, n_max;
+    unsigned n_cnt;
+};
+struct AggWant {
+    bool sum, mn, mx;
+};
+
+template <int L>
+__device__ __forceinline__ void agg_tile_clear(AggTile<L> &lt, AggWant w, int tid, int nthreads) {
+    using GT = GroupTypes<L>;
+    for (int j = tid; j < kAggSlots; j += nthreads) {
+        lt.key[j] = AggTile<L>::kE;
+        lt.cnt[j] = 0u;
+        if (w.sum) lt.sum[j] = 0ull;
+        if (w.mn) lt.mn[j] = GT::kMax;
+        if (w.mx) lt.mx[j] = GT::kMin;
+    }
+    if (tid == 0) {
+        lt.n_cnt = 0u;
+        lt.n_sum = 0ull;
+        lt.n_min = GT::kMax;
+        lt.n_max = GT::kMin;
+    }
+}
+
+// one row (K, V) into the tile's table; false: the walk ended on neither EMPTY nor K, the row goes to the global table itself
+template <int L>
+__device__ __forceinline__ bool agg_tile_add(AggTile<L> &lt, AggWant w, unsigned long long K, unsigned long long V) {
+    using ext_t = typename GroupTypes<L>::ext_t;
+    constexpr unsigned long long kE = AggTile<L>::kE;
+    if (Lay<L>::null_key(K)) {
+        atomicAdd(&lt.n_cnt, 1u);
+        if (w.sum) atomicAdd(&lt.n_sum, V);
+        if (w.mn) atomicMin(&lt.n_min, (ext_t)V);
+        if (w.mx) atomicMax(&lt.n_max, (ext_t)V);
+        return true;
+    }
+    unsigned h = (unsigned)slot_of(K, 64 - kAggSlotsLog);
+    bool in = false;
+    for (int step = 0; step < kAggWalk; ++step) {
+        unsigned long long e = __hip_atomic_load(&lt.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (e == kE) e = atomicCAS(&lt.key[h], kE, K);
+        if (e == kE || e == K) {
+            in = true;
+            break;
+        }
+        h = (h + 1u) & (unsigned)(kAggSlots - 1);
+    }
+    if (!in) return false;
+    atomicAdd(&lt.cnt[h], 1u);
+    if (w.sum) atomicAdd(&lt.sum[h], V);
+    if (w.mn) atomicMin(&lt.mn[h], (ext_t)V);
+    if (w.mx) atomicMax(&lt.mx[h], (ext_t)V);
+    return true;
+}
+
+// every occupied slot once into the global accumulators at slot(key) (~0: no slot, the partial is dropped -- the
+// bounded insert's overflow); the INT64_MIN words into entry null_entry
+template <int L, typename SLOT>
+__device__ __forceinline__ void agg_tile_flush(const AggTile<L> &lt, AggWant w, const GroupAcc &acc,
+                                               unsigned long long null_entry, int tid, int nthreads, SLOT slot) {
+    using GT = GroupTypes<L>;
+    using cnt_t = typename GT::cnt_t;
+    for (int j = tid; j < kAggSlots; j += nthreads) {
+        const unsigned long long k = lt.key[j];
+        if (k == AggTile<L>::kE) continue;
+        const unsigned long long h = slot(k);
+        if (h == ~0ull) continue;
+        acc_add<L>(acc, h, (cnt_t)lt.cnt[j], w.sum ? lt.sum[j] : 0ull, w.mn ? lt.mn[j] : GT::kMax,
+                   w.mx ? lt.mx[j] : GT::kMin);
+    }
+    if (L == kWide && tid == 0 && lt.n_cnt != 0u) acc_add<L>(acc, null_entry, (cnt_t)lt.n_cnt, lt.n_sum, lt.n_min, lt.n_max);
+}
+
 template <int L, int FORM>
 __global__ __launch_bounds__(kBlock) void k_aggregate(TableDev t, SrcDev src, GroupAcc acc) {
     using LY = Lay<L>;
@@ -2054,17 +2147,10 @@ __global__ __launch_bounds__(kBlock) void k_aggregate(TableDev t, SrcDev src, Gr
     using GT = GroupTypes<L>;
     using ext_t = typename GT::ext_t;
     using cnt_t = typename GT::cnt_t;
-    constexpr unsigned long long kE = L == kWide ? kEmptyKey64 : ~0ull;   // (a zero-extended i32 key is never all ones)
-    __shared__ unsigned long long lkey[kAggSlots];
-    __shared__ unsigned long long lsum[kAggSlots];
-    __shared__ ext_t lmin[kAggSlots], lmax[kAggSlots];
-    __shared__ unsigned lcnt[kAggSlots];
-    __shared__ unsigned long long n_sum;
-    __shared__ ext_t n_min, n_max;
-    __shared__ unsigned n_cnt;
+    __shared__ AggTile<L> lt;
     slot_t *sl = (slot_t *)t.slots;
-    const bool w_sum = acc.sum != nullptr, w_min = acc.mn != nullptr, w_max = acc.mx != nullptr;
-    const bool vals = w_sum || w_min || w_max;   // (uniform) else only the key is read
+    const AggWant w{acc.sum != nullptr, acc.mn != nullptr, acc.mx != nullptr};
+    const bool vals = w.sum || w.mn || w.mx;   // (uniform) else only the key is read
     const unsigned long long nt = (unsigned long long)((src.n + kProbeTile - 1) / kProbeTile);
     for (unsigned long long q = blockIdx.x; q < nt; q += gridDim.x) {
         unsigned long long K[kProbeItems], V[kProbeItems];
@@ -2084,51 +2170,14 @@ __global__ __launch_bounds__(kBlock) void k_aggregate(TableDev t, SrcDev src, Gr
                 ok |= 1u << i;
             }
         }
-        for (int j = threadIdx.x; j < kAggSlots; j += kBlock) {
-            lkey[j] = kE;
-            lcnt[j] = 0u;
-            if (w_sum) lsum[j] = 0ull;
-            if (w_min) lmin[j] = GT::kMax;
-            if (w_max) lmax[j] = GT::kMin;
-        }
-        if (threadIdx.x == 0) {
-            n_cnt = 0u;
-            n_sum = 0ull;
-            n_min = GT::kMax;
-            n_max = GT::kMin;
-        }
+        agg_tile_clear(lt, w, (int)threadIdx.x, kBlock);
         __syncthreads();
         // ---- the tile's rows into the LDS table
         unsigned direct = 0;
 #pragma unroll
         for (int i = 0; i < kProbeItems; ++i) {
             if (!((ok >> i) & 1u)) continue;
-            if (LY::null_key(K[i])) {
-                atomicAdd(&n_cnt, 1u);
-                if (w_sum) atomicAdd(&n_sum, V[i]);
-                if (w_min) atomicMin(&n_min, (ext_t)V[i]);
-                if (w_max) atomicMax(&n_max, (ext_t)V[i]);
-                continue;
-            }
-            unsigned h = (unsigned)slot_of(K[i], 64 - kAggSlotsLog);
-            bool in = false;
-            for (int step = 0; step < kAggWalk; ++step) {
-                unsigned long long e = __hip_atomic_load(&lkey[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (e == kE) e = atomicCAS(&lkey[h], kE, K[i]);
-                if (e == kE || e == K[i]) {
-                    in = true;
-                    break;
-                }
-                h = (h + 1u) & (unsigned)(kAggSlots - 1);
-            }
-            if (in) {
-                atomicAdd(&lcnt[h], 1u);
-                if (w_sum) atomicAdd(&lsum[h], V[i]);
-                if (w_min) atomicMin(&lmin[h], (ext_t)V[i]);
-                if (w_max) atomicMax(&lmax[h], (ext_t)V[i]);
-            } else {
-                direct |= 1u << i;
-            }
+            if (!agg_tile_add(lt, w, K[i], V[i])) direct |= 1u << i;
         }
         // ---- the rows the LDS table did not admit: the global table, one by one
 #pragma unroll
@@ -2138,14 +2187,8 @@ __global__ __launch_bounds__(kBlock) void k_aggregate(TableDev t, SrcDev src, Gr
         }
         __syncthreads();
         // ---- one flush per occupied LDS slot
-        for (int j = threadIdx.x; j < kAggSlots; j += kBlock) {
-            const unsigned long long k = lkey[j];
-            if (k == kE) continue;
-            acc_add<L>(acc, agg_slot<L>(sl, t, k), (cnt_t)lcnt[j], w_sum ? lsum[j] : 0ull, w_min ? lmin[j] : GT::kMax,
-                       w_max ? lmax[j] : GT::kMin);
-        }
-        if (L == kWide && threadIdx.x == 0 && n_cnt != 0u)
-            acc_add<L>(acc, t.mask + 1ull, (cnt_t)n_cnt, n_sum, n_min, n_max);
+        agg_tile_flush(lt, w, acc, t.mask + 1ull, (int)threadIdx.x, kBlock,
+                       [&](unsigned long long k) { return agg_slot<L>(sl, t, k); });
         __syncthreads();   // the LDS table is cleared for the next tile
     }
 }
@@ -2228,6 +2271,189 @@ __global__ __launch_bounds__(kBlock) void k_emit_aggregate(TableDev t, GroupAcc 
             if (omin) omin[gi] = (out_t)mn[cap];
             if (omax) omax[gi] = (out_t)mx[cap];
         }
+    }
+}
+
+// ------------------------------------------------------------------ star aggregate
+// GROUP BY over a star probe's survivors in one pass (hj.h "Star aggregate"):
+// k_star's tiles, teams, table copies and key prefetch in front of
+// k_aggregate's collapse.  Nothing per row reaches memory: no result byte, no
+// tile count, no scan and no write launch.  Per tile
+//   1. a.order[0 .. a.nwalk) is walked with one loop body (the index is
+//      wave-uniform, so the dimension's fields are scalar loads of the kernel
+//      arguments and one set of eight keys is live): first the dimensions that
+//      can drop a row (INNER, ANTI) in the caller's order, a row that failed
+//      one loading no further key, then the grouped LEFT ones, for the
+//      survivors alone.  A LEFT dimension outside the key is never read.  A
+//      grouped dimension's walk takes the smallest payload (to the first equal
+//      key when the table's meta[1] is clear, else on to EMPTY; the side list's
+//      minimum for a wide INT64_MIN key); an ungrouped one ends at the first
+//      equal key.  Each grouped payload is folded into the row's group key
+//      g += (P - gbase) << gshift as it arrives.
+//   2. sval is loaded for the survivors, and only when sum / min / max is asked
+//      for.
+//   3. the survivors are collapsed in the LDS table (AggTile<kWide>: the group
+//      table is wide in both forms) and flushed with the bounded insert below.
+// The teams of a workgroup share ONE collapse table: beside per-team tables
+// (36 KiB) two 64-KiB table copies would no longer fit a CU's 160 KiB, and the
+// teams already meet at a barrier every step.  All of a workgroup's threads
+// clear and flush it.
+// Overflow: bit 63 of *a.counter (zeroed by k_aggregate_init in front) is the
+// flag.  agg_slot_bounded sets it when a counted walk of the whole table found
+// neither the key nor EMPTY; thread 0 reads it at the start of every tile and
+// the workgroup leaves the loop behind the tile's first barrier.  The emit adds
+// its counts below the bit and stores nothing, its positions being >= 2^63.
+
+// agg_slot as a COUNTED loop: at most capacity steps, then the flag and ~0.
+// Every 256 steps it looks at the flag, so a full table costs one long walk,
+// not one per row.
+__device__ __forceinline__ unsigned long long agg_slot_bounded(Slot64 *sl, const TableDev &t, unsigned long long K,
+                                                               unsigned long long *flag) {
+    unsigned long long h = slot_of(K, t.shift);
+    for (unsigned long long step = 0; step <= t.mask; ++step) {
+        unsigned long long old = __hip_atomic_load(&sl[h].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == kEmptyKey64) old = atomicCAS(&sl[h].key, kEmptyKey64, K);
+        if (old == kEmptyKey64 || old == K) return h;
+        if ((step & 255ull) == 255ull &&
+            (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 63) != 0ull)
+            return ~0ull;
+        h = (h + 1) & t.mask;
+    }
+    atomicOr(flag, 1ull << 63);
+    return ~0ull;
+}
+
+template <int L, int ND>
+__global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(StarAggArgs a) {
+    using slot_t = typename Lay<L>::slot_t;
+    constexpr long long kMaxPay = 0x7fffffffffffffffll;
+    __shared__ AggTile<kWide> lt;
+    __shared__ long long s_side_min[kStarMaxDims];
+    __shared__ unsigned long long s_side_n[kStarMaxDims];
+    __shared__ unsigned s_unique[kStarMaxDims];
+    __shared__ unsigned s_stop;
+    extern __shared__ ulonglong2 s_tab[];
+    static_assert(sizeof(AggTile<kWide>) + 128 <= kStarAggStaticLds, "the placement plan's bound on the static LDS");
+
+    const int tid = threadIdx.x & (kBlock - 1), team = threadIdx.x / kBlock, teams = blockDim.x / kBlock;
+    const AggWant w{a.acc.sum != nullptr, a.acc.mn != nullptr, a.acc.mx != nullptr};
+    const bool vals = w.sum || w.mn || w.mx;   // (uniform) else sval is not read
+    Slot64 *gsl = (Slot64 *)a.gt.slots;
+    if (threadIdx.x < kStarMaxDims) {
+        s_side_min[threadIdx.x] = kMaxPay;
+        s_side_n[threadIdx.x] = 0ull;
+        s_unique[threadIdx.x] = 1u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const StarDim &dm = a.d[d];
+        const bool grouped = a.gshift[d] >= 0;
+        if (dm.kind == kStarLeft && !grouped) continue;   // (uniform) never walked
+        if (dm.lds_off >= 0) {
+            ulonglong2 *dst = s_tab + (dm.lds_off >> 4);
+            const unsigned long long n16 = (dm.t.mask + 1) * sizeof(slot_t) / 16;
+            const ulonglong2 *g16 = (const ulonglong2 *)dm.t.slots;
+            for (unsigned long long j = threadIdx.x; j < n16; j += blockDim.x) dst[j] = g16[j];
+        }
+        const unsigned long long side_n = L == kWide ? dm.t.meta[0] : 0ull;
+        if (threadIdx.x == 0) {
+            s_side_n[d] = side_n;
+            if (grouped)
+                s_unique[d] = __hip_atomic_load(&dm.t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull ? 1u : 0u;
+        }
+        if (!grouped || side_n == 0ull) continue;   // (uniform)
+        long long m = kMaxPay;
+        for (unsigned long long j = threadIdx.x; j < side_n; j += blockDim.x) {
+            const long long p = (long long)dm.t.side[j];
+            m = p < m ? p : m;
+        }
+        atomicMin(&s_side_min[d], m);
+    }
+    __syncthreads();
+
+    const unsigned long long nt = (unsigned long long)((a.n + kProbeTile - 1) / kProbeTile);
+    auto row_of = [&](unsigned long long q, int i) { return (long long)q * kProbeTile + (long long)i * kBlock + tid; };
+    auto valid_of = [&](unsigned long long q) {
+        unsigned v = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) v |= row_of(q, i) < a.n ? 1u << i : 0u;
+        return v;
+    };
+    auto load_keys = [&](const void *col, unsigned long long q, unsigned rows, star_key_t<L> (&K)[kProbeItems]) {
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) K[i] = (rows >> i) & 1u ? star_key<L>(col, row_of(q, i)) : star_key_t<L>(0);
+    };
+    // loaded ahead: the first walked dimension's keys of the next tile
+    const void *first_col = a.nwalk > 0 ? a.d[a.order[0]].key : nullptr;
+    star_key_t<L> KN[kProbeItems] = {};
+    const unsigned long long step = (unsigned long long)gridDim.x * teams, q0 = (unsigned long long)blockIdx.x * teams + team;
+    if (q0 < nt && first_col) load_keys(first_col, q0, valid_of(q0), KN);
+    for (unsigned long long qb = (unsigned long long)blockIdx.x * teams; qb < nt; qb += step) {
+        const unsigned long long q = qb + team, qn = q + step;
+        if (threadIdx.x == 0)
+            s_stop = (unsigned)(__hip_atomic_load(a.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 63);
+        agg_tile_clear(lt, w, (int)threadIdx.x, (int)blockDim.x);
+        unsigned alive = q < nt ? valid_of(q) : 0u;
+        star_key_t<L> KF[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) KF[i] = KN[i];
+        if (qn < nt && first_col) load_keys(first_col, qn, valid_of(qn), KN);
+        unsigned long long G[kProbeItems] = {};
+#pragma unroll 1
+        for (int j = 0; j < a.nwalk; ++j) {
+            const int d = a.order[j];   // (uniform)
+            const StarDim &dm = a.d[d];
+            const int gs = a.gshift[d];
+            star_key_t<L> K[kProbeItems];
+            long long RP[kProbeItems];
+            if (j == 0) {
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i) K[i] = KF[i];
+            } else {
+                load_keys(dm.key, q, alive, K);
+            }
+            const unsigned found = star_walk<L, true>(dm, alive, K, s_side_n[d], s_side_min[d], gs < 0 || s_unique[d] != 0u, RP);
+            if (dm.kind == kStarInner) alive &= found;
+            else if (dm.kind == kStarAnti) alive &= ~found;
+            if (gs >= 0) {
+                const long long base = a.gbase[d];
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i) {
+                    if (!((alive >> i) & 1u)) continue;
+                    long long p = (long long)dm.null_pay;
+                    if ((found >> i) & 1u) p = L == kWide ? RP[i] : (long long)(int)RP[i];
+                    G[i] += ((unsigned long long)p - (unsigned long long)base) << gs;
+                }
+            }
+        }
+        unsigned long long V[kProbeItems];
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            V[i] = 0ull;
+            if (vals && ((alive >> i) & 1u)) {
+                if constexpr (L == kWide) V[i] = ((const unsigned long long *)a.sval)[row_of(q, i)];
+                else V[i] = (unsigned long long)(long long)((const int *)a.sval)[row_of(q, i)];
+            }
+        }
+        __syncthreads();   // the table is clear, s_stop is everybody's
+        if (s_stop != 0u) break;   // (uniform)
+        unsigned direct = 0;
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((alive >> i) & 1u)) continue;
+            if (!agg_tile_add(lt, w, G[i], V[i])) direct |= 1u << i;
+        }
+#pragma unroll
+        for (int i = 0; i < kProbeItems; ++i) {
+            if (!((direct >> i) & 1u)) continue;
+            const unsigned long long h = agg_slot_bounded(gsl, a.gt, G[i], a.counter);
+            if (h != ~0ull) acc_add<kWide>(a.acc, h, 1ull, V[i], (long long)V[i], (long long)V[i]);
+        }
+        __syncthreads();
+        agg_tile_flush(lt, w, a.acc, a.gt.mask + 1ull, (int)threadIdx.x, (int)blockDim.x,
+                       [&](unsigned long long k) { return agg_slot_bounded(gsl, a.gt, k, a.counter); });
+        __syncthreads();   // the table is cleared, s_stop rewritten for the next tile
     }
 }
 
@@ -2807,6 +3033,18 @@ star_kernel_t star_kernel(int layout, int ndims, int mode) {
     default: return nullptr;
     }
 }
+typedef void (*star_agg_kernel_t)(StarAggArgs);
+star_agg_kernel_t star_agg_kernel(int layout, int ndims) {
+    if (layout != kWide && layout != kNarrow) return nullptr;
+    const bool w = layout == kWide;
+    switch (ndims) {
+    case 1: return w ? k_star_agg<kWide, 1> : k_star_agg<kNarrow, 1>;
+    case 2: return w ? k_star_agg<kWide, 2> : k_star_agg<kNarrow, 2>;
+    case 3: return w ? k_star_agg<kWide, 3> : k_star_agg<kNarrow, 3>;
+    case 4: return w ? k_star_agg<kWide, 4> : k_star_agg<kNarrow, 4>;
+    default: return nullptr;
+    }
+}
 }  // namespace
 
 hipError_t star_prepare() {
@@ -2817,7 +3055,79 @@ hipError_t star_prepare() {
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
                 if (e != hipSuccess) return e;
             }
+    for (int layout : {(int)kWide, (int)kNarrow})
+        for (int nd = 1; nd <= kStarMaxDims; ++nd) {
+            const hipError_t e = hipFuncSetAttribute((const void *)star_agg_kernel(layout, nd),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
+            if (e != hipSuccess) return e;
+        }
     return hipSuccess;
+}
+
+hipError_t launch_star_aggregate(int layout, int ndims, StarAggArgs a, const GroupOut &out, StarPlan *plan,
+                                 hipStream_t st) {
+    if (ndims < 1 || ndims > kStarMaxDims || (layout != kWide && layout != kNarrow)) return hipErrorInvalidValue;
+    const unsigned long long cap = a.gt.mask + 1ull, entries = cap + 1ull;
+    a.counter = out.counter;
+    hipError_t e = launch_init(a.gt, kWide, cap, st);
+    if (e != hipSuccess) return e;
+    const unsigned most = (unsigned)(cu_count() * 8);
+    const unsigned fl = grid_for((long long)entries, kBlock), gi = fl < most ? fl : most;
+    hipLaunchKernelGGL(k_aggregate_init<kWide>, dim3(gi), dim3(kBlock), 0, st, a.acc, entries, out.counter);
+    *plan = StarPlan{3, 0u, 0, 0, 0};
+    if (a.n > 0) {
+        // the walk order: the dimensions that can drop a row in the caller's order, then the grouped LEFT ones
+        a.nwalk = 0;
+        for (int d = 0; d < ndims; ++d)
+            if (a.d[d].kind != kStarLeft) a.order[a.nwalk++] = d;
+        for (int d = 0; d < ndims; ++d)
+            if (a.d[d].kind == kStarLeft && a.gshift[d] >= 0) a.order[a.nwalk++] = d;
+        // placement: launch_star's rule over the walked tables, the budget being what the CU has left beside the
+        // kernel's static LDS and no more than kLdsPerCu
+        const size_t sb = layout == kWide ? 16 : 8;
+        const size_t budget = (size_t)(kLdsCu - kStarAggStaticLds < kLdsPerCu ? kLdsCu - kStarAggStaticLds : kLdsPerCu);
+        size_t bytes[kStarMaxDims];
+        int order[kStarMaxDims];
+        for (int j = 0; j < a.nwalk; ++j) {
+            const int d = a.order[j];
+            bytes[d] = (size_t)(a.d[d].t.mask + 1) * sb;
+            int k = j;
+            for (; k > 0 && bytes[order[k - 1]] > bytes[d]; --k) order[k] = order[k - 1];
+            order[k] = d;
+        }
+        int lds_dims = 0;
+        size_t lds_bytes = 0;
+        for (int d = 0; d < kStarMaxDims; ++d) a.d[d].lds_off = -1;
+        for (int j = 0; j < a.nwalk; ++j) {
+            const size_t b = bytes[order[j]];
+            if (b > (size_t)kLdsTableBytes || lds_bytes + b > budget) break;
+            lds_dims |= 1 << order[j];
+            lds_bytes += b;
+        }
+        size_t off = 0;
+        for (int d = 0; d < ndims; ++d)
+            if ((lds_dims >> d) & 1) {
+                a.d[d].lds_off = (int)off;
+                off += bytes[d];
+            }
+        // persistent workgroups: with table copies kStarTeams teams each, as many as the LDS lets a CU hold;
+        // without, one team each and eight per CU (the collapse table alone, as k_aggregate's)
+        const unsigned tiles = grid_for(a.n, kProbeTile);
+        unsigned teams = 1, per_cu = 8;
+        if (lds_bytes) {
+            teams = kStarTeams;
+            per_cu = (unsigned)((size_t)kLdsCu / (lds_bytes + (size_t)kStarAggStaticLds));
+            if (per_cu * teams > 8) per_cu = 8 / teams;
+            if (per_cu < 1) per_cu = 1;
+        }
+        const unsigned mostw = (unsigned)cu_count() * per_cu, want = (tiles + teams - 1) / teams;
+        const unsigned grid = mostw < want ? mostw : want;
+        hipLaunchKernelGGL(star_agg_kernel(layout, ndims), dim3(grid), dim3(kBlock * teams), lds_bytes, st, a);
+        *plan = StarPlan{4, grid, (long long)tiles, lds_dims, (long long)lds_bytes};
+    }
+    const unsigned tl = grid_for((long long)cap, kProbeTile), g = tl < most ? tl : most;
+    hipLaunchKernelGGL(k_emit_aggregate<kWide>, dim3(g), dim3(kBlock), 0, st, a.gt, a.acc, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_star(int layout, int ndims, StarArgs a, const FilterWork &ws, StarPlan *plan, hipStream_t st) {

@@ -64,6 +64,8 @@ HJ_STAR_ANTI = 2
 STAR_TILE = 2048
 STAR_LDS_TABLE_BYTES = 64 * 1024
 STAR_LDS_BUDGET_BYTES = 128 * 1024
+# the star aggregate (k_star_agg): the group table's smallest capacity (hj_star_reserve_groups)
+STAR_GROUP_MIN_CAPACITY = 2048
 HJ_GROUP_MATCHED = 0
 HJ_GROUP_ALL = 1
 HJ_OUTER_BUILD = 1
@@ -179,6 +181,14 @@ def _load():
                                    C.POINTER(_vp), _vp, _i64, _vp, _vp]),
         "hj_dev_star_i32": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(_vp), C.POINTER(C.c_int32),
                                    _i64, _i64, C.POINTER(_vp), _vp, _i64, _vp, _vp]),
+        "hj_star_reserve_groups": (_int, [_vp, _i64]),
+        "hj_star_group_capacity": (_i64, [_vp]),
+        "hj_dev_star_aggregate_i64": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(_vp),
+                                             C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(_i64), _vp, _i64, _vp, _vp,
+                                             _vp, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_star_aggregate_i32": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(_vp),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(_i64), _vp, _i64, _vp,
+                                             _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_partition_i64": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_dev_partition_tuples_i64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_partition_of": (_int, [_i64, _int]),

@@ -472,6 +472,90 @@ class StarProbe:
         cnt = self.probe_into(dims, stream=stream)
         return int(cnt.item()) if sync else cnt
 
+    # ---- star aggregate (hj.h "Star aggregate"): GROUP BY over the qualifying rows, one fused pass
+    def reserve_groups(self, max_groups):
+        """Size the group table for `max_groups` distinct groups (grow-only);
+        after it aggregate_into launches kernels only and can be captured."""
+        check(lib.hj_star_reserve_groups(self._s, int(max_groups)), "hj_star_reserve_groups")
+
+    @property
+    def group_capacity(self):
+        """Slots of the group table (0 before the first reserve_groups)."""
+        return int(lib.hj_star_group_capacity(self._s))
+
+    def aggregate_into(self, dims, val=None, out_key=None, out_cnt=None, out_sum=None, out_min=None, out_max=None,
+                       count=None, group=None, base=None, stream=None):
+        """The raw call: one row (key, count, sum, min, max of val) per
+        distinct group key over the rows every dimension admits, aligned at the
+        same index of each int64 column passed (any may be None: not computed;
+        all None counts the groups).  group: per dimension the bit position of
+        its payload's field in the key, or -1 / None to leave it out (default:
+        none -- one group); base: per dimension the value subtracted first
+        (default 0).  val: a column of the key columns' dtype, needed for sum,
+        min and max.  Needs reserve_groups.  `count` (int64 device tensor)
+        receives G; negative: the group table overflowed (bit 63).  Returns count."""
+        hjs, keys, kinds, nulls = self._dims(dims)
+        nd, dt, n = len(dims), keys[0].dtype, keys[0].numel()
+        group = [-1] * nd if group is None else [-1 if g is None else int(g) for g in group]
+        base = [0] * nd if base is None else [int(b) for b in base]
+        if len(group) != nd or len(base) != nd:
+            raise ValueError("group and base need one entry per dimension")
+        outs = [o for o in (out_key, out_cnt, out_sum, out_min, out_max) if o is not None]
+        _need_cuda(val, *outs)
+        if any(o.dtype != torch.int64 or o.dim() != 1 for o in outs):
+            raise ValueError("the star aggregate's output columns are int64")
+        cap = outs[0].shape[0] if outs else 0
+        if any(o.shape[0] != cap for o in outs):
+            raise ValueError("output columns differ in length")
+        if val is not None and (val.dtype != dt or val.dim() != 1 or val.numel() != n):
+            raise ValueError("the value column takes the key columns' dtype and length")
+        count = self._count if count is None else count
+        a_ctx = (C.c_void_p * nd)(*[h._ctx for h in hjs])
+        a_kind = (C.c_int * nd)(*kinds)
+        a_key = (C.c_void_p * nd)(*[k.data_ptr() for k in keys])
+        a_shift = (C.c_int * nd)(*group)
+        a_base = (C.c_int64 * nd)(*base)
+        wide = dt == torch.int64
+        a_null = ((C.c_int64 if wide else C.c_int32) * nd)(*nulls)
+        f = lib.hj_dev_star_aggregate_i64 if wide else lib.hj_dev_star_aggregate_i32
+        check(f(self._s, nd, a_ctx, a_kind, a_key, a_null, a_shift, a_base, _ptr(val), n, _ptr(out_key), _ptr(out_cnt),
+                _ptr(out_sum), _ptr(out_min), _ptr(out_max), cap, _ptr(count), _stream(self.device, stream)),
+              "hj_dev_star_aggregate_i64" if wide else "hj_dev_star_aggregate_i32")
+        return count
+
+    def aggregate(self, dims, val=None, aggs=("count", "sum"), group=None, base=None, max_groups=None, capacity=None,
+                  stream=None):
+        """{"key": tensor, agg: tensor, ...} trimmed to G, for aggs among
+        "count", "sum", "min", "max" (all int64).  max_groups: reserve_groups
+        first (None: the table as it stands).  capacity=None counts the groups
+        first and allocates exactly; a capacity below G is grown to G and the
+        call repeated.  Raises HJError when the group table overflowed.
+        Synchronises to read G."""
+        if any(a not in GROUP_AGGS for a in aggs):
+            raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
+        if max_groups is not None:
+            self.reserve_groups(max_groups)
+
+        def groups(cnt):
+            g = int(cnt.item())
+            if g < 0:   # bit 63 (hj.h)
+                raise HJError(f"star aggregate: more groups than the group table of {self.group_capacity} slots "
+                              "admits (reserve_groups)")
+            return g
+
+        cap = groups(self.aggregate_into(dims, group=group, base=base, stream=stream)) if capacity is None \
+            else int(capacity)
+        for _ in range(2):
+            cap = max(1, cap)
+            out_key = torch.empty(cap, dtype=torch.int64, device=self.device)
+            cols = {a: torch.empty(cap, dtype=torch.int64, device=self.device) for a in aggs}
+            g = groups(self.aggregate_into(dims, val, out_key, cols.get("count"), cols.get("sum"), cols.get("min"),
+                                           cols.get("max"), group=group, base=base, stream=stream))
+            if g <= cap:
+                return {"key": out_key[:g], **{a: c[:g] for a, c in cols.items()}}
+            cap = g
+        raise RuntimeError("star aggregate output did not fit after resizing")
+
 
 class HashJoin:
     """One device's hash-join context (table workspace + phase timing)."""
@@ -1599,6 +1683,90 @@ def star_join(dims, device=None, stream=None):
         return star.probe(probe_dims, stream=stream)
     finally:
         star.close()   # (waits for the device before the contexts go)
+        for hj in hjs:
+            hj.close()
+
+
+def star_aggregate(dims, val=None, group_by=None, aggs=("count", "sum"), max_groups=None, device=None, stream=None):
+    """A star query in one call: dims = [(rkey, rpay, skey, how[, null]), ...]
+    as star_join's, val the fact column to aggregate (the key columns' dtype;
+    None with aggs of "count" alone), group_by one boolean per dimension: the
+    qualifying fact rows are grouped by the payloads of the dimensions marked
+    (a "left" dimension's null is a group value; an "anti" dimension has no
+    payload and cannot be marked).  Builds the dimensions under the global
+    strategy, packs the grouped payload columns' ranges with a KeyCodec, runs
+    StarProbe.aggregate and returns {"keys": [per dimension its payload column
+    of the groups, None where not grouped], agg: int64 tensor, ...}, one row
+    per group in no particular order.  max_groups defaults to the product over
+    the grouped dimensions of their build rows (+ 1 for "left"), at most the
+    fact rows.  Raises HJError when the grouped ranges do not fit 64 bits
+    together (HJ_ERR_RANGE).  Synchronises."""
+    if not dims:
+        raise ValueError("star_aggregate needs at least one dimension")
+    group_by = [False] * len(dims) if group_by is None else [bool(g) for g in group_by]
+    if len(group_by) != len(dims):
+        raise ValueError("group_by needs one entry per dimension")
+    dev = dims[0][2].device.index if device is None else device
+    hjs, star, kc = [], StarProbe(dev), None
+    try:
+        probe_dims, cols, rows = [], [], []
+        for d, g in zip(dims, group_by):
+            if len(d) not in (4, 5):
+                raise ValueError("a dimension is (rkey, rpay, skey, how[, null])")
+            rkey, rpay, skey, how = d[:4]
+            null = d[4] if len(d) == 5 and d[4] is not None else -1
+            if g and how == "anti":
+                raise ValueError("an anti dimension has no payload to group by")
+            hj = HashJoin(dev)
+            hjs.append(hj)
+            hj.set_strategy("global")
+            hj.build_table(rkey, rpay, stream=stream)
+            probe_dims.append((hj, skey, how, null))
+            if g:   # the values its payload takes: the build's payloads (i32: the row ids) and a LEFT null
+                pay = rpay if rkey.dtype == torch.int64 else torch.arange(rkey.numel(), dtype=torch.int32, device=rkey.device)
+                if how == "left":
+                    pay = torch.cat([pay, torch.tensor([null], dtype=pay.dtype, device=pay.device)])
+                cols.append(pay.contiguous())
+                rows.append(rkey.numel() + (how == "left"))
+        n = probe_dims[0][1].numel()
+        grouped = [i for i, g in enumerate(group_by) if g]
+        group = base = None
+        if grouped:
+            kc = KeyCodec([c.dtype for c in cols], dev)
+            # one observe per column, the others held at a value of their own (an empty one at 0)
+            rep = [c[:1] if c.numel() else torch.zeros(1, dtype=c.dtype, device=c.device) for c in cols]
+            for i, c in enumerate(cols):
+                if c.numel():
+                    kc.observe([c if j == i else rep[j].expand(c.numel()).contiguous() for j in range(len(cols))],
+                               stream=stream)
+            kc.seal(stream=stream)
+            plan = kc.info()
+            if not plan["fits"]:
+                raise HJError(f"star_aggregate failed with {HJ_ERR_RANGE}: the grouped payload ranges need "
+                              f"{plan['total_bits']} bits together")
+            group, base = [-1] * len(dims), [0] * len(dims)
+            for c, i in enumerate(grouped):
+                if plan["bits"][c] > 0:
+                    group[i] = sum(plan["bits"][c + 1:])
+                    base[i] = plan["lo"][c]
+        if max_groups is None:
+            max_groups = 1
+            for r in rows:
+                max_groups *= r
+            max_groups = min(max_groups, n)
+        a = star.aggregate(probe_dims, val, aggs=aggs, group=group, base=base, max_groups=max_groups, stream=stream)
+        keys = [None] * len(dims)
+        if grouped:
+            for i, col in zip(grouped, kc.unpack(a["key"].contiguous(), stream=stream)):
+                keys[i] = col
+        out = {"keys": keys}
+        out.update({k: v for k, v in a.items() if k != "key"})
+        torch.cuda.synchronize(dev)
+        return out
+    finally:
+        star.close()   # (waits for the device before the contexts go)
+        if kc is not None:
+            kc.close()
         for hj in hjs:
             hj.close()
 
