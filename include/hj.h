@@ -1001,6 +1001,104 @@ int hj_dev_star_aggregate_i32(hj_star *s, int ndims, hj_ctx *const dims[], const
                               int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap, uint64_t *d_count,
                               void *stream);
 
+/* ---------------------------------------------------------------- Star query
+ * The star aggregate with the fact row's own part of a star-schema query in
+ * the same pass: predicates on fact columns, a value that is an expression of
+ * two fact columns, and group fields taken from fact columns.  Nothing is
+ * written per row and no column is read for a row that already failed.
+ *
+ * hj_star_fact is a HOST struct read at call time; its values travel in the
+ * kernel arguments as dims / kinds / gshift do.  Every fact column of a call
+ * (pcol, vb, fcol, as sval and skeys) has the call's layout: int64 for _i64,
+ * int32 for _i32.  Columns may alias each other, sval or a key column: all are
+ * only read.  The arguments are hj_dev_star_aggregate_*'s with `fact` after
+ * gbase.
+ *
+ * Which rows qualify.  Row j qualifies iff every predicate admits it AND every
+ * dimension admits it (the star aggregate's rule, unchanged).  Predicate p
+ * admits row j iff plo[p] <= pcol[p][j] <= phi[p] under HJ_PRED_IN, iff
+ * pcol[p][j] < plo[p] or pcol[p][j] > phi[p] under HJ_PRED_OUT.  The compares
+ * are SIGNED int64 compares; int32 column values are sign-extended first.  plo
+ * / phi are int64 in both forms: bounds outside int32 are legal and mean
+ * "always" or "never".  plo = INT64_MIN, phi = INT64_MAX admits every row
+ * under IN and none under OUT; plo > phi is an empty range: no row under IN,
+ * every row under OUT.  INT64_MIN and INT64_MAX are column values like any
+ * other.
+ *
+ * The value.  v(j) = sval[j] <vop> vb[j] in two's-complement int64: it wraps,
+ * MUL is the low 64 bits.  int32 columns are sign-extended first, so i32 MUL /
+ * ADD / SUB never wrap.  sum / min / max are over v.  vb is read only when vop
+ * != HJ_VALUE_A and one of sum / min / max is asked for, and only for
+ * qualifying rows.
+ *
+ * The group key.  The star aggregate's g(j) plus, for each f < nfact,
+ *     ((uint64)(fcol[f][j] - fbase[f]) << fshift[f])             (mod 2^64)
+ * fshift is 0..63; a fact group that takes no part is simply not listed.
+ * Keeping the fields apart is the caller's business, as for gshift.  fcol is
+ * read for qualifying rows only.
+ *
+ * The result is exactly what hj_dev_star_aggregate_i64 returns over the
+ * qualifying rows with that value and that key.  Carried over unchanged: the
+ * output rules and the count form, *d_count and its bit 63 on group-table
+ * overflow, hj_star_reserve_groups, the contexts being only read, bit-equality
+ * across runs and placements, and the launches being kernels only, a linear
+ * graph under capture (bounds, shifts and bases travel in the captured
+ * arguments).
+ *
+ * fact == NULL is no predicate, HJ_VALUE_A and no fact group: the call then
+ * equals hj_dev_star_aggregate_* bit for bit (it runs the same kernel).
+ *
+ * ndims == 0 is legal here (and only here: hj_dev_star_aggregate_* keeps its
+ * 1..4); dims, kinds, skeys, the null array and gshift may then be NULL.  This
+ * is a filtered GROUP BY over the fact columns alone.  With nothing grouped all
+ * qualifying rows form one group with key 0; with no qualifying row M = 0.  No
+ * table is read and the pass asks for no dynamic LDS.
+ *
+ * hj_star_last_plan reports the call as it reports a star aggregate: 4
+ * launches, or 3 when n == 0.
+ *
+ * Errors, in this order (extending the star aggregate's): a null star
+ * (HJ_ERR_ARG, "null star", before any device is touched); ndims outside
+ * 0..HJ_STAR_MAX_DIMS, or with ndims > 0 a null dims, kinds, skeys, null-value
+ * array or gshift; per dimension as the star aggregate; the fact descriptor,
+ * each HJ_ERR_ARG naming the field and index: npreds outside
+ * 0..HJ_STAR_MAX_PREDS, a pkind outside the two, vop outside 0..3, nfact
+ * outside 0..HJ_STAR_MAX_FACT_GROUPS, an fshift outside 0..63; no group
+ * reserve (HJ_ERR_STATE); a null count pointer; n < 0; with n > 0 a null key
+ * column, then a null pcol[p], then a null fcol[f]; the sval rule; vop !=
+ * HJ_VALUE_A with sum / min / max asked for and vb == NULL (n > 0); the output
+ * rules.  n == 0 takes null columns everywhere. */
+#define HJ_STAR_MAX_PREDS 4
+#define HJ_STAR_MAX_FACT_GROUPS 2
+#define HJ_PRED_IN  0   /* the row needs plo <= col[j] <= phi            */
+#define HJ_PRED_OUT 1   /* the row needs col[j] < plo or col[j] > phi    */
+#define HJ_VALUE_A   0  /* v(j) = sval[j]                                */
+#define HJ_VALUE_ADD 1  /* v(j) = sval[j] + vb[j]   (wrapping int64)     */
+#define HJ_VALUE_SUB 2  /* v(j) = sval[j] - vb[j]                        */
+#define HJ_VALUE_MUL 3  /* v(j) = sval[j] * vb[j]                        */
+typedef struct {
+    int npreds;
+    const void *pcol[HJ_STAR_MAX_PREDS];
+    int64_t plo[HJ_STAR_MAX_PREDS], phi[HJ_STAR_MAX_PREDS];
+    int pkind[HJ_STAR_MAX_PREDS];
+    int vop;
+    const void *vb;
+    int nfact;
+    const void *fcol[HJ_STAR_MAX_FACT_GROUPS];
+    int fshift[HJ_STAR_MAX_FACT_GROUPS];
+    int64_t fbase[HJ_STAR_MAX_FACT_GROUPS];
+} hj_star_fact;
+int hj_dev_star_query_i64(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
+                          const int64_t *const skeys[], const int64_t null_pay[], const int gshift[],
+                          const int64_t gbase[], const hj_star_fact *fact, const int64_t *sval, int64_t n,
+                          int64_t *out_key, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                          int64_t out_cap, uint64_t *d_count, void *stream);
+int hj_dev_star_query_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
+                          const int32_t *const skeys[], const int32_t null_row[], const int gshift[],
+                          const int64_t gbase[], const hj_star_fact *fact, const int32_t *sval, int64_t n,
+                          int64_t *out_key, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                          int64_t out_cap, uint64_t *d_count, void *stream);
+
 /* Radix partition of rows into nparts (1..8192) groups by a key hash independent of
  * the table's slot hash: out_tuples (2*n int64) receives packed {key, pay}
  * tuples grouped by partition in order 0..nparts-1, d_counts (nparts uint64)

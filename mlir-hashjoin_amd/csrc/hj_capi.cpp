@@ -3131,18 +3131,21 @@ StarGroups star_groups(const hj_star *s) {
     return g;
 }
 
-// Both star aggregate entry points behind their casts: the checks in hj.h's order, then the launches.
+// The star aggregate's and the star query's entry points behind their casts: the checks in hj.h's order, then the
+// launches.  query: hj_dev_star_query_* (ndims == 0 is legal, `fact` may be given); else fact is null.
 int do_star_aggregate(hj_star *s, int layout, int ndims, hj_ctx *const dims[], const int kinds[],
                       const void *const skeys[], const unsigned long long null_pay[], const int gshift[],
                       const int64_t gbase[], const void *sval, int64_t n, void *out_key, void *out_cnt, void *out_sum,
-                      void *out_min, void *out_max, int64_t cap, uint64_t *d_count, void *stream) {
+                      void *out_min, void *out_max, int64_t cap, uint64_t *d_count, void *stream,
+                      const hj_star_fact *fact = nullptr, bool query = false) {
     if (!s) HJ_FAIL(HJ_ERR_ARG, "null star");
-    if (ndims < 1 || ndims > HJ_STAR_MAX_DIMS)
-        HJ_FAIL(HJ_ERR_ARG, "star aggregate: ndims must be in 1.." + std::to_string(HJ_STAR_MAX_DIMS));
-    if (!dims || !kinds || !skeys || !null_pay || !gshift)
-        HJ_FAIL(HJ_ERR_ARG, "star aggregate: null dims, kinds, skeys, null-value or gshift array");
+    const std::string what = query ? "star query" : "star aggregate";
+    if (ndims < (query ? 0 : 1) || ndims > HJ_STAR_MAX_DIMS)
+        HJ_FAIL(HJ_ERR_ARG, what + ": ndims must be in " + (query ? "0.." : "1..") + std::to_string(HJ_STAR_MAX_DIMS));
+    if (ndims > 0 && (!dims || !kinds || !skeys || !null_pay || !gshift))
+        HJ_FAIL(HJ_ERR_ARG, what + ": null dims, kinds, skeys, null-value or gshift array");
     for (int d = 0; d < ndims; ++d) {
-        const std::string who = "star aggregate: dimension " + std::to_string(d);
+        const std::string who = what + ": dimension " + std::to_string(d);
         const hj_ctx *c = dims[d];
         if (!c) HJ_FAIL(HJ_ERR_ARG, who + ": null context");
         if (kinds[d] != HJ_STAR_INNER && kinds[d] != HJ_STAR_LEFT && kinds[d] != HJ_STAR_ANTI)
@@ -3155,13 +3158,35 @@ int do_star_aggregate(hj_star *s, int layout, int ndims, hj_ctx *const dims[], c
         if (c->used != HJ_STRATEGY_GLOBAL && !c->dual)
             HJ_FAIL(HJ_ERR_STATE, who + ": a radix-only build has no global table (build it under HJ_STRATEGY_GLOBAL)");
     }
-    if (!s->groups) HJ_FAIL(HJ_ERR_STATE, "star aggregate: no group table (call hj_star_reserve_groups first)");
+    if (fact) {
+        if (fact->npreds < 0 || fact->npreds > HJ_STAR_MAX_PREDS)
+            HJ_FAIL(HJ_ERR_ARG, "star query: fact.npreds must be in 0.." + std::to_string(HJ_STAR_MAX_PREDS));
+        for (int p = 0; p < fact->npreds; ++p)
+            if (fact->pkind[p] != HJ_PRED_IN && fact->pkind[p] != HJ_PRED_OUT)
+                HJ_FAIL(HJ_ERR_ARG, "star query: fact.pkind[" + std::to_string(p) + "] must be HJ_PRED_IN or HJ_PRED_OUT");
+        if (fact->vop < HJ_VALUE_A || fact->vop > HJ_VALUE_MUL)
+            HJ_FAIL(HJ_ERR_ARG, "star query: fact.vop must be HJ_VALUE_A, _ADD, _SUB or _MUL");
+        if (fact->nfact < 0 || fact->nfact > HJ_STAR_MAX_FACT_GROUPS)
+            HJ_FAIL(HJ_ERR_ARG, "star query: fact.nfact must be in 0.." + std::to_string(HJ_STAR_MAX_FACT_GROUPS));
+        for (int f = 0; f < fact->nfact; ++f)
+            if (fact->fshift[f] < 0 || fact->fshift[f] > 63)
+                HJ_FAIL(HJ_ERR_ARG, "star query: fact.fshift[" + std::to_string(f) + "] must be in 0..63");
+    }
+    if (!s->groups) HJ_FAIL(HJ_ERR_STATE, what + ": no group table (call hj_star_reserve_groups first)");
     if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
     if (n < 0) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: a negative row count");
     for (int d = 0; d < ndims; ++d)
         if (n > 0 && !skeys[d]) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: dimension " + std::to_string(d) + " has null keys");
+    if (fact && n > 0) {
+        for (int p = 0; p < fact->npreds; ++p)
+            if (!fact->pcol[p]) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: fact.pcol[" + std::to_string(p) + "] is null");
+        for (int f = 0; f < fact->nfact; ++f)
+            if (!fact->fcol[f]) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: fact.fcol[" + std::to_string(f) + "] is null");
+    }
     const bool vals = out_sum || out_min || out_max;
-    if (vals && !sval && n > 0) HJ_FAIL(HJ_ERR_ARG, "star aggregate: sum, min or max without a value column");
+    if (vals && !sval && n > 0) HJ_FAIL(HJ_ERR_ARG, what + ": sum, min or max without a value column");
+    if (fact && fact->vop != HJ_VALUE_A && vals && !fact->vb && n > 0)
+        HJ_FAIL(HJ_ERR_ARG, "star query: fact.vb is null under a vop other than HJ_VALUE_A with sum, min or max asked for");
     const bool any = out_key || out_cnt || vals;
     if (cap < 0) HJ_FAIL(HJ_ERR_ARG, "negative output capacity");
     if (cap > 0 && !any) HJ_FAIL(HJ_ERR_ARG, "out_cap > 0 with every output null (the count form is out_cap == 0)");
@@ -3185,8 +3210,32 @@ int do_star_aggregate(hj_star *s, int layout, int ndims, hj_ctx *const dims[], c
     a.gt = g.t;
     a.acc = hj::GroupAcc{g.acc.cnt, out_sum ? g.acc.sum : nullptr, out_min ? g.acc.mn : nullptr,
                          out_max ? g.acc.mx : nullptr};
+    // the fact side; one that asks for nothing (and a dimension to walk) is the star aggregate's own kernel
+    bool fact_pass = ndims == 0;
+    hj::StarFact ff{};
+    if (fact) {
+        static_assert(hj::kStarMaxPreds == HJ_STAR_MAX_PREDS && hj::kStarMaxFactGroups == HJ_STAR_MAX_FACT_GROUPS &&
+                      hj::kStarValueMul == HJ_VALUE_MUL, "hj.h and hj_internal.h agree");
+        ff.npreds = fact->npreds;
+        for (int p = 0; p < fact->npreds; ++p) {
+            ff.pcol[p] = fact->pcol[p];
+            ff.plo[p] = fact->plo[p];
+            ff.phi[p] = fact->phi[p];
+            ff.pkind[p] = fact->pkind[p];
+        }
+        ff.vop = vals ? fact->vop : HJ_VALUE_A;
+        ff.vb = ff.vop != HJ_VALUE_A ? fact->vb : nullptr;
+        ff.nfact = fact->nfact;
+        for (int f = 0; f < fact->nfact; ++f) {
+            ff.fcol[f] = fact->fcol[f];
+            ff.fshift[f] = fact->fshift[f];
+            ff.fbase[f] = fact->fbase[f];
+        }
+        fact_pass |= fact->npreds > 0 || ff.vop != HJ_VALUE_A || fact->nfact > 0;
+    }
     const hj::GroupOut out{out_key, out_cnt, out_sum, out_min, out_max, cap, (unsigned long long *)d_count, 0ull, 0};
-    HJ_HIP(hj::launch_star_aggregate(layout, ndims, a, out, &s->plan, (hipStream_t)stream));
+    HJ_HIP(hj::launch_star_aggregate(layout, ndims, a, out, &s->plan, (hipStream_t)stream,
+                                     fact_pass ? &ff : nullptr));
     return HJ_OK;
 }
 
@@ -3273,6 +3322,29 @@ int hj_dev_star_aggregate_i32(hj_star *s, int ndims, hj_ctx *const dims[], const
     return do_star_aggregate(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys, null_row ? nulls : nullptr,
                              gshift, gbase, sval, n, out_key, out_cnt, out_sum, out_min, out_max, out_cap, d_count,
                              stream);
+}
+
+int hj_dev_star_query_i64(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
+                          const int64_t *const skeys[], const int64_t null_pay[], const int gshift[],
+                          const int64_t gbase[], const hj_star_fact *fact, const int64_t *sval, int64_t n,
+                          int64_t *out_key, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                          int64_t out_cap, uint64_t *d_count, void *stream) {
+    return do_star_aggregate(s, kWide, ndims, dims, kinds, (const void *const *)skeys,
+                             (const unsigned long long *)null_pay, gshift, gbase, sval, n, out_key, out_cnt, out_sum,
+                             out_min, out_max, out_cap, d_count, stream, fact, true);
+}
+
+int hj_dev_star_query_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
+                          const int32_t *const skeys[], const int32_t null_row[], const int gshift[],
+                          const int64_t gbase[], const hj_star_fact *fact, const int32_t *sval, int64_t n,
+                          int64_t *out_key, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
+                          int64_t out_cap, uint64_t *d_count, void *stream) {
+    unsigned long long nulls[HJ_STAR_MAX_DIMS] = {};
+    if (null_row && ndims >= 1 && ndims <= HJ_STAR_MAX_DIMS)
+        for (int d = 0; d < ndims; ++d) nulls[d] = (unsigned long long)(long long)null_row[d];
+    return do_star_aggregate(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys, null_row ? nulls : nullptr,
+                             gshift, gbase, sval, n, out_key, out_cnt, out_sum, out_min, out_max, out_cap, d_count,
+                             stream, fact, true);
 }
 
 int hj_star_reserve(hj_star *s, int64_t max_rows) {

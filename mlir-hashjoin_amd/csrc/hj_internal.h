@@ -593,6 +593,23 @@ hipError_t star_prepare();
 hipError_t launch_star(int layout, int ndims, StarArgs a, const FilterWork &ws, StarPlan *plan, hipStream_t st);
 // Star aggregate (hj_kernels.hip, k_star_agg; hj.h "Star aggregate"): GROUP BY
 // over the star probe's qualifying rows in one pass.  d[].out is not read.
+// The star query's fact side (hj.h "Star query", hj_star_fact): predicates on
+// fact columns, the value's second operand and the group key's fact fields.
+// Every column has the call's layout (int64 / int32, sign-extended).
+constexpr int kStarMaxPreds = 4, kStarMaxFactGroups = 2;
+enum StarValueOp : int { kStarValueA = 0, kStarValueAdd = 1, kStarValueSub = 2, kStarValueMul = 3 };
+struct StarFact {
+    const void *pcol[kStarMaxPreds]; // predicate p admits row j iff (plo <= pcol[j] <= phi) != (pkind == 1)
+    long long plo[kStarMaxPreds], phi[kStarMaxPreds];
+    int pkind[kStarMaxPreds];
+    int npreds;
+    int vop;                         // v(j) = sval[j] <vop> vb[j], wrapping int64
+    const void *vb;                  // null: vop is kStarValueA, or none of sum / min / max
+    const void *fcol[kStarMaxFactGroups];   // the key's fact field f: (fcol[j] - fbase) << fshift
+    long long fbase[kStarMaxFactGroups];
+    int fshift[kStarMaxFactGroups];
+    int nfact;
+};
 struct StarAggArgs {                 // by value in the kernel arguments
     StarDim d[kStarMaxDims];
     long long gbase[kStarMaxDims];   // the group key's field of dimension d: (payload - gbase) << gshift
@@ -605,13 +622,19 @@ struct StarAggArgs {                 // by value in the kernel arguments
     GroupAcc acc;                    // its accumulators (wide), slots + 1 entries
     unsigned long long *counter;     // set by launch_star_aggregate: out.counter, whose bit 63 is the overflow flag
 };
+struct StarQueryArgs : StarAggArgs { // the FACT instantiations' arguments; the others take StarAggArgs as before
+    StarFact f;
+};
 // Kernels only: the group table's fill, k_aggregate_init (it zeroes
 // out.counter), k_star_agg (n > 0) and k_emit_aggregate<kWide>.  Placement as
 // launch_star's over the tables the pass walks (INNER, ANTI, grouped LEFT), the
 // budget being min(kLdsPerCu, 160 KiB - the kernel's static LDS).  out.r is
 // the group key column; every out column is int64.  star_prepare covers it.
+// fact (the star query): the pass is the FACT instantiation over *fact;
+// ndims == 0 is then legal: no dimension is walked, no table read, no LDS asked
+// for beside the static one.  Null: the star aggregate's own instantiation.
 hipError_t launch_star_aggregate(int layout, int ndims, StarAggArgs a, const GroupOut &out, StarPlan *plan,
-                                 hipStream_t st);
+                                 hipStream_t st, const StarFact *fact = nullptr);
 // launches of exclusive_scan_u64 over len words (hj_radix.hip)
 int exclusive_scan_launches(unsigned long long len);
 

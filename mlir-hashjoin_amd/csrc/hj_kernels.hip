@@ -2323,8 +2323,24 @@ __device__ __forceinline__ unsigned long long agg_slot_bounded(Slot64 *sl, const
     return ~0ull;
 }
 
-template <int L, int ND>
-__global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(StarAggArgs a) {
+// FACT (hj.h "Star query"): the fact row's own part of the query, in front of
+// and behind the walks; the instantiations without it are the star aggregate's
+// code unchanged.  Per tile
+//   0. the predicates a.f.pcol[0 .. npreds) in the caller's order, one loop
+//      body (one set of eight values live): the column is loaded for the rows
+//      still alive and compared as signed int64.  A row that failed loads no
+//      further predicate column and no key, and walks no table.
+//   1. the walks, over what is left.
+//   2. sval, then a.f.vb when the value is an expression, for the survivors.
+//   2a. each a.f.fcol for the survivors, folded into the group key.
+//   3. unchanged.
+// With a predicate the column loaded ahead for the next tile is pcol[0] (every
+// row of the tile reads it; the first walked dimension's keys are then read by
+// the predicates' survivors alone).  ndims == 0 runs ND = 1 with nwalk == 0 and
+// a LEFT, ungrouped dummy dimension the prologue skips.
+template <int L, int ND, bool FACT = false>
+__global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(
+    std::conditional_t<FACT, StarQueryArgs, StarAggArgs> a) {
     using slot_t = typename Lay<L>::slot_t;
     constexpr long long kMaxPay = 0x7fffffffffffffffll;
     __shared__ AggTile<kWide> lt;
@@ -2384,8 +2400,13 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(StarAggArgs a)
 #pragma unroll
         for (int i = 0; i < kProbeItems; ++i) K[i] = (rows >> i) & 1u ? star_key<L>(col, row_of(q, i)) : star_key_t<L>(0);
     };
-    // loaded ahead: the first walked dimension's keys of the next tile
+    // loaded ahead: the first walked dimension's keys of the next tile (FACT with a predicate: its first column)
+    bool pred_first = false;   // (uniform)
     const void *first_col = a.nwalk > 0 ? a.d[a.order[0]].key : nullptr;
+    if constexpr (FACT) {
+        pred_first = a.f.npreds > 0;
+        if (pred_first) first_col = a.f.pcol[0];
+    }
     star_key_t<L> KN[kProbeItems] = {};
     const unsigned long long step = (unsigned long long)gridDim.x * teams, q0 = (unsigned long long)blockIdx.x * teams + team;
     if (q0 < nt && first_col) load_keys(first_col, q0, valid_of(q0), KN);
@@ -2400,6 +2421,27 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(StarAggArgs a)
         for (int i = 0; i < kProbeItems; ++i) KF[i] = KN[i];
         if (qn < nt && first_col) load_keys(first_col, qn, valid_of(qn), KN);
         unsigned long long G[kProbeItems] = {};
+        if constexpr (FACT) {
+#pragma unroll 1
+            for (int p = 0; p < a.f.npreds; ++p) {
+                star_key_t<L> K[kProbeItems];
+                if (p == 0) {
+#pragma unroll
+                    for (int i = 0; i < kProbeItems; ++i) K[i] = KF[i];
+                } else {
+                    load_keys(a.f.pcol[p], q, alive, K);
+                }
+                const long long lo = a.f.plo[p], hi = a.f.phi[p];
+                const bool outside = a.f.pkind[p] != 0;   // (uniform)
+                unsigned pass = 0;
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i) {
+                    const long long x = L == kWide ? (long long)K[i] : (long long)(int)K[i];
+                    pass |= ((x >= lo && x <= hi) != outside) ? 1u << i : 0u;
+                }
+                alive &= pass;
+            }
+        }
 #pragma unroll 1
         for (int j = 0; j < a.nwalk; ++j) {
             const int d = a.order[j];   // (uniform)
@@ -2407,7 +2449,7 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(StarAggArgs a)
             const int gs = a.gshift[d];
             star_key_t<L> K[kProbeItems];
             long long RP[kProbeItems];
-            if (j == 0) {
+            if (j == 0 && !pred_first) {
 #pragma unroll
                 for (int i = 0; i < kProbeItems; ++i) K[i] = KF[i];
             } else {
@@ -2434,6 +2476,32 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(StarAggArgs a)
             if (vals && ((alive >> i) & 1u)) {
                 if constexpr (L == kWide) V[i] = ((const unsigned long long *)a.sval)[row_of(q, i)];
                 else V[i] = (unsigned long long)(long long)((const int *)a.sval)[row_of(q, i)];
+            }
+        }
+        if constexpr (FACT) {
+            auto fact_word = [&](const void *col, int i) {   // a fact column's value of row slot i, sign-extended
+                if constexpr (L == kWide) return ((const unsigned long long *)col)[row_of(q, i)];
+                else return (unsigned long long)(long long)((const int *)col)[row_of(q, i)];
+            };
+            if (vals && a.f.vop != kStarValueA) {   // (uniform)
+                const int op = a.f.vop;
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i) {
+                    if (!((alive >> i) & 1u)) continue;
+                    const unsigned long long b = fact_word(a.f.vb, i);
+                    V[i] = op == kStarValueAdd ? V[i] + b : op == kStarValueSub ? V[i] - b : V[i] * b;
+                }
+            }
+#pragma unroll 1
+            for (int f = 0; f < a.f.nfact; ++f) {
+                const void *col = a.f.fcol[f];
+                const unsigned long long base = (unsigned long long)a.f.fbase[f];
+                const int fs = a.f.fshift[f];
+#pragma unroll
+                for (int i = 0; i < kProbeItems; ++i) {
+                    if (!((alive >> i) & 1u)) continue;
+                    G[i] += (fact_word(col, i) - base) << fs;
+                }
             }
         }
         __syncthreads();   // the table is clear, s_stop is everybody's
@@ -3033,15 +3101,17 @@ star_kernel_t star_kernel(int layout, int ndims, int mode) {
     default: return nullptr;
     }
 }
-typedef void (*star_agg_kernel_t)(StarAggArgs);
-star_agg_kernel_t star_agg_kernel(int layout, int ndims) {
+template <bool FACT>
+using star_agg_kernel_t = void (*)(std::conditional_t<FACT, StarQueryArgs, StarAggArgs>);
+template <bool FACT>
+star_agg_kernel_t<FACT> star_agg_kernel(int layout, int ndims) {
     if (layout != kWide && layout != kNarrow) return nullptr;
     const bool w = layout == kWide;
     switch (ndims) {
-    case 1: return w ? k_star_agg<kWide, 1> : k_star_agg<kNarrow, 1>;
-    case 2: return w ? k_star_agg<kWide, 2> : k_star_agg<kNarrow, 2>;
-    case 3: return w ? k_star_agg<kWide, 3> : k_star_agg<kNarrow, 3>;
-    case 4: return w ? k_star_agg<kWide, 4> : k_star_agg<kNarrow, 4>;
+    case 1: return w ? k_star_agg<kWide, 1, FACT> : k_star_agg<kNarrow, 1, FACT>;
+    case 2: return w ? k_star_agg<kWide, 2, FACT> : k_star_agg<kNarrow, 2, FACT>;
+    case 3: return w ? k_star_agg<kWide, 3, FACT> : k_star_agg<kNarrow, 3, FACT>;
+    case 4: return w ? k_star_agg<kWide, 4, FACT> : k_star_agg<kNarrow, 4, FACT>;
     default: return nullptr;
     }
 }
@@ -3056,17 +3126,24 @@ hipError_t star_prepare() {
                 if (e != hipSuccess) return e;
             }
     for (int layout : {(int)kWide, (int)kNarrow})
-        for (int nd = 1; nd <= kStarMaxDims; ++nd) {
-            const hipError_t e = hipFuncSetAttribute((const void *)star_agg_kernel(layout, nd),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
-            if (e != hipSuccess) return e;
-        }
+        for (int nd = 1; nd <= kStarMaxDims; ++nd)
+            for (const void *k : {(const void *)star_agg_kernel<false>(layout, nd),
+                                  (const void *)star_agg_kernel<true>(layout, nd)}) {
+                const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
+                if (e != hipSuccess) return e;
+            }
     return hipSuccess;
 }
 
 hipError_t launch_star_aggregate(int layout, int ndims, StarAggArgs a, const GroupOut &out, StarPlan *plan,
-                                 hipStream_t st) {
-    if (ndims < 1 || ndims > kStarMaxDims || (layout != kWide && layout != kNarrow)) return hipErrorInvalidValue;
+                                 hipStream_t st, const StarFact *fact) {
+    if (ndims < (fact ? 0 : 1) || ndims > kStarMaxDims || (layout != kWide && layout != kNarrow))
+        return hipErrorInvalidValue;
+    if (ndims == 0) {   // the ND = 1 instantiation over a dimension that is never walked
+        a.d[0] = StarDim{};
+        a.d[0].kind = kStarLeft;
+        a.gshift[0] = -1;
+    }
     const unsigned long long cap = a.gt.mask + 1ull, entries = cap + 1ull;
     a.counter = out.counter;
     hipError_t e = launch_init(a.gt, kWide, cap, st);
@@ -3122,7 +3199,15 @@ hipError_t launch_star_aggregate(int layout, int ndims, StarAggArgs a, const Gro
         }
         const unsigned mostw = (unsigned)cu_count() * per_cu, want = (tiles + teams - 1) / teams;
         const unsigned grid = mostw < want ? mostw : want;
-        hipLaunchKernelGGL(star_agg_kernel(layout, ndims), dim3(grid), dim3(kBlock * teams), lds_bytes, st, a);
+        if (fact) {
+            StarQueryArgs qa{};
+            static_cast<StarAggArgs &>(qa) = a;
+            qa.f = *fact;
+            hipLaunchKernelGGL(star_agg_kernel<true>(layout, ndims ? ndims : 1), dim3(grid), dim3(kBlock * teams),
+                               lds_bytes, st, qa);
+        } else {
+            hipLaunchKernelGGL(star_agg_kernel<false>(layout, ndims), dim3(grid), dim3(kBlock * teams), lds_bytes, st, a);
+        }
         *plan = StarPlan{4, grid, (long long)tiles, lds_dims, (long long)lds_bytes};
     }
     const unsigned tl = grid_for((long long)cap, kProbeTile), g = tl < most ? tl : most;

@@ -76,6 +76,24 @@ _i64 = C.c_int64
 _u64 = C.c_uint64
 _int = C.c_int
 
+# the star query (hj.h "Star query"): the fact side of a call
+HJ_STAR_MAX_PREDS = 4
+HJ_STAR_MAX_FACT_GROUPS = 2
+HJ_PRED_IN = 0
+HJ_PRED_OUT = 1
+HJ_VALUE_A = 0
+HJ_VALUE_ADD = 1
+HJ_VALUE_SUB = 2
+HJ_VALUE_MUL = 3
+
+
+class StarFact(C.Structure):
+    """hj_star_fact: a host struct read at call time."""
+    _fields_ = [("npreds", _int), ("pcol", _vp * HJ_STAR_MAX_PREDS), ("plo", _i64 * HJ_STAR_MAX_PREDS),
+                ("phi", _i64 * HJ_STAR_MAX_PREDS), ("pkind", _int * HJ_STAR_MAX_PREDS), ("vop", _int), ("vb", _vp),
+                ("nfact", _int), ("fcol", _vp * HJ_STAR_MAX_FACT_GROUPS), ("fshift", _int * HJ_STAR_MAX_FACT_GROUPS),
+                ("fbase", _i64 * HJ_STAR_MAX_FACT_GROUPS)]
+
 
 def _load():
     # One HIP runtime per process: PyTorch-ROCm ships its own libamdhip64.so
@@ -189,6 +207,12 @@ def _load():
         "hj_dev_star_aggregate_i32": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(_vp),
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(_i64), _vp, _i64, _vp,
                                              _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_star_query_i64": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(_vp),
+                                         C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(StarFact), _vp,
+                                         _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+        "hj_dev_star_query_i32": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(_vp),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(StarFact),
+                                         _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
         "hj_dev_partition_i64": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_dev_partition_tuples_i64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
         "hj_partition_of": (_int, [_i64, _int]),

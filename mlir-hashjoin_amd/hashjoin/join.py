@@ -22,7 +22,8 @@ import os
 import torch
 
 from ._lib import (HJ_ASOF_BACKWARD, HJ_ASOF_FORWARD, HJ_ASOF_STRICT, HJ_ERR_RANGE, HJ_EXISTS_ANTI, HJ_EXISTS_SEMI, HJ_EXPAND_INNER, HJ_EXPAND_OUTER, HJ_FILTER_PASS, HJ_FILTER_REJECT, HJ_GROUP_ALL, HJ_GROUP_MATCHED, HJ_KEYS_MAX_COLS, HJ_OK, HJ_OUTER_BUILD, HJ_OUTER_FULL, HJ_STAR_ANTI, HJ_STAR_INNER, HJ_STAR_LEFT, HJ_STAR_MAX_DIMS, HJ_STRATEGY_AUTO,
-                   HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, HJError, check, lib)
+                   HJ_PRED_IN, HJ_PRED_OUT, HJ_STAR_MAX_FACT_GROUPS, HJ_STAR_MAX_PREDS, HJ_STRATEGY_GLOBAL, HJ_STRATEGY_RADIX, HJ_VALUE_ADD,
+                   HJ_VALUE_MUL, HJ_VALUE_SUB, HJError, StarFact, check, lib)
 
 STRATEGIES = {"auto": HJ_STRATEGY_AUTO, "global": HJ_STRATEGY_GLOBAL, "radix": HJ_STRATEGY_RADIX}
 EXISTS_KINDS = {"semi": HJ_EXISTS_SEMI, "anti": HJ_EXISTS_ANTI}
@@ -33,6 +34,8 @@ EXPAND_KINDS = {"inner": HJ_EXPAND_INNER, "outer": HJ_EXPAND_OUTER}
 FILTER_KINDS = {"pass": HJ_FILTER_PASS, "reject": HJ_FILTER_REJECT}
 ASOF_DIRECTIONS = {"backward": HJ_ASOF_BACKWARD, "forward": HJ_ASOF_FORWARD}
 STAR_KINDS = {"inner": HJ_STAR_INNER, "left": HJ_STAR_LEFT, "anti": HJ_STAR_ANTI}
+STAR_PREDS = {"in": HJ_PRED_IN, "out": HJ_PRED_OUT}
+STAR_VALUE_OPS = {"add": HJ_VALUE_ADD, "sub": HJ_VALUE_SUB, "mul": HJ_VALUE_MUL}
 
 
 def _ptr(t):
@@ -394,10 +397,10 @@ class StarProbe:
                     lds_dims=[bool((ld.value >> d) & 1) for d in range(HJ_STAR_MAX_DIMS)], lds_bytes=b.value)
 
     @staticmethod
-    def _dims(dims):
+    def _dims(dims, least=1):
         """(contexts, key columns, kinds, nulls) of a dimension list; raises on a malformed one."""
-        if not 1 <= len(dims) <= HJ_STAR_MAX_DIMS:
-            raise ValueError(f"a star probe takes 1..{HJ_STAR_MAX_DIMS} dimensions")
+        if not least <= len(dims) <= HJ_STAR_MAX_DIMS:
+            raise ValueError(f"a star probe takes {least}..{HJ_STAR_MAX_DIMS} dimensions")
         hjs, keys, kinds, nulls = [], [], [], []
         for d in dims:
             if len(d) not in (3, 4):
@@ -555,6 +558,102 @@ class StarProbe:
                 return {"key": out_key[:g], **{a: c[:g] for a, c in cols.items()}}
             cap = g
         raise RuntimeError("star aggregate output did not fit after resizing")
+
+    # ---- star query (hj.h "Star query"): the star aggregate with fact-side predicates, a two-column value
+    # expression and fact-side group fields in the same pass
+    def query_into(self, dims, val=None, out_key=None, out_cnt=None, out_sum=None, out_min=None, out_max=None,
+                   count=None, where=None, expr=None, fact_group=None, group=None, base=None, stream=None):
+        """aggregate_into over the rows that also pass every predicate of
+        `where` -- (col, lo, hi[, "in" | "out"]): lo <= col <= hi, or outside it
+        -- with the value val <op> col_b under expr = (op, col_b), op in "add" |
+        "sub" | "mul" (wrapping int64), and each fact_group entry (col, shift,
+        base) adding the field (col - base) << shift to the group key.  Every
+        fact column has the key columns' dtype and length.  dims may be empty:
+        a filtered GROUP BY over the fact columns alone, dtype and length then
+        taken from the first fact column given.  Returns count."""
+        hjs, keys, kinds, nulls = self._dims(dims, least=0)
+        nd = len(dims)
+        where = [] if where is None else [tuple(w) for w in where]
+        fact_group = [] if fact_group is None else [tuple(f) for f in fact_group]
+        if len(where) > HJ_STAR_MAX_PREDS or any(len(w) not in (3, 4) for w in where):
+            raise ValueError(f"where takes up to {HJ_STAR_MAX_PREDS} predicates (col, lo, hi[, 'in' | 'out'])")
+        if len(fact_group) > HJ_STAR_MAX_FACT_GROUPS or any(len(f) != 3 for f in fact_group):
+            raise ValueError(f"fact_group takes up to {HJ_STAR_MAX_FACT_GROUPS} entries (col, shift, base)")
+        if expr is not None and (len(expr) != 2 or expr[0] not in STAR_VALUE_OPS):
+            raise ValueError("expr is None or (op, col_b) with op in 'add', 'sub', 'mul'")
+        fcols = [w[0] for w in where] + [f[0] for f in fact_group] + ([expr[1]] if expr is not None else [])
+        shape = keys + [c for c in fcols + [val] if c is not None]
+        if not shape:
+            raise ValueError("a star query without a dimension needs a fact column")
+        dt, n = shape[0].dtype, shape[0].numel()
+        for c in shape:
+            if not isinstance(c, torch.Tensor) or c.dim() != 1 or c.dtype != dt or c.numel() != n or \
+                    dt not in (torch.int64, torch.int32):
+                raise ValueError("the fact columns are 1-D int64 / int32 tensors of the key columns' dtype and length")
+        group = [-1] * nd if group is None else [-1 if g is None else int(g) for g in group]
+        base = [0] * nd if base is None else [int(b) for b in base]
+        if len(group) != nd or len(base) != nd:
+            raise ValueError("group and base need one entry per dimension")
+        outs = [o for o in (out_key, out_cnt, out_sum, out_min, out_max) if o is not None]
+        _need_cuda(*shape, *outs)
+        if any(o.dtype != torch.int64 or o.dim() != 1 for o in outs):
+            raise ValueError("the star query's output columns are int64")
+        cap = outs[0].shape[0] if outs else 0
+        if any(o.shape[0] != cap for o in outs):
+            raise ValueError("output columns differ in length")
+        fact = StarFact()
+        fact.npreds = len(where)
+        for p, w in enumerate(where):
+            fact.pcol[p], fact.plo[p], fact.phi[p] = w[0].data_ptr(), int(w[1]), int(w[2])
+            fact.pkind[p] = STAR_PREDS[w[3] if len(w) == 4 else "in"]
+        if expr is not None:
+            fact.vop, fact.vb = STAR_VALUE_OPS[expr[0]], _ptr(expr[1])
+        fact.nfact = len(fact_group)
+        for f, (col, shift, fbase) in enumerate(fact_group):
+            fact.fcol[f], fact.fshift[f], fact.fbase[f] = col.data_ptr(), int(shift), int(fbase)
+        count = self._count if count is None else count
+        wide = dt == torch.int64
+        a_ctx = (C.c_void_p * nd)(*[h._ctx for h in hjs]) if nd else None
+        a_kind = (C.c_int * nd)(*kinds) if nd else None
+        a_key = (C.c_void_p * nd)(*[k.data_ptr() for k in keys]) if nd else None
+        a_shift = (C.c_int * nd)(*group) if nd else None
+        a_base = (C.c_int64 * nd)(*base) if nd else None
+        a_null = ((C.c_int64 if wide else C.c_int32) * nd)(*nulls) if nd else None
+        f = lib.hj_dev_star_query_i64 if wide else lib.hj_dev_star_query_i32
+        check(f(self._s, nd, a_ctx, a_kind, a_key, a_null, a_shift, a_base, C.byref(fact), _ptr(val), n, _ptr(out_key),
+                _ptr(out_cnt), _ptr(out_sum), _ptr(out_min), _ptr(out_max), cap, _ptr(count),
+                _stream(self.device, stream)), "hj_dev_star_query_i64" if wide else "hj_dev_star_query_i32")
+        return count
+
+    def query(self, dims, val=None, aggs=("count", "sum"), where=None, expr=None, fact_group=None, group=None,
+              base=None, max_groups=None, capacity=None, stream=None):
+        """aggregate's dict over query_into: {"key": tensor, agg: tensor, ...}
+        trimmed to G.  Raises HJError when the group table overflowed.
+        Synchronises to read G."""
+        if any(a not in GROUP_AGGS for a in aggs):
+            raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
+        if max_groups is not None:
+            self.reserve_groups(max_groups)
+        kw = dict(where=where, expr=expr, fact_group=fact_group, group=group, base=base, stream=stream)
+
+        def groups(cnt):
+            g = int(cnt.item())
+            if g < 0:   # bit 63 (hj.h)
+                raise HJError(f"star query: more groups than the group table of {self.group_capacity} slots "
+                              "admits (reserve_groups)")
+            return g
+
+        cap = groups(self.query_into(dims, val, **kw)) if capacity is None else int(capacity)
+        for _ in range(2):
+            cap = max(1, cap)
+            out_key = torch.empty(cap, dtype=torch.int64, device=self.device)
+            cols = {a: torch.empty(cap, dtype=torch.int64, device=self.device) for a in aggs}
+            g = groups(self.query_into(dims, val, out_key, cols.get("count"), cols.get("sum"), cols.get("min"),
+                                       cols.get("max"), **kw))
+            if g <= cap:
+                return {"key": out_key[:g], **{a: c[:g] for a, c in cols.items()}}
+            cap = g
+        raise RuntimeError("star query output did not fit after resizing")
 
 
 class HashJoin:
@@ -1767,6 +1866,92 @@ def star_aggregate(dims, val=None, group_by=None, aggs=("count", "sum"), max_gro
         star.close()   # (waits for the device before the contexts go)
         if kc is not None:
             kc.close()
+        for hj in hjs:
+            hj.close()
+
+
+def star_query(dims, val=None, where=None, expr=None, group_by=None, fact_group_by=None, aggs=("count", "sum"),
+               max_groups=None, device=None, stream=None):
+    """star_aggregate with the fact row's own part of the query: dims (may be
+    empty), val, group_by, aggs and max_groups as star_aggregate's; where and
+    expr as StarProbe.query_into's; fact_group_by a list of fact columns to
+    group by as well.  One key is laid out over the grouped dimensions' payload
+    fields followed by the fact columns' fields -- a fact column's width from
+    its observed minimum and maximum, a 0-bit field left out -- and unpacked
+    again: returns {"keys": [per dimension its payload column of the groups,
+    None where not grouped], "fact_keys": [per fact_group_by column its column
+    of the groups, in the column's dtype], agg: int64 tensor, ...}.  Raises
+    HJError (HJ_ERR_RANGE) when the fields need more than 64 bits together.
+    Synchronises."""
+    dims = list(dims)
+    group_by = [False] * len(dims) if group_by is None else [bool(g) for g in group_by]
+    fcols = [] if fact_group_by is None else list(fact_group_by)
+    if len(group_by) != len(dims):
+        raise ValueError("group_by needs one entry per dimension")
+    if len(fcols) > HJ_STAR_MAX_FACT_GROUPS:
+        raise ValueError(f"fact_group_by takes up to {HJ_STAR_MAX_FACT_GROUPS} columns")
+    some = [d[2] for d in dims] + [w[0] for w in (where or [])] + fcols + [c for c in (val,) if c is not None]
+    if not some:
+        raise ValueError("star_query needs a dimension or a fact column")
+    dev = some[0].device.index if device is None else device
+    n = some[0].numel()
+    hjs, star = [], StarProbe(dev)
+    try:
+        probe_dims, fields = [], []   # fields: (lo, hi) of every key field, the grouped dimensions' first
+        for d, g in zip(dims, group_by):
+            if len(d) not in (4, 5):
+                raise ValueError("a dimension is (rkey, rpay, skey, how[, null])")
+            rkey, rpay, skey, how = d[:4]
+            null = d[4] if len(d) == 5 and d[4] is not None else -1
+            if g and how == "anti":
+                raise ValueError("an anti dimension has no payload to group by")
+            hj = HashJoin(dev)
+            hjs.append(hj)
+            hj.set_strategy("global")
+            hj.build_table(rkey, rpay, stream=stream)
+            probe_dims.append((hj, skey, how, null))
+            if g:   # the values its payload takes: the build's payloads (i32: the row ids) and a LEFT null
+                vals = []
+                if rkey.numel():
+                    vals = [int(rpay.min()), int(rpay.max())] if rkey.dtype == torch.int64 else [0, rkey.numel() - 1]
+                if how == "left":
+                    vals.append(int(null))
+                fields.append((min(vals), max(vals)) if vals else (0, 0))
+        for c in fcols:
+            fields.append((int(c.min()), int(c.max())) if c.numel() else (0, 0))
+        bits = [(hi - lo).bit_length() for lo, hi in fields]
+        if sum(bits) > 64:
+            raise HJError(f"star_query failed with {HJ_ERR_RANGE}: the grouped ranges need {sum(bits)} bits together")
+        shifts = [sum(bits[i + 1:]) for i in range(len(bits))]
+        grouped = [i for i, g in enumerate(group_by) if g]
+        group, base = [-1] * len(dims), [0] * len(dims)
+        for k, i in enumerate(grouped):
+            if bits[k]:
+                group[i], base[i] = shifts[k], fields[k][0]
+        ng = len(grouped)
+        fact_group = [(c, shifts[ng + k], fields[ng + k][0]) for k, c in enumerate(fcols) if bits[ng + k]]
+        if max_groups is None:
+            max_groups = 1
+            for b in bits:
+                max_groups <<= b
+            max_groups = max(1, min(max_groups, n))
+        a = star.query(probe_dims, val, aggs=aggs, where=where, expr=expr, fact_group=fact_group, group=group,
+                       base=base, max_groups=max_groups, stream=stream)
+        key = a.pop("key")
+
+        def field(k, dtype):   # field k of every group key, back in its column's values
+            f = (key >> shifts[k]) & ((1 << bits[k]) - 1) if 0 < bits[k] < 64 else key if bits[k] else torch.zeros_like(key)
+            return (f + fields[k][0]).to(dtype)
+
+        keys = [None] * len(dims)
+        for k, i in enumerate(grouped):
+            keys[i] = field(k, probe_dims[i][1].dtype)
+        out = {"keys": keys, "fact_keys": [field(ng + k, c.dtype) for k, c in enumerate(fcols)]}
+        out.update(a)
+        torch.cuda.synchronize(dev)
+        return out
+    finally:
+        star.close()   # (waits for the device before the contexts go)
         for hj in hjs:
             hj.close()
 
