@@ -3052,51 +3052,83 @@ int star_work(hj_star *s, int64_t rows) {
     return HJ_OK;
 }
 
-// Both entry points behind their casts: the checks in hj.h's order, then the launches.
-int do_star(hj_star *s, int layout, int ndims, hj_ctx *const dims[], const int kinds[], const void *const skeys[],
-            const unsigned long long null_pay[], int64_t n, int64_t row_base, void *const out_pay[], void *out_row,
-            int64_t cap, uint64_t *d_count, void *stream) {
+// The checks every star entry point makes first, in hj.h's order.  what: its name in the messages; least: the fewest
+// dimensions it takes; grouped: it takes gshift, whose checks sit between the device's and the layout's.
+int star_check_dims(const std::string &what, int layout, int ndims, int least, const hj_star *s, hj_ctx *const dims[],
+                    const int kinds[], const void *skeys, const void *null_pay, const int gshift[], bool grouped) {
     if (!s) HJ_FAIL(HJ_ERR_ARG, "null star");
-    if (ndims < 1 || ndims > HJ_STAR_MAX_DIMS)
-        HJ_FAIL(HJ_ERR_ARG, "star probe: ndims must be in 1.." + std::to_string(HJ_STAR_MAX_DIMS));
-    if (!dims || !kinds || !skeys || !null_pay) HJ_FAIL(HJ_ERR_ARG, "star probe: null dims, kinds, skeys or null-value array");
+    if (ndims < least || ndims > HJ_STAR_MAX_DIMS)
+        HJ_FAIL(HJ_ERR_ARG,
+                what + ": ndims must be in " + std::to_string(least) + ".." + std::to_string(HJ_STAR_MAX_DIMS));
+    if (ndims > 0 && (!dims || !kinds || !skeys || !null_pay || (grouped && !gshift)))
+        HJ_FAIL(HJ_ERR_ARG, what + ": null dims, kinds, skeys" +
+                                (grouped ? ", null-value or gshift array" : " or null-value array"));
     for (int d = 0; d < ndims; ++d) {
-        const std::string who = "star probe: dimension " + std::to_string(d);
+        const std::string who = what + ": dimension " + std::to_string(d);
         const hj_ctx *c = dims[d];
         if (!c) HJ_FAIL(HJ_ERR_ARG, who + ": null context");
         if (kinds[d] != HJ_STAR_INNER && kinds[d] != HJ_STAR_LEFT && kinds[d] != HJ_STAR_ANTI)
             HJ_FAIL(HJ_ERR_ARG, who + ": kind must be HJ_STAR_INNER, HJ_STAR_LEFT or HJ_STAR_ANTI");
         if (c->device != s->device) HJ_FAIL(HJ_ERR_ARG, who + ": a context of another device");
+        if (grouped) {
+            if (gshift[d] < -1 || gshift[d] > 63) HJ_FAIL(HJ_ERR_ARG, who + ": gshift must be -1 or in 0..63");
+            if (kinds[d] == HJ_STAR_ANTI && gshift[d] >= 0)
+                HJ_FAIL(HJ_ERR_ARG, who + ": an ANTI dimension has no payload to group by");
+        }
         if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, who + ": no build of this layout");
         if (c->used != HJ_STRATEGY_GLOBAL && !c->dual)
             HJ_FAIL(HJ_ERR_STATE, who + ": a radix-only build has no global table (build it under HJ_STRATEGY_GLOBAL)");
     }
+    return HJ_OK;
+}
+
+int star_check_rows(const uint64_t *d_count, int64_t n, int ndims, const void *const skeys[]) {
     if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
     if (n < 0) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: a negative row count");
-    bool any_out = out_row != nullptr;
     for (int d = 0; d < ndims; ++d)
         if (n > 0 && !skeys[d]) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: dimension " + std::to_string(d) + " has null keys");
+    return HJ_OK;
+}
+
+int star_check_cap(int64_t cap, bool any_out) {
+    if (cap < 0) HJ_FAIL(HJ_ERR_ARG, "negative output capacity");
+    if (cap > 0 && !any_out) HJ_FAIL(HJ_ERR_ARG, "out_cap > 0 with every output null (the count form is out_cap == 0)");
+    if (cap == 0 && any_out) HJ_FAIL(HJ_ERR_ARG, "out_cap == 0 with an output (the count form takes none)");
+    return HJ_OK;
+}
+
+void star_fill_dims(hj::StarDim (&sd)[HJ_STAR_MAX_DIMS], int ndims, hj_ctx *const dims[], const int kinds[],
+                    const void *const skeys[], const unsigned long long null_pay[], void *const out_pay[]) {
+    for (int d = 0; d < ndims; ++d)
+        sd[d] = hj::StarDim{table_dev(dims[d]), skeys[d], out_pay ? out_pay[d] : nullptr, null_pay[d], kinds[d], -1};
+}
+
+// An _i32 entry point's null rows as the kernels' 64-bit null payloads, sign-extended into v; null stays null.
+const unsigned long long *widen_nulls(const int32_t null_row[], int ndims, unsigned long long (&v)[HJ_STAR_MAX_DIMS]) {
+    for (int d = 0; null_row && d < ndims && d < HJ_STAR_MAX_DIMS; ++d)
+        v[d] = (unsigned long long)(long long)null_row[d];
+    return null_row ? v : nullptr;
+}
+
+// Both entry points behind their casts: the checks in hj.h's order, then the launches.
+int do_star(hj_star *s, int layout, int ndims, hj_ctx *const dims[], const int kinds[], const void *const skeys[],
+            const unsigned long long null_pay[], int64_t n, int64_t row_base, void *const out_pay[], void *out_row,
+            int64_t cap, uint64_t *d_count, void *stream) {
+    HJ_TRY(star_check_dims("star probe", layout, ndims, 1, s, dims, kinds, skeys, null_pay, nullptr, false));
+    HJ_TRY(star_check_rows(d_count, n, ndims, skeys));
+    bool any_out = out_row != nullptr;
     for (int d = 0; d < ndims; ++d) {
         void *o = out_pay ? out_pay[d] : nullptr;
         if (o && kinds[d] == HJ_STAR_ANTI)
             HJ_FAIL(HJ_ERR_ARG, "star probe: dimension " + std::to_string(d) + ": an ANTI dimension has no payload column");
         any_out |= o != nullptr;
     }
-    if (cap < 0) HJ_FAIL(HJ_ERR_ARG, "negative output capacity");
-    if (cap > 0 && !any_out) HJ_FAIL(HJ_ERR_ARG, "out_cap > 0 with every output null (the count form is out_cap == 0)");
-    if (cap == 0 && any_out) HJ_FAIL(HJ_ERR_ARG, "out_cap == 0 with an output (the count form takes none)");
+    HJ_TRY(star_check_cap(cap, any_out));
     if (layout == kNarrow && (row_base < 0 || row_base > INT32_MAX - n)) HJ_FAIL(HJ_ERR_ARG, "row ids past 2^31 - 1");
     HJ_TRY(star_work(s, n));
     HJ_HIP(hipSetDevice(s->device));
     hj::StarArgs a{};
-    for (int d = 0; d < ndims; ++d) {
-        a.d[d].t = table_dev(dims[d]);
-        a.d[d].key = skeys[d];
-        a.d[d].out = out_pay ? out_pay[d] : nullptr;
-        a.d[d].null_pay = null_pay[d];
-        a.d[d].kind = kinds[d];
-        a.d[d].lds_off = -1;
-    }
+    star_fill_dims(a.d, ndims, dims, kinds, skeys, null_pay, out_pay);
     a.n = n;
     a.row_base = row_base;
     a.cap = cap;
@@ -3138,26 +3170,8 @@ int do_star_aggregate(hj_star *s, int layout, int ndims, hj_ctx *const dims[], c
                       const int64_t gbase[], const void *sval, int64_t n, void *out_key, void *out_cnt, void *out_sum,
                       void *out_min, void *out_max, int64_t cap, uint64_t *d_count, void *stream,
                       const hj_star_fact *fact = nullptr, bool query = false) {
-    if (!s) HJ_FAIL(HJ_ERR_ARG, "null star");
     const std::string what = query ? "star query" : "star aggregate";
-    if (ndims < (query ? 0 : 1) || ndims > HJ_STAR_MAX_DIMS)
-        HJ_FAIL(HJ_ERR_ARG, what + ": ndims must be in " + (query ? "0.." : "1..") + std::to_string(HJ_STAR_MAX_DIMS));
-    if (ndims > 0 && (!dims || !kinds || !skeys || !null_pay || !gshift))
-        HJ_FAIL(HJ_ERR_ARG, what + ": null dims, kinds, skeys, null-value or gshift array");
-    for (int d = 0; d < ndims; ++d) {
-        const std::string who = what + ": dimension " + std::to_string(d);
-        const hj_ctx *c = dims[d];
-        if (!c) HJ_FAIL(HJ_ERR_ARG, who + ": null context");
-        if (kinds[d] != HJ_STAR_INNER && kinds[d] != HJ_STAR_LEFT && kinds[d] != HJ_STAR_ANTI)
-            HJ_FAIL(HJ_ERR_ARG, who + ": kind must be HJ_STAR_INNER, HJ_STAR_LEFT or HJ_STAR_ANTI");
-        if (c->device != s->device) HJ_FAIL(HJ_ERR_ARG, who + ": a context of another device");
-        if (gshift[d] < -1 || gshift[d] > 63) HJ_FAIL(HJ_ERR_ARG, who + ": gshift must be -1 or in 0..63");
-        if (kinds[d] == HJ_STAR_ANTI && gshift[d] >= 0)
-            HJ_FAIL(HJ_ERR_ARG, who + ": an ANTI dimension has no payload to group by");
-        if (c->layout != layout) HJ_FAIL(HJ_ERR_STATE, who + ": no build of this layout");
-        if (c->used != HJ_STRATEGY_GLOBAL && !c->dual)
-            HJ_FAIL(HJ_ERR_STATE, who + ": a radix-only build has no global table (build it under HJ_STRATEGY_GLOBAL)");
-    }
+    HJ_TRY(star_check_dims(what, layout, ndims, query ? 0 : 1, s, dims, kinds, skeys, null_pay, gshift, true));
     if (fact) {
         if (fact->npreds < 0 || fact->npreds > HJ_STAR_MAX_PREDS)
             HJ_FAIL(HJ_ERR_ARG, "star query: fact.npreds must be in 0.." + std::to_string(HJ_STAR_MAX_PREDS));
@@ -3173,10 +3187,7 @@ int do_star_aggregate(hj_star *s, int layout, int ndims, hj_ctx *const dims[], c
                 HJ_FAIL(HJ_ERR_ARG, "star query: fact.fshift[" + std::to_string(f) + "] must be in 0..63");
     }
     if (!s->groups) HJ_FAIL(HJ_ERR_STATE, what + ": no group table (call hj_star_reserve_groups first)");
-    if (!d_count) HJ_FAIL(HJ_ERR_ARG, "null count pointer");
-    if (n < 0) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: a negative row count");
-    for (int d = 0; d < ndims; ++d)
-        if (n > 0 && !skeys[d]) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: dimension " + std::to_string(d) + " has null keys");
+    HJ_TRY(star_check_rows(d_count, n, ndims, skeys));
     if (fact && n > 0) {
         for (int p = 0; p < fact->npreds; ++p)
             if (!fact->pcol[p]) HJ_FAIL(HJ_ERR_ARG, "bad probe relation: fact.pcol[" + std::to_string(p) + "] is null");
@@ -3187,24 +3198,15 @@ int do_star_aggregate(hj_star *s, int layout, int ndims, hj_ctx *const dims[], c
     if (vals && !sval && n > 0) HJ_FAIL(HJ_ERR_ARG, what + ": sum, min or max without a value column");
     if (fact && fact->vop != HJ_VALUE_A && vals && !fact->vb && n > 0)
         HJ_FAIL(HJ_ERR_ARG, "star query: fact.vb is null under a vop other than HJ_VALUE_A with sum, min or max asked for");
-    const bool any = out_key || out_cnt || vals;
-    if (cap < 0) HJ_FAIL(HJ_ERR_ARG, "negative output capacity");
-    if (cap > 0 && !any) HJ_FAIL(HJ_ERR_ARG, "out_cap > 0 with every output null (the count form is out_cap == 0)");
-    if (cap == 0 && any) HJ_FAIL(HJ_ERR_ARG, "out_cap == 0 with an output (the count form takes none)");
+    HJ_TRY(star_check_cap(cap, out_key || out_cnt || vals));
     HJ_HIP(hipSetDevice(s->device));
     const StarGroups g = star_groups(s);
     hj::StarAggArgs a{};
-    for (int d = 0; d < ndims; ++d) {
-        a.d[d].t = table_dev(dims[d]);
-        a.d[d].key = skeys[d];
-        a.d[d].out = nullptr;
-        a.d[d].null_pay = null_pay[d];
-        a.d[d].kind = kinds[d];
-        a.d[d].lds_off = -1;
-        a.gshift[d] = gshift[d];
-        a.gbase[d] = gbase ? gbase[d] : 0;
+    star_fill_dims(a.d, ndims, dims, kinds, skeys, null_pay, nullptr);
+    for (int d = 0; d < HJ_STAR_MAX_DIMS; ++d) {
+        a.gshift[d] = d < ndims ? gshift[d] : -1;
+        a.gbase[d] = d < ndims && gbase ? gbase[d] : 0;
     }
-    for (int d = ndims; d < HJ_STAR_MAX_DIMS; ++d) a.gshift[d] = -1;
     a.sval = vals ? sval : nullptr;
     a.n = n;
     a.gt = g.t;
@@ -3316,12 +3318,10 @@ int hj_dev_star_aggregate_i32(hj_star *s, int ndims, hj_ctx *const dims[], const
                               const int64_t gbase[], const int32_t *sval, int64_t n, int64_t *out_key, int64_t *out_cnt,
                               int64_t *out_sum, int64_t *out_min, int64_t *out_max, int64_t out_cap, uint64_t *d_count,
                               void *stream) {
-    unsigned long long nulls[HJ_STAR_MAX_DIMS] = {};
-    if (null_row && ndims >= 1 && ndims <= HJ_STAR_MAX_DIMS)
-        for (int d = 0; d < ndims; ++d) nulls[d] = (unsigned long long)(long long)null_row[d];
-    return do_star_aggregate(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys, null_row ? nulls : nullptr,
-                             gshift, gbase, sval, n, out_key, out_cnt, out_sum, out_min, out_max, out_cap, d_count,
-                             stream);
+    unsigned long long w[HJ_STAR_MAX_DIMS] = {};
+    return do_star_aggregate(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys,
+                             widen_nulls(null_row, ndims, w), gshift, gbase, sval, n, out_key, out_cnt, out_sum,
+                             out_min, out_max, out_cap, d_count, stream);
 }
 
 int hj_dev_star_query_i64(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[],
@@ -3339,12 +3339,10 @@ int hj_dev_star_query_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int
                           const int64_t gbase[], const hj_star_fact *fact, const int32_t *sval, int64_t n,
                           int64_t *out_key, int64_t *out_cnt, int64_t *out_sum, int64_t *out_min, int64_t *out_max,
                           int64_t out_cap, uint64_t *d_count, void *stream) {
-    unsigned long long nulls[HJ_STAR_MAX_DIMS] = {};
-    if (null_row && ndims >= 1 && ndims <= HJ_STAR_MAX_DIMS)
-        for (int d = 0; d < ndims; ++d) nulls[d] = (unsigned long long)(long long)null_row[d];
-    return do_star_aggregate(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys, null_row ? nulls : nullptr,
-                             gshift, gbase, sval, n, out_key, out_cnt, out_sum, out_min, out_max, out_cap, d_count,
-                             stream, fact, true);
+    unsigned long long w[HJ_STAR_MAX_DIMS] = {};
+    return do_star_aggregate(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys,
+                             widen_nulls(null_row, ndims, w), gshift, gbase, sval, n, out_key, out_cnt, out_sum,
+                             out_min, out_max, out_cap, d_count, stream, fact, true);
 }
 
 int hj_star_reserve(hj_star *s, int64_t max_rows) {
@@ -3373,11 +3371,9 @@ int hj_dev_star_i64(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds
 int hj_dev_star_i32(hj_star *s, int ndims, hj_ctx *const dims[], const int kinds[], const int32_t *const skeys[],
                     const int32_t null_row[], int64_t n, int64_t row_base, int32_t *const out_pay[], int32_t *out_row,
                     int64_t out_cap, uint64_t *d_count, void *stream) {
-    unsigned long long nulls[HJ_STAR_MAX_DIMS] = {};
-    if (null_row && ndims >= 1 && ndims <= HJ_STAR_MAX_DIMS)
-        for (int d = 0; d < ndims; ++d) nulls[d] = (unsigned long long)(long long)null_row[d];
-    return do_star(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys, null_row ? nulls : nullptr, n, row_base,
-                   (void *const *)out_pay, out_row, out_cap, d_count, stream);
+    unsigned long long w[HJ_STAR_MAX_DIMS] = {};
+    return do_star(s, kNarrow, ndims, dims, kinds, (const void *const *)skeys, widen_nulls(null_row, ndims, w), n,
+                   row_base, (void *const *)out_pay, out_row, out_cap, d_count, stream);
 }
 
 }  // extern "C"

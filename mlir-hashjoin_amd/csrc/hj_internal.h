@@ -562,7 +562,7 @@ struct StarDim {
     void *out;                       // its payload column (int64 / int32; null: not asked for)
     unsigned long long null_pay;     // LEFT: the payload of a row without a partner
     int kind;
-    int lds_off;                     // set by launch_star: byte offset of the table's copy in dynamic LDS, < 0: global
+    int lds_off;                     // set by star_place: byte offset of the table's copy in dynamic LDS, < 0: global
 };
 struct StarArgs {                    // by value in the kernel arguments
     StarDim d[kStarMaxDims];
@@ -626,10 +626,11 @@ struct StarQueryArgs : StarAggArgs { // the FACT instantiations' arguments; the 
     StarFact f;
 };
 // Kernels only: the group table's fill, k_aggregate_init (it zeroes
-// out.counter), k_star_agg (n > 0) and k_emit_aggregate<kWide>.  Placement as
-// launch_star's over the tables the pass walks (INNER, ANTI, grouped LEFT), the
-// budget being min(kLdsPerCu, 160 KiB - the kernel's static LDS).  out.r is
-// the group key column; every out column is int64.  star_prepare covers it.
+// out.counter), k_star_agg (n > 0) and k_emit_aggregate<kWide>.  Placement by
+// star_place, as launch_star's, over the tables the pass walks (INNER, ANTI,
+// grouped LEFT), the budget being min(kLdsPerCu, 160 KiB - the kernel's static
+// LDS).  out.r is the group key column; every out column is int64.
+// star_prepare covers it.
 // fact (the star query): the pass is the FACT instantiation over *fact;
 // ndims == 0 is then legal: no dimension is walked, no table read, no LDS asked
 // for beside the static one.  Null: the star aggregate's own instantiation.

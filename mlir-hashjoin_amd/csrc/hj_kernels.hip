@@ -965,34 +965,88 @@ __device__ __forceinline__ unsigned star_walk(const StarDim &dm, unsigned rows,
     return star_walk_t<L, MIN, false>(dm, rows, K, side_n, side_min, unique, RP);
 }
 
+// The skeleton k_star and k_star_agg share.  The one difference between them:
+// k_star unrolls its dimension loops over ND and so holds walks, unique, side_n
+// and side_min in registers; k_star_agg walks a.order[] with a run-time index
+// under #pragma unroll 1 and therefore keeps them in LDS.
+//
+// The workgroup's copy of dm's table into s_tab at dm.lds_off, when the host planned one (it plans a copy only for
+// a dimension the launch walks).
+template <int L>
+__device__ __forceinline__ void star_copy_table(const StarDim &dm) {
+    extern __shared__ ulonglong2 s_tab[];
+    if (dm.lds_off >= 0) {
+        ulonglong2 *dst = s_tab + (dm.lds_off >> 4);
+        const unsigned long long n16 = (dm.t.mask + 1) * sizeof(typename Lay<L>::slot_t) / 16;
+        const ulonglong2 *g16 = (const ulonglong2 *)dm.t.slots;
+        for (unsigned long long j = threadIdx.x; j < n16; j += blockDim.x) dst[j] = g16[j];
+    }
+}
+// The workgroup's minimum over a side list of side_n payloads into *slot (LDS, preset to the largest payload).
+__device__ __forceinline__ void star_side_min(const TableDev &t, unsigned long long side_n, long long *slot) {
+    long long m = 0x7fffffffffffffffll;
+    for (unsigned long long j = threadIdx.x; j < side_n; j += blockDim.x) {
+        const long long p = (long long)t.side[j];
+        m = p < m ? p : m;
+    }
+    atomicMin(slot, m);
+}
+// Tile geometry: the row of thread tid's slot i in tile q, and its slots of tile q below n.
+__device__ __forceinline__ long long star_row(unsigned long long q, int i, int tid) {
+    return (long long)q * kProbeTile + (long long)i * kBlock + tid;
+}
+__device__ __forceinline__ unsigned star_valid(unsigned long long q, int tid, long long n) {
+    unsigned v = 0;
+#pragma unroll
+    for (int i = 0; i < kProbeItems; ++i) v |= star_row(q, i, tid) < n ? 1u << i : 0u;
+    return v;
+}
+// A column's keys of tile q for the slots in `rows`.  The column is a pointer (k_star_agg) or the dimension whose
+// key column it is (k_star), and the row comes from the kernel's row_of, a lambda over star_row that holds tid by
+// reference: dm->key and tid are then read per slot, inside the slot's branch, which is what the kernels' own
+// loops did.  Handed over by value they are read once ahead of the eight branches, the column's base address is
+// kept live across them, and the kernels' register counts and spills move (some occupancies with them).
+__device__ __forceinline__ const void *star_col(const void *col) { return col; }
+__device__ __forceinline__ const void *star_col(const StarDim *dm) { return dm->key; }
+template <int L, class Col, class Row>
+__device__ __forceinline__ void star_load_keys(Col col, unsigned long long q, unsigned rows,
+                                               star_key_t<L> (&K)[kProbeItems], const Row &row_of) {
+#pragma unroll
+    for (int i = 0; i < kProbeItems; ++i) K[i] = (rows >> i) & 1u ? star_key<L>(star_col(col), row_of(q, i)) : star_key_t<L>(0);
+}
+// A team = kBlock threads = one tile at a time; the teams of a workgroup share the table copies.  They take tiles
+// qb .. qb + teams - 1 together, qb from first() on in steps of step(), the grid's teams: every team of a workgroup
+// runs the same number of steps (its barriers), a team past the last tile an empty one.
+struct StarTeam {
+    int tid, team, teams;
+    __device__ __forceinline__ unsigned long long first() const { return (unsigned long long)blockIdx.x * teams; }
+    __device__ __forceinline__ unsigned long long step() const { return (unsigned long long)gridDim.x * teams; }
+};
+__device__ __forceinline__ StarTeam star_team() {
+    return {(int)(threadIdx.x & (kBlock - 1)), (int)(threadIdx.x / kBlock), (int)(blockDim.x / kBlock)};
+}
+
 template <int L, int ND, int MODE>
 __global__ __launch_bounds__(kBlock * kStarTeams) void k_star(StarArgs a) {
     using LY = Lay<L>;
-    using slot_t = typename LY::slot_t;
     using out_t = typename LY::out_t;
     constexpr int NW = kBlock / 64;
     constexpr long long kMaxPay = 0x7fffffffffffffffll;
     __shared__ long long s_side_min[kStarMaxDims];
     __shared__ unsigned s_cw[kProbeItems * NW];
-    extern __shared__ ulonglong2 s_tab[];
 
     // the dimensions this launch walks, their tables' copies and side lists
     bool walks[ND], unique[ND];
     unsigned long long side_n[ND];
     long long side_min[ND];
-    // a team = kBlock threads = one tile at a time; the teams of a workgroup share the table copies
-    const int tid = threadIdx.x & (kBlock - 1), team = threadIdx.x / kBlock, teams = blockDim.x / kBlock;
+    const StarTeam tm = star_team();
+    const int tid = tm.tid, team = tm.team;
     if (threadIdx.x < kStarMaxDims) s_side_min[threadIdx.x] = kMaxPay;
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
         const StarDim &dm = a.d[d];
         walks[d] = MODE == kStarDecide ? dm.kind != kStarLeft : dm.out != nullptr;
-        if (dm.lds_off >= 0) {   // (the host plans a copy only for a dimension this launch walks)
-            ulonglong2 *dst = s_tab + (dm.lds_off >> 4);
-            const unsigned long long n16 = (dm.t.mask + 1) * sizeof(slot_t) / 16;
-            const ulonglong2 *g16 = (const ulonglong2 *)dm.t.slots;
-            for (unsigned long long j = threadIdx.x; j < n16; j += blockDim.x) dst[j] = g16[j];
-        }
+        star_copy_table<L>(dm);
         unique[d] = true;
         side_n[d] = 0ull;
         if (walks[d]) {
@@ -1006,12 +1060,7 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star(StarArgs a) {
     for (int d = 0; d < ND; ++d) {
         side_min[d] = kMaxPay;
         if (MODE == kStarDecide || side_n[d] == 0ull) continue;   // (uniform)
-        long long m = kMaxPay;
-        for (unsigned long long j = threadIdx.x; j < side_n[d]; j += blockDim.x) {
-            const long long p = (long long)a.d[d].t.side[j];
-            m = p < m ? p : m;
-        }
-        atomicMin(&s_side_min[d], m);
+        star_side_min(a.d[d].t, side_n[d], &s_side_min[d]);
     }
     __syncthreads();
 #pragma unroll
@@ -1020,35 +1069,22 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star(StarArgs a) {
 
     const int lane = tid & 63, wv = tid >> 6;
     const unsigned long long nt = (unsigned long long)((a.n + kProbeTile - 1) / kProbeTile);
-    auto row_of = [&](unsigned long long q, int i) { return (long long)q * kProbeTile + (long long)i * kBlock + tid; };
-    auto valid_of = [&](unsigned long long q) {
-        unsigned v = 0;
-#pragma unroll
-        for (int i = 0; i < kProbeItems; ++i) v |= row_of(q, i) < a.n ? 1u << i : 0u;
-        return v;
-    };
-    // dimension d's keys of tile q for the rows in `rows`
-    auto load_keys = [&](int d, unsigned long long q, unsigned rows, star_key_t<L> (&K)[kProbeItems]) {
-#pragma unroll
-        for (int i = 0; i < kProbeItems; ++i) K[i] = (rows >> i) & 1u ? star_key<L>(a.d[d].key, row_of(q, i)) : star_key_t<L>(0);
-    };
+    auto row_of = [&](unsigned long long q, int i) { return star_row(q, i, tid); };
     // loaded ahead: the first walked dimension's keys of the next tile (kStarWrite: the next tile's result byte)
     [[maybe_unused]] star_key_t<L> KN[kProbeItems] = {};
     [[maybe_unused]] unsigned byte_n = 0;
-    // the workgroup's teams take tiles qb .. qb + teams - 1 together and step by the grid's teams: every team
-    // of a workgroup runs the same number of steps (the decision's barrier), a team past the last tile an empty one
-    const unsigned long long step = (unsigned long long)gridDim.x * teams, q0 = (unsigned long long)blockIdx.x * teams + team;
+    const unsigned long long step = tm.step(), q0 = tm.first() + team;
     if (q0 < nt) {
         if constexpr (MODE == kStarWrite) {
             byte_n = a.bitmap[q0 * kBlock + tid];
         } else {
 #pragma unroll
             for (int d = 0; d < ND; ++d)
-                if (d == a.first) load_keys(d, q0, valid_of(q0), KN);
+                if (d == a.first) star_load_keys<L>(&a.d[d], q0, star_valid(q0, tid, a.n), KN, row_of);
         }
     }
     [[maybe_unused]] unsigned par = 0;
-    for (unsigned long long qb = (unsigned long long)blockIdx.x * teams; qb < nt; qb += step) {
+    for (unsigned long long qb = tm.first(); qb < nt; qb += step) {
         const unsigned long long q = qb + team, qn = q + step;
         const bool active = q < nt;
         unsigned alive;
@@ -1057,13 +1093,13 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star(StarArgs a) {
             alive = active ? byte_n : 0u;
             if (qn < nt) byte_n = a.bitmap[qn * kBlock + tid];
         } else {
-            alive = active ? valid_of(q) : 0u;
+            alive = active ? star_valid(q, tid, a.n) : 0u;
 #pragma unroll
             for (int i = 0; i < kProbeItems; ++i) KF[i] = KN[i];
             if (qn < nt) {
 #pragma unroll
                 for (int d = 0; d < ND; ++d)
-                    if (d == a.first) load_keys(d, qn, valid_of(qn), KN);
+                    if (d == a.first) star_load_keys<L>(&a.d[d], qn, star_valid(qn, tid, a.n), KN, row_of);
             }
         }
         if constexpr (MODE == kStarDecide) {
@@ -1076,7 +1112,7 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star(StarArgs a) {
 #pragma unroll
                     for (int i = 0; i < kProbeItems; ++i) K[i] = KF[i];
                 } else {
-                    load_keys(d, q, alive, K);
+                    star_load_keys<L>(&a.d[d], q, alive, K, row_of);
                 }
                 const unsigned found = star_walk<L, false>(a.d[d], alive, K, side_n[d], kMaxPay, true, RP);
                 alive &= a.d[d].kind == kStarInner ? found : ~found;
@@ -1146,7 +1182,7 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star(StarArgs a) {
 #pragma unroll
                     for (int i = 0; i < kProbeItems; ++i) KA[d][i] = KF[i];
                 } else {
-                    load_keys(d, q, alive, KA[d]);
+                    star_load_keys<L>(&a.d[d], q, alive, KA[d], row_of);
                 }
             }
 #pragma unroll
@@ -2341,17 +2377,16 @@ __device__ __forceinline__ unsigned long long agg_slot_bounded(Slot64 *sl, const
 template <int L, int ND, bool FACT = false>
 __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(
     std::conditional_t<FACT, StarQueryArgs, StarAggArgs> a) {
-    using slot_t = typename Lay<L>::slot_t;
     constexpr long long kMaxPay = 0x7fffffffffffffffll;
     __shared__ AggTile<kWide> lt;
     __shared__ long long s_side_min[kStarMaxDims];
     __shared__ unsigned long long s_side_n[kStarMaxDims];
     __shared__ unsigned s_unique[kStarMaxDims];
     __shared__ unsigned s_stop;
-    extern __shared__ ulonglong2 s_tab[];
     static_assert(sizeof(AggTile<kWide>) + 128 <= kStarAggStaticLds, "the placement plan's bound on the static LDS");
 
-    const int tid = threadIdx.x & (kBlock - 1), team = threadIdx.x / kBlock, teams = blockDim.x / kBlock;
+    const StarTeam tm = star_team();
+    const int tid = tm.tid, team = tm.team;
     const AggWant w{a.acc.sum != nullptr, a.acc.mn != nullptr, a.acc.mx != nullptr};
     const bool vals = w.sum || w.mn || w.mx;   // (uniform) else sval is not read
     Slot64 *gsl = (Slot64 *)a.gt.slots;
@@ -2366,12 +2401,7 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(
         const StarDim &dm = a.d[d];
         const bool grouped = a.gshift[d] >= 0;
         if (dm.kind == kStarLeft && !grouped) continue;   // (uniform) never walked
-        if (dm.lds_off >= 0) {
-            ulonglong2 *dst = s_tab + (dm.lds_off >> 4);
-            const unsigned long long n16 = (dm.t.mask + 1) * sizeof(slot_t) / 16;
-            const ulonglong2 *g16 = (const ulonglong2 *)dm.t.slots;
-            for (unsigned long long j = threadIdx.x; j < n16; j += blockDim.x) dst[j] = g16[j];
-        }
+        star_copy_table<L>(dm);
         const unsigned long long side_n = L == kWide ? dm.t.meta[0] : 0ull;
         if (threadIdx.x == 0) {
             s_side_n[d] = side_n;
@@ -2379,27 +2409,12 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(
                 s_unique[d] = __hip_atomic_load(&dm.t.meta[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull ? 1u : 0u;
         }
         if (!grouped || side_n == 0ull) continue;   // (uniform)
-        long long m = kMaxPay;
-        for (unsigned long long j = threadIdx.x; j < side_n; j += blockDim.x) {
-            const long long p = (long long)dm.t.side[j];
-            m = p < m ? p : m;
-        }
-        atomicMin(&s_side_min[d], m);
+        star_side_min(dm.t, side_n, &s_side_min[d]);
     }
     __syncthreads();
 
     const unsigned long long nt = (unsigned long long)((a.n + kProbeTile - 1) / kProbeTile);
-    auto row_of = [&](unsigned long long q, int i) { return (long long)q * kProbeTile + (long long)i * kBlock + tid; };
-    auto valid_of = [&](unsigned long long q) {
-        unsigned v = 0;
-#pragma unroll
-        for (int i = 0; i < kProbeItems; ++i) v |= row_of(q, i) < a.n ? 1u << i : 0u;
-        return v;
-    };
-    auto load_keys = [&](const void *col, unsigned long long q, unsigned rows, star_key_t<L> (&K)[kProbeItems]) {
-#pragma unroll
-        for (int i = 0; i < kProbeItems; ++i) K[i] = (rows >> i) & 1u ? star_key<L>(col, row_of(q, i)) : star_key_t<L>(0);
-    };
+    auto row_of = [&](unsigned long long q, int i) { return star_row(q, i, tid); };
     // loaded ahead: the first walked dimension's keys of the next tile (FACT with a predicate: its first column)
     bool pred_first = false;   // (uniform)
     const void *first_col = a.nwalk > 0 ? a.d[a.order[0]].key : nullptr;
@@ -2408,18 +2423,18 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(
         if (pred_first) first_col = a.f.pcol[0];
     }
     star_key_t<L> KN[kProbeItems] = {};
-    const unsigned long long step = (unsigned long long)gridDim.x * teams, q0 = (unsigned long long)blockIdx.x * teams + team;
-    if (q0 < nt && first_col) load_keys(first_col, q0, valid_of(q0), KN);
-    for (unsigned long long qb = (unsigned long long)blockIdx.x * teams; qb < nt; qb += step) {
+    const unsigned long long step = tm.step(), q0 = tm.first() + team;
+    if (q0 < nt && first_col) star_load_keys<L>(first_col, q0, star_valid(q0, tid, a.n), KN, row_of);
+    for (unsigned long long qb = tm.first(); qb < nt; qb += step) {
         const unsigned long long q = qb + team, qn = q + step;
         if (threadIdx.x == 0)
             s_stop = (unsigned)(__hip_atomic_load(a.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 63);
         agg_tile_clear(lt, w, (int)threadIdx.x, (int)blockDim.x);
-        unsigned alive = q < nt ? valid_of(q) : 0u;
+        unsigned alive = q < nt ? star_valid(q, tid, a.n) : 0u;
         star_key_t<L> KF[kProbeItems];
 #pragma unroll
         for (int i = 0; i < kProbeItems; ++i) KF[i] = KN[i];
-        if (qn < nt && first_col) load_keys(first_col, qn, valid_of(qn), KN);
+        if (qn < nt && first_col) star_load_keys<L>(first_col, qn, star_valid(qn, tid, a.n), KN, row_of);
         unsigned long long G[kProbeItems] = {};
         if constexpr (FACT) {
 #pragma unroll 1
@@ -2429,7 +2444,7 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(
 #pragma unroll
                     for (int i = 0; i < kProbeItems; ++i) K[i] = KF[i];
                 } else {
-                    load_keys(a.f.pcol[p], q, alive, K);
+                    star_load_keys<L>(a.f.pcol[p], q, alive, K, row_of);
                 }
                 const long long lo = a.f.plo[p], hi = a.f.phi[p];
                 const bool outside = a.f.pkind[p] != 0;   // (uniform)
@@ -2453,7 +2468,7 @@ __global__ __launch_bounds__(kBlock * kStarTeams) void k_star_agg(
 #pragma unroll
                 for (int i = 0; i < kProbeItems; ++i) K[i] = KF[i];
             } else {
-                load_keys(dm.key, q, alive, K);
+                star_load_keys<L>(dm.key, q, alive, K, row_of);
             }
             const unsigned found = star_walk<L, true>(dm, alive, K, s_side_n[d], s_side_min[d], gs < 0 || s_unique[d] != 0u, RP);
             if (dm.kind == kStarInner) alive &= found;
@@ -3080,59 +3095,104 @@ hipError_t launch_probe_lookup(const TableDev &t, int layout, const SrcDev &src,
 // ---------------------------------------------------------------- star probe
 namespace {
 static_assert(kFilterTile == kProbeTile && kFilterBlock == kBlock, "the star probe shares the key filter's workspace shape");
-typedef void (*star_kernel_t)(StarArgs);
-template <int L, int MODE>
-star_kernel_t star_kernel_nd(int ndims) {
-    switch (ndims) {
-    case 1: return k_star<L, 1, MODE>;
-    case 2: return k_star<L, 2, MODE>;
-    case 3: return k_star<L, 3, MODE>;
-    case 4: return k_star<L, 4, MODE>;
-    default: return nullptr;
-    }
+// Every star kernel there is: f(layout, ndims, variant, kernel) for each (layout, ND, variant), the first three
+// as int_c.  The variants are k_star's modes and, behind them, k_star_agg without and with FACT.  star_prepare and
+// star_launch both go through here, so an instantiation is named once and none can miss its attribute.
+enum : int { kStarAgg = 3, kStarQuery = 4 };
+template <int V>
+using star_args_t =
+    std::conditional_t<V == kStarQuery, StarQueryArgs, std::conditional_t<V == kStarAgg, StarAggArgs, StarArgs>>;
+template <int... V, class F>
+void for_ints(F &&f) {
+    (f(int_c<V>{}), ...);
 }
-star_kernel_t star_kernel(int layout, int ndims, int mode) {
-    if (layout != kWide && layout != kNarrow) return nullptr;
-    const bool w = layout == kWide;
-    switch (mode) {
-    case kStarDecide: return w ? star_kernel_nd<kWide, kStarDecide>(ndims) : star_kernel_nd<kNarrow, kStarDecide>(ndims);
-    case kStarWrite: return w ? star_kernel_nd<kWide, kStarWrite>(ndims) : star_kernel_nd<kNarrow, kStarWrite>(ndims);
-    case kStarAll: return w ? star_kernel_nd<kWide, kStarAll>(ndims) : star_kernel_nd<kNarrow, kStarAll>(ndims);
-    default: return nullptr;
-    }
+template <class F>
+void for_each_star_kernel(F &&f) {
+    for_ints<kWide, kNarrow>([&](auto l) {
+        for_ints<1, 2, 3, 4>([&](auto nd) {
+            for_ints<kStarDecide, kStarWrite, kStarAll, kStarAgg, kStarQuery>([&](auto v) {
+                constexpr int L = decltype(l)::value, ND = decltype(nd)::value, V = decltype(v)::value;
+                static_assert(ND <= kStarMaxDims);
+                if constexpr (V <= kStarAll) f(l, nd, v, k_star<L, ND, V>);
+                else f(l, nd, v, k_star_agg<L, ND, V == kStarQuery>);
+            });
+        });
+    });
 }
-template <bool FACT>
-using star_agg_kernel_t = void (*)(std::conditional_t<FACT, StarQueryArgs, StarAggArgs>);
-template <bool FACT>
-star_agg_kernel_t<FACT> star_agg_kernel(int layout, int ndims) {
-    if (layout != kWide && layout != kNarrow) return nullptr;
-    const bool w = layout == kWide;
-    switch (ndims) {
-    case 1: return w ? k_star_agg<kWide, 1, FACT> : k_star_agg<kNarrow, 1, FACT>;
-    case 2: return w ? k_star_agg<kWide, 2, FACT> : k_star_agg<kNarrow, 2, FACT>;
-    case 3: return w ? k_star_agg<kWide, 3, FACT> : k_star_agg<kNarrow, 3, FACT>;
-    case 4: return w ? k_star_agg<kWide, 4, FACT> : k_star_agg<kNarrow, 4, FACT>;
-    default: return nullptr;
+// (the launchers have checked layout and ndims: exactly one instantiation matches)
+template <int V>
+void star_launch(int layout, int ndims, unsigned grid, unsigned threads, size_t lds, hipStream_t st,
+                 const star_args_t<V> &a) {
+    for_each_star_kernel([&](auto l, auto nd, auto v, auto k) {
+        if constexpr (decltype(v)::value == V)
+            if (l == layout && nd == ndims) hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, st, a);
+    });
+}
+
+// The placement plan of a persistent launch that walks dimensions walk[0 .. nwalk): their tables ascending by
+// size (ties in walk order) get a copy in dynamic LDS while each is an LDS table's size at most and they fit the
+// budget together.  Assigns lds_off in dimension order, -1 where there is no copy.
+struct StarPlacement {
+    int lds_dims;
+    size_t lds_bytes;
+};
+StarPlacement star_place(int layout, int ndims, StarDim (&dims)[kStarMaxDims], const int *walk, int nwalk,
+                         size_t budget) {
+    const size_t sb = layout == kWide ? 16 : 8;
+    size_t bytes[kStarMaxDims];
+    int order[kStarMaxDims];
+    for (int j = 0; j < nwalk; ++j) {
+        const int d = walk[j];
+        bytes[d] = (size_t)(dims[d].t.mask + 1) * sb;
+        int k = j;
+        for (; k > 0 && bytes[order[k - 1]] > bytes[d]; --k) order[k] = order[k - 1];
+        order[k] = d;
     }
+    StarPlacement p{0, 0};
+    for (int j = 0; j < nwalk; ++j) {
+        const size_t b = bytes[order[j]];
+        if (b > (size_t)kLdsTableBytes || p.lds_bytes + b > budget) break;
+        p.lds_dims |= 1 << order[j];
+        p.lds_bytes += b;
+    }
+    size_t off = 0;
+    for (int d = 0; d < kStarMaxDims; ++d) {
+        dims[d].lds_off = -1;
+        if (d < ndims && ((p.lds_dims >> d) & 1)) {
+            dims[d].lds_off = (int)off;
+            off += bytes[d];
+        }
+    }
+    return p;
+}
+
+// The persistent grid over `tiles` tiles.  With table copies: workgroups of kStarTeams teams, per CU as many as
+// lds_cu / (lds_bytes + static_lds) and the wave slots (8 teams) admit.  Without: one team each, plain_per_cu per
+// CU, or one workgroup per tile when that is 0.
+struct StarGrid {
+    unsigned grid, teams;
+};
+StarGrid star_grid(unsigned tiles, size_t lds_bytes, size_t lds_cu, size_t static_lds, unsigned plain_per_cu) {
+    unsigned teams = 1, per_cu = plain_per_cu;
+    if (lds_bytes) {
+        teams = kStarTeams;   // (4 workgroups x 2 teams x 4 waves are a CU's 32 wave slots)
+        per_cu = (unsigned)(lds_cu / (lds_bytes + static_lds));
+        if (per_cu * teams > 8) per_cu = 8 / teams;
+        if (per_cu < 1) per_cu = 1;
+    }
+    if (per_cu == 0) return {tiles, teams};
+    const unsigned most = (unsigned)cu_count() * per_cu, want = (tiles + teams - 1) / teams;
+    return {most < want ? most : want, teams};
 }
 }  // namespace
 
 hipError_t star_prepare() {
-    for (int layout : {(int)kWide, (int)kNarrow})
-        for (int nd = 1; nd <= kStarMaxDims; ++nd)
-            for (int mode : {(int)kStarDecide, (int)kStarWrite, (int)kStarAll}) {
-                const hipError_t e = hipFuncSetAttribute((const void *)star_kernel(layout, nd, mode),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
-                if (e != hipSuccess) return e;
-            }
-    for (int layout : {(int)kWide, (int)kNarrow})
-        for (int nd = 1; nd <= kStarMaxDims; ++nd)
-            for (const void *k : {(const void *)star_agg_kernel<false>(layout, nd),
-                                  (const void *)star_agg_kernel<true>(layout, nd)}) {
-                const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
-                if (e != hipSuccess) return e;
-            }
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    for_each_star_kernel([&](auto, auto, auto, auto k) {
+        if (e != hipSuccess) return;
+        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsPerCu);
+    });
+    return e;
 }
 
 hipError_t launch_star_aggregate(int layout, int ndims, StarAggArgs a, const GroupOut &out, StarPlan *plan,
@@ -3159,56 +3219,21 @@ hipError_t launch_star_aggregate(int layout, int ndims, StarAggArgs a, const Gro
             if (a.d[d].kind != kStarLeft) a.order[a.nwalk++] = d;
         for (int d = 0; d < ndims; ++d)
             if (a.d[d].kind == kStarLeft && a.gshift[d] >= 0) a.order[a.nwalk++] = d;
-        // placement: launch_star's rule over the walked tables, the budget being what the CU has left beside the
-        // kernel's static LDS and no more than kLdsPerCu
-        const size_t sb = layout == kWide ? 16 : 8;
+        // placement: the budget is what the CU has left beside the kernel's static LDS and no more than kLdsPerCu
         const size_t budget = (size_t)(kLdsCu - kStarAggStaticLds < kLdsPerCu ? kLdsCu - kStarAggStaticLds : kLdsPerCu);
-        size_t bytes[kStarMaxDims];
-        int order[kStarMaxDims];
-        for (int j = 0; j < a.nwalk; ++j) {
-            const int d = a.order[j];
-            bytes[d] = (size_t)(a.d[d].t.mask + 1) * sb;
-            int k = j;
-            for (; k > 0 && bytes[order[k - 1]] > bytes[d]; --k) order[k] = order[k - 1];
-            order[k] = d;
-        }
-        int lds_dims = 0;
-        size_t lds_bytes = 0;
-        for (int d = 0; d < kStarMaxDims; ++d) a.d[d].lds_off = -1;
-        for (int j = 0; j < a.nwalk; ++j) {
-            const size_t b = bytes[order[j]];
-            if (b > (size_t)kLdsTableBytes || lds_bytes + b > budget) break;
-            lds_dims |= 1 << order[j];
-            lds_bytes += b;
-        }
-        size_t off = 0;
-        for (int d = 0; d < ndims; ++d)
-            if ((lds_dims >> d) & 1) {
-                a.d[d].lds_off = (int)off;
-                off += bytes[d];
-            }
-        // persistent workgroups: with table copies kStarTeams teams each, as many as the LDS lets a CU hold;
-        // without, one team each and eight per CU (the collapse table alone, as k_aggregate's)
+        const StarPlacement p = star_place(layout, ndims, a.d, a.order, a.nwalk, budget);
+        // without copies eight workgroups per CU (the collapse table alone, as k_aggregate's)
         const unsigned tiles = grid_for(a.n, kProbeTile);
-        unsigned teams = 1, per_cu = 8;
-        if (lds_bytes) {
-            teams = kStarTeams;
-            per_cu = (unsigned)((size_t)kLdsCu / (lds_bytes + (size_t)kStarAggStaticLds));
-            if (per_cu * teams > 8) per_cu = 8 / teams;
-            if (per_cu < 1) per_cu = 1;
-        }
-        const unsigned mostw = (unsigned)cu_count() * per_cu, want = (tiles + teams - 1) / teams;
-        const unsigned grid = mostw < want ? mostw : want;
+        const StarGrid g = star_grid(tiles, p.lds_bytes, (size_t)kLdsCu, (size_t)kStarAggStaticLds, 8);
         if (fact) {
             StarQueryArgs qa{};
             static_cast<StarAggArgs &>(qa) = a;
             qa.f = *fact;
-            hipLaunchKernelGGL(star_agg_kernel<true>(layout, ndims ? ndims : 1), dim3(grid), dim3(kBlock * teams),
-                               lds_bytes, st, qa);
+            star_launch<kStarQuery>(layout, ndims ? ndims : 1, g.grid, kBlock * g.teams, p.lds_bytes, st, qa);
         } else {
-            hipLaunchKernelGGL(star_agg_kernel<false>(layout, ndims), dim3(grid), dim3(kBlock * teams), lds_bytes, st, a);
+            star_launch<kStarAgg>(layout, ndims, g.grid, kBlock * g.teams, p.lds_bytes, st, a);
         }
-        *plan = StarPlan{4, grid, (long long)tiles, lds_dims, (long long)lds_bytes};
+        *plan = StarPlan{4, g.grid, (long long)tiles, p.lds_dims, (long long)p.lds_bytes};
     }
     const unsigned tl = grid_for((long long)cap, kProbeTile), g = tl < most ? tl : most;
     hipLaunchKernelGGL(k_emit_aggregate<kWide>, dim3(g), dim3(kBlock), 0, st, a.gt, a.acc, out);
@@ -3229,69 +3254,41 @@ hipError_t launch_star(int layout, int ndims, StarArgs a, const FilterWork &ws, 
         return hipGetLastError();
     }
     // placement: the tables the probe launch walks (the decision's INNER and
-    // ANTI dimensions; keep-all: the ones with a payload column), ascending,
-    // while they fit
-    const size_t sb = layout == kWide ? 16 : 8;
-    size_t bytes[kStarMaxDims];
-    int order[kStarMaxDims], no = 0;
-    for (int d = 0; d < ndims; ++d) {
-        bytes[d] = (size_t)(a.d[d].t.mask + 1) * sb;
-        if (drops ? a.d[d].kind == kStarLeft : !a.d[d].out) continue;   // the probe launch does not walk it
-        int j = no++;
-        for (; j > 0 && bytes[order[j - 1]] > bytes[d]; --j) order[j] = order[j - 1];
-        order[j] = d;
-    }
-    int lds_dims = 0;
-    size_t lds_bytes = 0;
-    for (int j = 0; j < no; ++j) {
-        const size_t b = bytes[order[j]];
-        if (b > (size_t)kLdsTableBytes || lds_bytes + b > (size_t)kLdsPerCu) break;
-        lds_dims |= 1 << order[j];
-        lds_bytes += b;
-    }
+    // ANTI dimensions; keep-all: the ones with a payload column)
+    int walk[kStarMaxDims], nwalk = 0;
+    for (int d = 0; d < ndims; ++d)
+        if (drops ? a.d[d].kind != kStarLeft : a.d[d].out != nullptr) walk[nwalk++] = d;
+    const StarPlacement p = star_place(layout, ndims, a.d, walk, nwalk, (size_t)kLdsPerCu);
     // the probe launch: as many workgroups of kStarTeams teams as its table
     // copies let a CU hold stride over the tiles; without a copy, one workgroup
     // of one team per tile.  The write
     // launch walks the survivors alone: no copies (a copy per workgroup costs
     // what the walks of a few rows do not give back) and one workgroup per tile.
     const unsigned tiles = grid_for(a.n, kProbeTile);
-    unsigned grid = tiles, teams = 1;
-    if (lds_bytes) {
-        unsigned per_cu = (unsigned)(kLdsPerCu / lds_bytes);
-        per_cu = per_cu > 8 ? 8 : per_cu;
-        teams = kStarTeams;   // (per_cu <= 8 / teams would do for the wave slots: 8 x 2 x 4 waves are a CU's 32)
-        if (per_cu * teams > 8) per_cu = 8 / teams;
-        const unsigned most = (unsigned)cu_count() * per_cu, want = (tiles + teams - 1) / teams;
-        grid = most < want ? most : want;
-    }
-    *plan = StarPlan{0, grid, (long long)tiles, lds_dims, (long long)lds_bytes};
-    auto launch = [&](int mode) {
+    const StarGrid g = star_grid(tiles, p.lds_bytes, (size_t)kLdsPerCu, 0, 0);
+    *plan = StarPlan{0, g.grid, (long long)tiles, p.lds_dims, (long long)p.lds_bytes};
+    auto launch = [&](auto m) {
+        constexpr int mode = decltype(m)::value;
+        constexpr bool write = mode == kStarWrite;
         StarArgs b = a;
-        size_t off = 0;
         b.first = -1;
         for (int d = 0; d < ndims; ++d) {
             const bool walks = mode == kStarDecide ? b.d[d].kind != kStarLeft : b.d[d].out != nullptr;
-            b.d[d].lds_off = -1;
-            if (!walks) continue;
-            if (b.first < 0) b.first = d;
-            if (mode != kStarWrite && ((lds_dims >> d) & 1)) {
-                b.d[d].lds_off = (int)off;
-                off += bytes[d];
-            }
+            if (write) b.d[d].lds_off = -1;
+            if (walks && b.first < 0) b.first = d;
         }
-        const bool write = mode == kStarWrite;
-        hipLaunchKernelGGL(star_kernel(layout, ndims, mode), dim3(write ? tiles : grid),
-                           dim3(kBlock * (write ? 1u : teams)), off, st, b);
+        star_launch<mode>(layout, ndims, write ? tiles : g.grid, kBlock * (write ? 1u : g.teams),
+                          write ? 0 : p.lds_bytes, st, b);
         ++plan->launches;
         return hipGetLastError();
     };
-    if (!drops) return launch(kStarAll);
-    hipError_t e = launch(kStarDecide);
+    if (!drops) return launch(int_c<kStarAll>{});
+    hipError_t e = launch(int_c<kStarDecide>{});
     if (e != hipSuccess) return e;
     e = exclusive_scan_u64(ws.tiles, (unsigned long long)tiles + 1, ws.sums, st);
     if (e != hipSuccess) return e;
     plan->launches += exclusive_scan_launches((unsigned long long)tiles + 1);
-    if (a.cap > 0) return launch(kStarWrite);
+    if (a.cap > 0) return launch(int_c<kStarWrite>{});
     hipLaunchKernelGGL(k_star_total, dim3(1), dim3(64), 0, st, (const unsigned long long *)(ws.tiles + tiles), 0ull,
                        a.count);
     ++plan->launches;

@@ -16,6 +16,7 @@ reference's i32 keys with i32 row ids.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -419,6 +420,57 @@ class StarProbe:
             raise ValueError("the dimensions' key columns must share a dtype and a length")
         return hjs, keys, kinds, nulls
 
+    @staticmethod
+    def _arrays(hjs, keys, kinds, nulls, wide):
+        """The ctypes arrays (contexts, kinds, key columns, nulls) of _dims' lists; None each without a dimension."""
+        nd = len(hjs)
+        if not nd:
+            return None, None, None, None
+        return ((C.c_void_p * nd)(*[h._ctx for h in hjs]), (C.c_int * nd)(*kinds),
+                (C.c_void_p * nd)(*[k.data_ptr() for k in keys]), ((C.c_int64 if wide else C.c_int32) * nd)(*nulls))
+
+    def _grouped(self, nd, group, base, inputs, outs, what):
+        """A grouped call's group / base as ctypes arrays (None each without a dimension) and its outputs' common
+        length, all checked; `what` names the call in the messages."""
+        group = [-1] * nd if group is None else [-1 if g is None else int(g) for g in group]
+        base = [0] * nd if base is None else [int(b) for b in base]
+        if len(group) != nd or len(base) != nd:
+            raise ValueError("group and base need one entry per dimension")
+        outs = [o for o in outs if o is not None]
+        _need_cuda(*inputs, *outs)
+        if any(o.dtype != torch.int64 or o.dim() != 1 for o in outs):
+            raise ValueError(f"the {what}'s output columns are int64")
+        cap = outs[0].shape[0] if outs else 0
+        if any(o.shape[0] != cap for o in outs):
+            raise ValueError("output columns differ in length")
+        return (C.c_int * nd)(*group) if nd else None, (C.c_int64 * nd)(*base) if nd else None, cap
+
+    def _collect(self, into, aggs, max_groups, capacity, what):
+        """{"key": tensor, agg: tensor, ...} trimmed to G from into(out_key, out_cnt, out_sum, out_min, out_max):
+        into() counts the groups first unless a capacity is given; one below G is grown to G and the call repeated."""
+        if any(a not in GROUP_AGGS for a in aggs):
+            raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
+        if max_groups is not None:
+            self.reserve_groups(max_groups)
+
+        def groups(cnt):
+            g = int(cnt.item())
+            if g < 0:   # bit 63 (hj.h)
+                raise HJError(f"{what}: more groups than the group table of {self.group_capacity} slots "
+                              "admits (reserve_groups)")
+            return g
+
+        cap = groups(into()) if capacity is None else int(capacity)
+        for _ in range(2):
+            cap = max(1, cap)
+            out_key = torch.empty(cap, dtype=torch.int64, device=self.device)
+            cols = {a: torch.empty(cap, dtype=torch.int64, device=self.device) for a in aggs}
+            g = groups(into(out_key, cols.get("count"), cols.get("sum"), cols.get("min"), cols.get("max")))
+            if g <= cap:
+                return {"key": out_key[:g], **{a: c[:g] for a, c in cols.items()}}
+            cap = g
+        raise RuntimeError(f"{what} output did not fit after resizing")
+
     def probe_into(self, dims, out_pay=None, out_row=None, count=None, row_base=0, stream=None):
         """The raw call: writes min(M, cap) qualifying rows, in input order,
         into the outputs given -- out_pay a list with one column or None per
@@ -438,17 +490,13 @@ class StarProbe:
         if any(o.shape[0] != cap for o in outs):
             raise ValueError("output columns differ in length")
         count = self._count if count is None else count
-        a_ctx = (C.c_void_p * nd)(*[h._ctx for h in hjs])
-        a_kind = (C.c_int * nd)(*kinds)
-        a_key = (C.c_void_p * nd)(*[k.data_ptr() for k in keys])
+        a_ctx, a_kind, a_key, a_null = self._arrays(hjs, keys, kinds, nulls, dt == torch.int64)
         a_out = (C.c_void_p * nd)(*[None if o is None else o.data_ptr() for o in out_pay])
         st = _stream(self.device, stream)
         if dt == torch.int64:
-            a_null = (C.c_int64 * nd)(*nulls)
             check(lib.hj_dev_star_i64(self._s, nd, a_ctx, a_kind, a_key, a_null, n, a_out, _ptr(out_row), cap,
                                       _ptr(count), st), "hj_dev_star_i64")
         else:
-            a_null = (C.c_int32 * nd)(*nulls)
             check(lib.hj_dev_star_i32(self._s, nd, a_ctx, a_kind, a_key, a_null, n, int(row_base), a_out,
                                       _ptr(out_row), cap, _ptr(count), st), "hj_dev_star_i32")
         return count
@@ -499,27 +547,13 @@ class StarProbe:
         receives G; negative: the group table overflowed (bit 63).  Returns count."""
         hjs, keys, kinds, nulls = self._dims(dims)
         nd, dt, n = len(dims), keys[0].dtype, keys[0].numel()
-        group = [-1] * nd if group is None else [-1 if g is None else int(g) for g in group]
-        base = [0] * nd if base is None else [int(b) for b in base]
-        if len(group) != nd or len(base) != nd:
-            raise ValueError("group and base need one entry per dimension")
-        outs = [o for o in (out_key, out_cnt, out_sum, out_min, out_max) if o is not None]
-        _need_cuda(val, *outs)
-        if any(o.dtype != torch.int64 or o.dim() != 1 for o in outs):
-            raise ValueError("the star aggregate's output columns are int64")
-        cap = outs[0].shape[0] if outs else 0
-        if any(o.shape[0] != cap for o in outs):
-            raise ValueError("output columns differ in length")
+        a_shift, a_base, cap = self._grouped(nd, group, base, [val], (out_key, out_cnt, out_sum, out_min, out_max),
+                                             "star aggregate")
         if val is not None and (val.dtype != dt or val.dim() != 1 or val.numel() != n):
             raise ValueError("the value column takes the key columns' dtype and length")
         count = self._count if count is None else count
-        a_ctx = (C.c_void_p * nd)(*[h._ctx for h in hjs])
-        a_kind = (C.c_int * nd)(*kinds)
-        a_key = (C.c_void_p * nd)(*[k.data_ptr() for k in keys])
-        a_shift = (C.c_int * nd)(*group)
-        a_base = (C.c_int64 * nd)(*base)
         wide = dt == torch.int64
-        a_null = ((C.c_int64 if wide else C.c_int32) * nd)(*nulls)
+        a_ctx, a_kind, a_key, a_null = self._arrays(hjs, keys, kinds, nulls, wide)
         f = lib.hj_dev_star_aggregate_i64 if wide else lib.hj_dev_star_aggregate_i32
         check(f(self._s, nd, a_ctx, a_kind, a_key, a_null, a_shift, a_base, _ptr(val), n, _ptr(out_key), _ptr(out_cnt),
                 _ptr(out_sum), _ptr(out_min), _ptr(out_max), cap, _ptr(count), _stream(self.device, stream)),
@@ -534,30 +568,10 @@ class StarProbe:
         first and allocates exactly; a capacity below G is grown to G and the
         call repeated.  Raises HJError when the group table overflowed.
         Synchronises to read G."""
-        if any(a not in GROUP_AGGS for a in aggs):
-            raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
-        if max_groups is not None:
-            self.reserve_groups(max_groups)
+        def into(*o):   # (the count call passes no value column)
+            return self.aggregate_into(dims, val if o else None, *o, group=group, base=base, stream=stream)
 
-        def groups(cnt):
-            g = int(cnt.item())
-            if g < 0:   # bit 63 (hj.h)
-                raise HJError(f"star aggregate: more groups than the group table of {self.group_capacity} slots "
-                              "admits (reserve_groups)")
-            return g
-
-        cap = groups(self.aggregate_into(dims, group=group, base=base, stream=stream)) if capacity is None \
-            else int(capacity)
-        for _ in range(2):
-            cap = max(1, cap)
-            out_key = torch.empty(cap, dtype=torch.int64, device=self.device)
-            cols = {a: torch.empty(cap, dtype=torch.int64, device=self.device) for a in aggs}
-            g = groups(self.aggregate_into(dims, val, out_key, cols.get("count"), cols.get("sum"), cols.get("min"),
-                                           cols.get("max"), group=group, base=base, stream=stream))
-            if g <= cap:
-                return {"key": out_key[:g], **{a: c[:g] for a, c in cols.items()}}
-            cap = g
-        raise RuntimeError("star aggregate output did not fit after resizing")
+        return self._collect(into, aggs, max_groups, capacity, "star aggregate")
 
     # ---- star query (hj.h "Star query"): the star aggregate with fact-side predicates, a two-column value
     # expression and fact-side group fields in the same pass
@@ -590,17 +604,8 @@ class StarProbe:
             if not isinstance(c, torch.Tensor) or c.dim() != 1 or c.dtype != dt or c.numel() != n or \
                     dt not in (torch.int64, torch.int32):
                 raise ValueError("the fact columns are 1-D int64 / int32 tensors of the key columns' dtype and length")
-        group = [-1] * nd if group is None else [-1 if g is None else int(g) for g in group]
-        base = [0] * nd if base is None else [int(b) for b in base]
-        if len(group) != nd or len(base) != nd:
-            raise ValueError("group and base need one entry per dimension")
-        outs = [o for o in (out_key, out_cnt, out_sum, out_min, out_max) if o is not None]
-        _need_cuda(*shape, *outs)
-        if any(o.dtype != torch.int64 or o.dim() != 1 for o in outs):
-            raise ValueError("the star query's output columns are int64")
-        cap = outs[0].shape[0] if outs else 0
-        if any(o.shape[0] != cap for o in outs):
-            raise ValueError("output columns differ in length")
+        a_shift, a_base, cap = self._grouped(nd, group, base, shape, (out_key, out_cnt, out_sum, out_min, out_max),
+                                             "star query")
         fact = StarFact()
         fact.npreds = len(where)
         for p, w in enumerate(where):
@@ -613,12 +618,7 @@ class StarProbe:
             fact.fcol[f], fact.fshift[f], fact.fbase[f] = col.data_ptr(), int(shift), int(fbase)
         count = self._count if count is None else count
         wide = dt == torch.int64
-        a_ctx = (C.c_void_p * nd)(*[h._ctx for h in hjs]) if nd else None
-        a_kind = (C.c_int * nd)(*kinds) if nd else None
-        a_key = (C.c_void_p * nd)(*[k.data_ptr() for k in keys]) if nd else None
-        a_shift = (C.c_int * nd)(*group) if nd else None
-        a_base = (C.c_int64 * nd)(*base) if nd else None
-        a_null = ((C.c_int64 if wide else C.c_int32) * nd)(*nulls) if nd else None
+        a_ctx, a_kind, a_key, a_null = self._arrays(hjs, keys, kinds, nulls, wide)
         f = lib.hj_dev_star_query_i64 if wide else lib.hj_dev_star_query_i32
         check(f(self._s, nd, a_ctx, a_kind, a_key, a_null, a_shift, a_base, C.byref(fact), _ptr(val), n, _ptr(out_key),
                 _ptr(out_cnt), _ptr(out_sum), _ptr(out_min), _ptr(out_max), cap, _ptr(count),
@@ -630,30 +630,8 @@ class StarProbe:
         """aggregate's dict over query_into: {"key": tensor, agg: tensor, ...}
         trimmed to G.  Raises HJError when the group table overflowed.
         Synchronises to read G."""
-        if any(a not in GROUP_AGGS for a in aggs):
-            raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
-        if max_groups is not None:
-            self.reserve_groups(max_groups)
         kw = dict(where=where, expr=expr, fact_group=fact_group, group=group, base=base, stream=stream)
-
-        def groups(cnt):
-            g = int(cnt.item())
-            if g < 0:   # bit 63 (hj.h)
-                raise HJError(f"star query: more groups than the group table of {self.group_capacity} slots "
-                              "admits (reserve_groups)")
-            return g
-
-        cap = groups(self.query_into(dims, val, **kw)) if capacity is None else int(capacity)
-        for _ in range(2):
-            cap = max(1, cap)
-            out_key = torch.empty(cap, dtype=torch.int64, device=self.device)
-            cols = {a: torch.empty(cap, dtype=torch.int64, device=self.device) for a in aggs}
-            g = groups(self.query_into(dims, val, out_key, cols.get("count"), cols.get("sum"), cols.get("min"),
-                                       cols.get("max"), **kw))
-            if g <= cap:
-                return {"key": out_key[:g], **{a: c[:g] for a, c in cols.items()}}
-            cap = g
-        raise RuntimeError("star query output did not fit after resizing")
+        return self._collect(lambda *o: self.query_into(dims, val, *o, **kw), aggs, max_groups, capacity, "star query")
 
 
 class HashJoin:
@@ -1755,6 +1733,36 @@ class HashJoin:
 
 
 # ------------------------------------------------------------------ datagen
+@contextlib.contextmanager
+def _star_built(dims, group_by, dev, stream, grouped=None):
+    """The one-call star functions' setup: a StarProbe and, per dimension (rkey, rpay, skey, how[, null]), a
+    HashJoin holding its build under the global strategy; grouped(rkey, rpay, how, null) is called behind the
+    build of each dimension marked in group_by.  Yields (star, [(hj, skey, how, null), ...], extras) and behind
+    the block closes the star, what the block appended to extras, and the contexts, in that order."""
+    hjs, star, extras = [], StarProbe(dev), []
+    try:
+        probe_dims = []
+        for d, g in zip(dims, group_by):
+            if len(d) not in (4, 5):
+                raise ValueError("a dimension is (rkey, rpay, skey, how[, null])")
+            rkey, rpay, skey, how = d[:4]
+            if g and how == "anti":
+                raise ValueError("an anti dimension has no payload to group by")
+            hj = HashJoin(dev)
+            hjs.append(hj)
+            hj.set_strategy("global")
+            hj.build_table(rkey, rpay, stream=stream)
+            null = d[4] if len(d) == 5 and d[4] is not None else -1
+            probe_dims.append((hj, skey, how, null))
+            if g:
+                grouped(rkey, rpay, how, null)
+        yield star, probe_dims, extras
+    finally:
+        star.close()   # (waits for the device before the contexts go)
+        for x in extras + hjs:
+            x.close()
+
+
 def star_join(dims, device=None, stream=None):
     """A star join in one call: dims = [(rkey, rpay, skey, how[, null]), ...],
     one entry per dimension -- its build columns (rpay None for int32 keys:
@@ -1767,23 +1775,8 @@ def star_join(dims, device=None, stream=None):
     if not dims:
         raise ValueError("star_join needs at least one dimension")
     dev = dims[0][2].device.index if device is None else device
-    hjs, star = [], StarProbe(dev)
-    try:
-        probe_dims = []
-        for d in dims:
-            if len(d) not in (4, 5):
-                raise ValueError("a dimension is (rkey, rpay, skey, how[, null])")
-            rkey, rpay, skey, how = d[:4]
-            hj = HashJoin(dev)
-            hjs.append(hj)
-            hj.set_strategy("global")
-            hj.build_table(rkey, rpay, stream=stream)
-            probe_dims.append((hj, skey, how, d[4] if len(d) == 5 else -1))
+    with _star_built(dims, [False] * len(dims), dev, stream) as (star, probe_dims, _):
         return star.probe(probe_dims, stream=stream)
-    finally:
-        star.close()   # (waits for the device before the contexts go)
-        for hj in hjs:
-            hj.close()
 
 
 def star_aggregate(dims, val=None, group_by=None, aggs=("count", "sum"), max_groups=None, device=None, stream=None):
@@ -1806,32 +1799,22 @@ def star_aggregate(dims, val=None, group_by=None, aggs=("count", "sum"), max_gro
     if len(group_by) != len(dims):
         raise ValueError("group_by needs one entry per dimension")
     dev = dims[0][2].device.index if device is None else device
-    hjs, star, kc = [], StarProbe(dev), None
-    try:
-        probe_dims, cols, rows = [], [], []
-        for d, g in zip(dims, group_by):
-            if len(d) not in (4, 5):
-                raise ValueError("a dimension is (rkey, rpay, skey, how[, null])")
-            rkey, rpay, skey, how = d[:4]
-            null = d[4] if len(d) == 5 and d[4] is not None else -1
-            if g and how == "anti":
-                raise ValueError("an anti dimension has no payload to group by")
-            hj = HashJoin(dev)
-            hjs.append(hj)
-            hj.set_strategy("global")
-            hj.build_table(rkey, rpay, stream=stream)
-            probe_dims.append((hj, skey, how, null))
-            if g:   # the values its payload takes: the build's payloads (i32: the row ids) and a LEFT null
-                pay = rpay if rkey.dtype == torch.int64 else torch.arange(rkey.numel(), dtype=torch.int32, device=rkey.device)
-                if how == "left":
-                    pay = torch.cat([pay, torch.tensor([null], dtype=pay.dtype, device=pay.device)])
-                cols.append(pay.contiguous())
-                rows.append(rkey.numel() + (how == "left"))
+    cols, rows = [], []
+
+    def grouped_dim(rkey, rpay, how, null):   # its payload's values: the build's (i32: the row ids) and a LEFT null
+        pay = rpay if rkey.dtype == torch.int64 else torch.arange(rkey.numel(), dtype=torch.int32, device=rkey.device)
+        if how == "left":
+            pay = torch.cat([pay, torch.tensor([null], dtype=pay.dtype, device=pay.device)])
+        cols.append(pay.contiguous())
+        rows.append(rkey.numel() + (how == "left"))
+
+    with _star_built(dims, group_by, dev, stream, grouped_dim) as (star, probe_dims, extras):
         n = probe_dims[0][1].numel()
         grouped = [i for i, g in enumerate(group_by) if g]
         group = base = None
         if grouped:
             kc = KeyCodec([c.dtype for c in cols], dev)
+            extras.append(kc)
             # one observe per column, the others held at a value of their own (an empty one at 0)
             rep = [c[:1] if c.numel() else torch.zeros(1, dtype=c.dtype, device=c.device) for c in cols]
             for i, c in enumerate(cols):
@@ -1862,12 +1845,6 @@ def star_aggregate(dims, val=None, group_by=None, aggs=("count", "sum"), max_gro
         out.update({k: v for k, v in a.items() if k != "key"})
         torch.cuda.synchronize(dev)
         return out
-    finally:
-        star.close()   # (waits for the device before the contexts go)
-        if kc is not None:
-            kc.close()
-        for hj in hjs:
-            hj.close()
 
 
 def star_query(dims, val=None, where=None, expr=None, group_by=None, fact_group_by=None, aggs=("count", "sum"),
@@ -1895,28 +1872,17 @@ def star_query(dims, val=None, where=None, expr=None, group_by=None, fact_group_
         raise ValueError("star_query needs a dimension or a fact column")
     dev = some[0].device.index if device is None else device
     n = some[0].numel()
-    hjs, star = [], StarProbe(dev)
-    try:
-        probe_dims, fields = [], []   # fields: (lo, hi) of every key field, the grouped dimensions' first
-        for d, g in zip(dims, group_by):
-            if len(d) not in (4, 5):
-                raise ValueError("a dimension is (rkey, rpay, skey, how[, null])")
-            rkey, rpay, skey, how = d[:4]
-            null = d[4] if len(d) == 5 and d[4] is not None else -1
-            if g and how == "anti":
-                raise ValueError("an anti dimension has no payload to group by")
-            hj = HashJoin(dev)
-            hjs.append(hj)
-            hj.set_strategy("global")
-            hj.build_table(rkey, rpay, stream=stream)
-            probe_dims.append((hj, skey, how, null))
-            if g:   # the values its payload takes: the build's payloads (i32: the row ids) and a LEFT null
-                vals = []
-                if rkey.numel():
-                    vals = [int(rpay.min()), int(rpay.max())] if rkey.dtype == torch.int64 else [0, rkey.numel() - 1]
-                if how == "left":
-                    vals.append(int(null))
-                fields.append((min(vals), max(vals)) if vals else (0, 0))
+    fields = []   # (lo, hi) of every key field, the grouped dimensions' first
+
+    def grouped_dim(rkey, rpay, how, null):   # its payload's values: the build's (i32: the row ids) and a LEFT null
+        vals = []
+        if rkey.numel():
+            vals = [int(rpay.min()), int(rpay.max())] if rkey.dtype == torch.int64 else [0, rkey.numel() - 1]
+        if how == "left":
+            vals.append(int(null))
+        fields.append((min(vals), max(vals)) if vals else (0, 0))
+
+    with _star_built(dims, group_by, dev, stream, grouped_dim) as (star, probe_dims, _):
         for c in fcols:
             fields.append((int(c.min()), int(c.max())) if c.numel() else (0, 0))
         bits = [(hi - lo).bit_length() for lo, hi in fields]
@@ -1950,10 +1916,6 @@ def star_query(dims, val=None, where=None, expr=None, group_by=None, fact_group_
         out.update(a)
         torch.cuda.synchronize(dev)
         return out
-    finally:
-        star.close()   # (waits for the device before the contexts go)
-        for hj in hjs:
-            hj.close()
 
 
 U64_MAX = (1 << 64) - 1

@@ -14,50 +14,11 @@ import torch
 
 import positional_cases as PC
 import star_cases as SC
-from hashjoin import HashJoin, HJError, StarProbe, _lib, lib, star_join
+from hashjoin import HashJoin, HJError, _lib, lib, star_join
+from star_gpu import (EXTRA, IDS, NULL, SENTINEL, TILE, WIDTHS, assert_same_state, build, context_state, ctxs, dev,
+                      dim_arrays, host, ptr, sentinels, star, strided_keys)
 
 pytestmark = pytest.mark.gpu
-
-NULL, SENTINEL, EXTRA, TILE = SC.NULL, SC.SENTINEL, SC.EXTRA, SC.TILE
-WIDTHS = [True, False]
-IDS = ["i64", "i32"]
-
-
-@pytest.fixture(scope="module")
-def ctxs():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    hs = [HashJoin(0) for _ in range(4)]
-    for h in hs:
-        h.set_strategy("global")
-    yield hs
-    for h in hs:
-        h.close()
-
-
-@pytest.fixture(scope="module")
-def star():
-    s = StarProbe(0)
-    yield s
-    s.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().astype(np.int64)
-
-
-def build(ctxs, c, keys=None):
-    """Every dimension of case c built in its own context: the probe's dimension list.
-    keys: the probe key columns already on the device."""
-    dims = []
-    for i, (h, d) in enumerate(zip(ctxs, c["dims"])):
-        h.build_table(dev(d["rk"]), dev(d["rp"]) if c["wide"] else None)
-        assert h.strategy_used == "global"
-        dims.append((h, dev(d["sk"]) if keys is None else keys[i], d["how"], d["null"]))
-    return dims
 
 
 def check(star, dims, c, e, cap=None, want_row=True, want=None, row_base=0, plan=None):
@@ -67,8 +28,8 @@ def check(star, dims, c, e, cap=None, want_row=True, want=None, row_base=0, plan
     dt = torch.int64 if c["wide"] else torch.int32
     cap = e.m + 5 if cap is None else cap
     want = [p is not None for p in e.pays] if want is None else want
-    bufs = [torch.full((cap + EXTRA,), SENTINEL, dtype=dt, device="cuda") if w else None for w in want]
-    rbuf = torch.full((cap + EXTRA,), SENTINEL, dtype=dt, device="cuda") if want_row else None
+    bufs = [sentinels(cap + EXTRA, dt) if w else None for w in want]
+    rbuf = sentinels(cap + EXTRA, dt) if want_row else None
     m = int(star.probe_into(dims, [None if b is None else b[:cap] for b in bufs],
                             None if rbuf is None else rbuf[:cap], row_base=row_base).item())
     if plan is not None:
@@ -266,11 +227,6 @@ def test_capacity_and_optional_outputs(ctxs, star, wide):
 
 
 # ------------------------------------------------------------------ more tiles than workgroups
-@functools.lru_cache(maxsize=None)
-def strided_keys(wide):
-    return [dev(d["sk"]) for d in SC.strided_case(wide)["dims"]]
-
-
 @pytest.mark.parametrize("forced_global", [False, True], ids=["all-lds", "one-global"])
 @pytest.mark.parametrize("hows", SC.STRIDED_HOWS, ids=["inner", "left"])
 @pytest.mark.parametrize("wide", WIDTHS, ids=IDS)
@@ -302,27 +258,13 @@ def test_strided_tiles(ctxs, star, wide, hows, forced_global):
 def test_contexts_untouched(ctxs, star, wide):
     c, e = SC.mixed_case(wide), SC.expect_of("mixed", wide)
     dims = build(ctxs, c)
-    dt = torch.int64 if wide else torch.int32
-
-    def state():
-        out = []
-        for h, sk, _, _ in dims:
-            o_r = torch.full((c["n"],), SENTINEL, dtype=dt, device="cuda")
-            o_c = torch.full((c["n"],), SENTINEL, dtype=torch.int32, device="cuda")
-            hits = int(h.probe_lookup(sk, o_r, o_c, null=NULL).item())
-            pairs = int(h.probe_relation(sk, sk if wide else None).item())
-            out.append((hits, pairs, host(o_r), host(o_c), h.has_duplicates(), h.strategy_used, h.capacity))
-        return out
-
-    before = state()
+    before = context_state(dims, c["n"], wide)
     used = [h.strategy_used for h, *_ in dims]
     check(star, dims, c, e)
     star.count(dims)
     assert [h.strategy_used for h, *_ in dims] == used
-    after = state()
-    for b, a in zip(before, after):
-        assert b[:2] == a[:2] and b[4:] == a[4:]
-        assert np.array_equal(b[2], a[2]) and np.array_equal(b[3], a[3])
+    after = context_state(dims, c["n"], wide)
+    assert_same_state(before, after)
     for i in range(3):   # and the lookups say what the expectation's dimension columns say
         assert np.array_equal(before[i][3], e.cnt[i])
 
@@ -331,12 +273,11 @@ def test_contexts_untouched(ctxs, star, wide):
 def raw_call(star, wide, hs, kinds, keys, n, outs, out_row, cap, count):
     nd = len(hs)
     f = lib.hj_dev_star_i64 if wide else lib.hj_dev_star_i32
-    args = [star._s, nd, (C.c_void_p * nd)(*[h._ctx for h in hs]), (C.c_int * nd)(*kinds),
-            (C.c_void_p * nd)(*[k.data_ptr() for k in keys]), ((C.c_int64 if wide else C.c_int32) * nd)(*[NULL] * nd), n]
+    args = [star._s, nd, *dim_arrays(wide, hs, kinds, keys), n]
     if not wide:
         args.append(0)
     args += [(C.c_void_p * nd)(*[None if o is None else o.data_ptr() for o in outs]),
-             None if out_row is None else C.c_void_p(out_row.data_ptr()), cap, C.c_void_p(count.data_ptr()), None]
+             ptr(out_row), cap, ptr(count), None]
     return f(*args), lib.hj_last_error().decode()
 
 

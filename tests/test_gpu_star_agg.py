@@ -15,78 +15,20 @@ import torch
 import star_agg_cases as AG
 import star_cases as SC
 from hashjoin import HashJoin, HJError, KeyCodec, StarProbe, _lib, lib, star_aggregate
+from star_gpu import (ARG, EXTRA, GROUP_AGGS, IDS, NULL, SENTINEL, TILE, WIDTHS, assert_same_state, build, check_groups,
+                      compare, context_state, ctxs, dev, dim_arrays, host, ptr, sentinels, star, strided_keys)
 
 pytestmark = pytest.mark.gpu
+STAR_GROUPS = 1 << 13   # the shared star fixture reserves them
 
-NULL, SENTINEL, EXTRA, TILE = SC.NULL, SC.SENTINEL, SC.EXTRA, SC.TILE
-WIDTHS = [True, False]
-IDS = ["i64", "i32"]
 COLS = AG.COLS
-GROUP_AGGS = ("count", "sum", "min", "max")
-ARG = {"key": "out_key", "cnt": "out_cnt", "sum": "out_sum", "min": "out_min", "max": "out_max"}
-
-
-@pytest.fixture(scope="module")
-def ctxs():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    hs = [HashJoin(0) for _ in range(4)]
-    for h in hs:
-        h.set_strategy("global")
-    yield hs
-    for h in hs:
-        h.close()
-
-
-@pytest.fixture(scope="module")
-def star():
-    s = StarProbe(0)
-    s.reserve_groups(1 << 13)
-    yield s
-    s.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().astype(np.int64)
-
-
-def build(ctxs, c, keys=None):
-    """Every dimension of case c built in its own context: the call's dimension list."""
-    dims = []
-    for i, (h, d) in enumerate(zip(ctxs, c["dims"])):
-        h.build_table(dev(d["rk"]), dev(d["rp"]) if c["wide"] else None)
-        assert h.strategy_used == "global"
-        dims.append((h, dev(d["sk"]) if keys is None else keys[i], d["how"], d["null"]))
-    return dims
-
-
-def compare(got, x, upto, full):
-    """got: the host columns written (a dict by COLS name), x the expectation
-    sorted by key.  Every row below `upto` is a true group row with its own
-    aggregates; full: they are all the groups."""
-    if "key" in got:
-        k = got["key"][:upto]
-        idx = np.searchsorted(x["key"], k)
-        assert (idx < len(x["key"])).all() and np.array_equal(x["key"][idx], k), "a key that is no group"
-        assert len(np.unique(k)) == upto, "a group twice"
-        for col, g in got.items():
-            assert np.array_equal(g[:upto], x[col][idx]), (col, np.flatnonzero(g[:upto] != x[col][idx])[:8])
-    elif full:   # no key column to match rows by: each column as a multiset
-        for col, g in got.items():
-            assert np.array_equal(np.sort(g[:upto]), np.sort(x[col])), col
-    if full:
-        assert upto == len(x["key"])
 
 
 def run(star, dims, c, e, val, gshift, gbase=None, want=COLS, cap=None, dval=None, plan=None):
     """One call at `cap` (None: G + 5) writing the columns in `want` against the expectation."""
     x = AG.expect(c, e, val, gshift, gbase)
-    G = len(x["key"])
-    cap = G + 5 if cap is None else cap
-    bufs = {col: torch.full((cap + EXTRA,), SENTINEL, dtype=torch.int64, device="cuda") for col in want}
+    cap = len(x["key"]) + 5 if cap is None else cap
+    bufs = {col: sentinels(cap + EXTRA) for col in want}
     needs_val = any(col in want for col in ("sum", "min", "max"))
     if dval is None and needs_val:
         dval = dev(val)
@@ -94,13 +36,7 @@ def run(star, dims, c, e, val, gshift, gbase=None, want=COLS, cap=None, dval=Non
                               **{ARG[col]: b[:cap] for col, b in bufs.items()})
     if plan is not None:
         plan(star.last_plan)
-    g = int(cnt.item())
-    assert g == G, (g, G)
-    upto = min(g, cap)
-    got = {col: host(b) for col, b in bufs.items()}
-    for col, a in got.items():
-        assert (a[upto:] == SENTINEL).all(), col
-    compare(got, x, upto, upto == G)
+    check_groups(cnt, bufs, x, cap)
     return x
 
 
@@ -276,11 +212,6 @@ def test_wide_int64_min_keys(ctxs, star, where):
 
 # ------------------------------------------------------------------ more tiles than workgroups
 @functools.lru_cache(maxsize=None)
-def strided_keys(wide):
-    return [dev(d["sk"]) for d in SC.strided_case(wide)["dims"]]
-
-
-@functools.lru_cache(maxsize=None)
 def strided_expect(wide, hows):
     c = SC.strided_case(wide, hows)
     val = AG.values(c)
@@ -303,17 +234,14 @@ def test_strided_tiles(ctxs, star, wide, hows, forced_global):
     dims = build(ctxs, c, strided_keys(wide))
     G = len(x["key"])
     star.reserve_groups(G)
-    bufs = {col: torch.full((G + EXTRA,), SENTINEL, dtype=torch.int64, device="cuda") for col in COLS}
+    bufs = {col: sentinels(G + EXTRA) for col in COLS}
     cnt = star.aggregate_into(dims, dev(val), group=gshift, base=gbase, **{ARG[col]: b[:G] for col, b in bufs.items()})
     p = star.last_plan
     assert p["tiles"] == 1026 and p["grid"] < p["tiles"], p   # on a part with more CUs this must fail, not pass unstrided
     assert p["lds_dims"] == [True, not forced_global, False, False], p
     assert p["lds_bytes"] == (64 if forced_global else 128) * 1024 and p["launches"] == 4, p
-    assert int(cnt.item()) == G and G > 512
-    got = {col: host(b) for col, b in bufs.items()}
-    for a in got.values():
-        assert (a[G:] == SENTINEL).all()
-    compare(got, x, G, True)
+    assert G > 512
+    check_groups(cnt, bufs, x, G)
     assert int(x["cnt"].sum()) == e.m
 
 
@@ -354,28 +282,13 @@ def test_count_form_and_optional_outputs(ctxs, star, wide):
 def test_contexts_untouched(ctxs, star, wide):
     c, e = SC.mixed_case(wide), SC.expect_of("mixed", wide)
     dims = build(ctxs, c)
-    dt = torch.int64 if wide else torch.int32
-
-    def state():
-        out = []
-        for h, sk, _, _ in dims:
-            o_r = torch.full((c["n"],), SENTINEL, dtype=dt, device="cuda")
-            o_c = torch.full((c["n"],), SENTINEL, dtype=torch.int32, device="cuda")
-            hits = int(h.probe_lookup(sk, o_r, o_c, null=NULL).item())
-            pairs = int(h.probe_relation(sk, sk if wide else None).item())
-            out.append((hits, pairs, host(o_r), host(o_c), h.has_duplicates(), h.strategy_used, h.capacity))
-        return out
-
-    before = state()
+    before = context_state(dims, c["n"], wide)
     used = [h.strategy_used for h, *_ in dims]
     gshift, gbase = AG.plan(c, (0, 1, 2))
     run(star, dims, c, e, AG.values(c), gshift, gbase)
     run(star, dims, c, e, None, gshift, gbase, want=())
     assert [h.strategy_used for h, *_ in dims] == used
-    after = state()
-    for b, a in zip(before, after):
-        assert b[:2] == a[:2] and b[4:] == a[4:]
-        assert np.array_equal(b[2], a[2]) and np.array_equal(b[3], a[3])
+    assert_same_state(before, context_state(dims, c["n"], wide))
     for i in range(3):   # and the lookups say what the expectation's dimension columns say
         assert np.array_equal(before[i][3], e.cnt[i])
 
@@ -457,12 +370,8 @@ def test_star_aggregate_range_error():
 def raw_call(s, wide, hs, kinds, keys, gshift, val, n, outs, cap, count, nulls=True):
     nd = len(hs)
     f = lib.hj_dev_star_aggregate_i64 if wide else lib.hj_dev_star_aggregate_i32
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-    rc = f(s, nd, (C.c_void_p * nd)(*[None if h is None else h._ctx for h in hs]), (C.c_int * nd)(*kinds),
-           (C.c_void_p * nd)(*[None if k is None else k.data_ptr() for k in keys]),
-           ((C.c_int64 if wide else C.c_int32) * nd)(*[NULL] * nd) if nulls else None,
-           None if gshift is None else (C.c_int * nd)(*gshift), None, ptr(val), n, *[ptr(o) for o in outs], cap,
-           ptr(count), None)
+    rc = f(s, nd, *dim_arrays(wide, hs, kinds, keys, nulls), None if gshift is None else (C.c_int * nd)(*gshift), None,
+           ptr(val), n, *[ptr(o) for o in outs], cap, ptr(count), None)
     return rc, lib.hj_last_error().decode()
 
 
@@ -474,7 +383,7 @@ def test_error_order(ctxs, star, wide):
     dims = build(ctxs, c)
     hs, keys = [d[0] for d in dims], [d[1] for d in dims]
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    col = torch.full((e.m + 5,), SENTINEL, dtype=torch.int64, device="cuda")
+    col = sentinels(e.m + 5)
     no, ARGE, STATE = [None] * 5, _lib.HJ_ERR_ARG, _lib.HJ_ERR_STATE
     fresh = StarProbe(0)                # no group reserve
     other = HashJoin(0)
@@ -625,11 +534,8 @@ def test_graph_replay_over_new_inputs(ctxs, star, wide):
             torch.cuda.synchronize()
             g.replay()
             torch.cuda.synchronize()
-            assert int(cnt.item()) == G and 1 < G < n
-            got = {col: host(b) for col, b in outs.items()}
-            for a in got.values():
-                assert (a[G:] == SENTINEL).all()
-            compare(got, x, G, True)
+            assert 1 < G < n
+            check_groups(cnt, outs, x, cap)
     finally:
         del g
         torch.cuda.synchronize()
@@ -649,8 +555,7 @@ def test_group_table_overflow(ctxs):
         assert s.group_capacity == AG.OVERFLOW_CAPACITY == _lib.STAR_GROUP_MIN_CAPACITY
         dims = build(ctxs, c)
         cap = AG.OVERFLOW_GROUPS + 5
-        key = torch.full((cap,), SENTINEL, dtype=torch.int64, device="cuda")
-        num = torch.full((cap,), SENTINEL, dtype=torch.int64, device="cuda")
+        key, num = sentinels(cap), sentinels(cap)
         m = int(s.aggregate_into(dims, None, key, num, group=[0]).item())
         torch.cuda.synchronize()
         assert m < 0, m                                              # bit 63

@@ -6,7 +6,6 @@ and EXTRA rows longer than the capacity passed, rows are matched to the
 expectation by their key, and the guard region must hold the sentinel.  The
 tile is 2048 rows throughout."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -15,73 +14,16 @@ import torch
 import star_agg_cases as AG
 import star_cases as SC
 import star_query_cases as QC
-from hashjoin import HashJoin, HJError, StarProbe, _lib, lib, star_query
+from hashjoin import HJError, StarProbe, _lib, lib, star_query
+from star_gpu import (ARG, EXTRA, GROUP_AGGS, IDS, NULL, SENTINEL, TILE, WIDTHS, assert_same_state, build, check_groups,
+                      compare, context_state, ctxs, dev, dim_arrays, host, ptr, sentinels, star)
 
 pytestmark = pytest.mark.gpu
+STAR_GROUPS = 1 << 13   # the shared star fixture reserves them
 
-NULL, SENTINEL, EXTRA, TILE = SC.NULL, SC.SENTINEL, SC.EXTRA, SC.TILE
-WIDTHS = [True, False]
-IDS = ["i64", "i32"]
 COLS = QC.COLS
-GROUP_AGGS = ("count", "sum", "min", "max")
-ARG = {"key": "out_key", "cnt": "out_cnt", "sum": "out_sum", "min": "out_min", "max": "out_max"}
 OPS = {"add": _lib.HJ_VALUE_ADD, "sub": _lib.HJ_VALUE_SUB, "mul": _lib.HJ_VALUE_MUL}
 assert TILE == 2048
-
-
-@pytest.fixture(scope="module")
-def ctxs():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    hs = [HashJoin(0) for _ in range(4)]
-    for h in hs:
-        h.set_strategy("global")
-    yield hs
-    for h in hs:
-        h.close()
-
-
-@pytest.fixture(scope="module")
-def star():
-    s = StarProbe(0)
-    s.reserve_groups(1 << 13)
-    yield s
-    s.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().astype(np.int64)
-
-
-def build(ctxs, c, keys=None):
-    """Every dimension of case c built in its own context: the call's dimension list."""
-    dims = []
-    for i, (h, d) in enumerate(zip(ctxs, c["dims"])):
-        h.build_table(dev(d["rk"]), dev(d["rp"]) if c["wide"] else None)
-        assert h.strategy_used == "global"
-        dims.append((h, dev(d["sk"]) if keys is None else keys[i], d["how"], d["null"]))
-    return dims
-
-
-def compare(got, x, upto, full):
-    """got: the host columns written (a dict by COLS name), x the expectation
-    sorted by key.  Every row below `upto` is a true group row with its own
-    aggregates; full: they are all the groups."""
-    if "key" in got:
-        k = got["key"][:upto]
-        idx = np.searchsorted(x["key"], k)
-        assert (idx < len(x["key"])).all() and np.array_equal(x["key"][idx], k), "a key that is no group"
-        assert len(np.unique(k)) == upto, "a group twice"
-        for col, g in got.items():
-            assert np.array_equal(g[:upto], x[col][idx]), (col, np.flatnonzero(g[:upto] != x[col][idx])[:8])
-    elif full:   # no key column to match rows by: each column as a multiset
-        for col, g in got.items():
-            assert np.array_equal(np.sort(g[:upto]), np.sort(x[col])), col
-    if full:
-        assert upto == len(x["key"])
 
 
 def qargs(q):
@@ -94,19 +36,12 @@ def qargs(q):
 def run(star, dims, c, q, want=COLS, cap=None, x=None, kw=None):
     """One query_into at `cap` (None: G + 5) writing the columns in `want` against the expectation."""
     x = QC.expect(c, q) if x is None else x
-    G = len(x["key"])
-    cap = G + 5 if cap is None else cap
-    bufs = {col: torch.full((cap + EXTRA,), SENTINEL, dtype=torch.int64, device="cuda") for col in want}
+    cap = len(x["key"]) + 5 if cap is None else cap
+    bufs = {col: sentinels(cap + EXTRA) for col in want}
     needs_val = any(col in want for col in ("sum", "min", "max"))
     cnt = star.query_into(dims, dev(q["val"]) if needs_val else None, **(qargs(q) if kw is None else kw),
                           **{ARG[col]: b[:cap] for col, b in bufs.items()})
-    g = int(cnt.item())
-    assert g == G, (g, G)
-    upto = min(g, cap)
-    got = {col: host(b) for col, b in bufs.items()}
-    for col, a in got.items():
-        assert (a[upto:] == SENTINEL).all(), col
-    compare(got, x, upto, upto == G)
+    check_groups(cnt, bufs, x, cap)
     return x
 
 
@@ -127,11 +62,7 @@ def raw_call(s, wide, hs, kinds, keys, gshift, fact, val, n, outs, cap, count, n
     nd = len(hs) if nd is None else nd
     k = len(hs)
     f = lib.hj_dev_star_query_i64 if wide else lib.hj_dev_star_query_i32
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-    rc = f(s, nd, (C.c_void_p * k)(*[None if h is None else h._ctx for h in hs]) if k else None,
-           (C.c_int * k)(*kinds) if k else None,
-           (C.c_void_p * k)(*[None if t is None else t.data_ptr() for t in keys]) if k else None,
-           ((C.c_int64 if wide else C.c_int32) * k)(*[NULL] * k) if nulls and k else None,
+    rc = f(s, nd, *dim_arrays(wide, hs, kinds, keys, nulls),
            None if gshift is None or not k else (C.c_int * k)(*gshift),
            None if gbase is None or not k else (C.c_int64 * k)(*gbase),
            None if fact is None else C.byref(fact), ptr(val), n, *[ptr(o) for o in outs], cap, ptr(count), None)
@@ -307,16 +238,12 @@ def test_strided_tiles(ctxs, star, wide):
     dims = build(ctxs, c)
     G = len(x["key"])
     star.reserve_groups(G)
-    bufs = {col: torch.full((G + EXTRA,), SENTINEL, dtype=torch.int64, device="cuda") for col in COLS}
+    bufs = {col: sentinels(G + EXTRA) for col in COLS}
     cnt = star.query_into(dims, dev(q["val"]), **qargs(q), **{ARG[col]: b[:G] for col, b in bufs.items()})
     p = star.last_plan
     assert p["tiles"] == 1026 and p["grid"] < p["tiles"], p   # on a part with more CUs this must fail, not pass unstrided
     assert p["lds_dims"] == [True, True, False, False] and p["lds_bytes"] == 128 * 1024 and p["launches"] == 4, p
-    assert int(cnt.item()) == G
-    got = {col: host(b) for col, b in bufs.items()}
-    for a in got.values():
-        assert (a[G:] == SENTINEL).all()
-    compare(got, x, G, True)
+    check_groups(cnt, bufs, x, G)
 
 
 # ------------------------------------------------------------------ 9. the composed path
@@ -409,26 +336,11 @@ def test_star_query_range_error():
 def test_contexts_untouched(ctxs, star, wide):
     c, _ = QC.edge_case(wide)
     dims = build(ctxs, c)
-    dt = torch.int64 if wide else torch.int32
-
-    def state():
-        out = []
-        for h, sk, _, _ in dims:
-            o_r = torch.full((c["n"],), SENTINEL, dtype=dt, device="cuda")
-            o_c = torch.full((c["n"],), SENTINEL, dtype=torch.int32, device="cuda")
-            hits = int(h.probe_lookup(sk, o_r, o_c, null=NULL).item())
-            pairs = int(h.probe_relation(sk, sk if wide else None).item())
-            out.append((hits, pairs, host(o_r), host(o_c), h.has_duplicates(), h.strategy_used, h.capacity))
-        return out
-
-    before = state()
+    before = context_state(dims, c["n"], wide)
     _, q = QC.edge_query(wide, QC.edge_predicates(wide)["four at once"][0])
     run(star, dims, c, q)
     run(star, dims, c, q, want=())
-    after = state()
-    for b, a in zip(before, after):
-        assert b[:2] == a[:2] and b[4:] == a[4:]
-        assert np.array_equal(b[2], a[2]) and np.array_equal(b[3], a[3])
+    assert_same_state(before, context_state(dims, c["n"], wide))
 
 
 # ------------------------------------------------------------------ 12. error order
@@ -612,11 +524,8 @@ def test_graph_replay_over_new_inputs(ctxs, star, wide):
             torch.cuda.synchronize()
             g.replay()
             torch.cuda.synchronize()
-            assert int(cnt.item()) == G and 1 < G < n
-            got = {col: host(b) for col, b in outs.items()}
-            for a in got.values():
-                assert (a[G:] == SENTINEL).all()
-            compare(got, x, G, True)
+            assert 1 < G < n
+            check_groups(cnt, outs, x, n)
     finally:
         del g
         torch.cuda.synchronize()
@@ -634,8 +543,7 @@ def test_group_table_overflow():
         s.reserve_groups(AG.OVERFLOW_RESERVE)
         assert s.group_capacity == AG.OVERFLOW_CAPACITY == _lib.STAR_GROUP_MIN_CAPACITY
         cap = QC.OVERFLOW_GROUPS + 5
-        key = torch.full((cap,), SENTINEL, dtype=torch.int64, device="cuda")
-        num = torch.full((cap,), SENTINEL, dtype=torch.int64, device="cuda")
+        key, num = sentinels(cap), sentinels(cap)
         dfg = dev(f["fg"])
         m = int(s.query_into([], None, key, num, fact_group=[(dfg, 0, 0)]).item())
         torch.cuda.synchronize()
