@@ -54,6 +54,77 @@ def _need_cuda(*ts):
             raise ValueError("hash join inputs must be contiguous device tensors")
 
 
+def _flagged(m):
+    """m, a count read back from the device, unless bit 63 flags it (hj.h)."""
+    if m < 0:
+        raise RuntimeError("hash join: internal work list overflow (count flagged)")
+    return m
+
+
+def _counted(cnt, sync):
+    """A count form's result: the number (synchronises), or the device tensor."""
+    return int(cnt.item()) if sync else cnt
+
+
+def _tuples(t):
+    if t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 2:
+        raise ValueError("tuples must be an (n, 2) int64 tensor")
+
+
+def _key_dtype(k):
+    if k.dtype not in (torch.int64, torch.int32):
+        raise TypeError("keys must be int32 or int64")
+
+
+def _relation(skey, spay, row_base, payload_required):
+    """The column forms' dispatch: ("i64", (key, payload, n)) or ("i32", (key, n, row_base)) -- the suffix of
+    hj_dev_<op>_<suffix> and its leading relation arguments -- behind the payload checks of each form."""
+    _key_dtype(skey)
+    n = skey.numel()
+    if skey.dtype == torch.int64:
+        if spay is None and payload_required:
+            raise ValueError("int64 probe needs an int64 payload column")
+        if spay is not None and (spay.dtype != torch.int64 or spay.numel() != n):
+            raise ValueError("int64 probe needs an int64 payload column of the same length")
+        return "i64", (_ptr(skey), _ptr(spay), n)
+    if spay is not None:
+        raise ValueError("i32 joins carry row ids, not payloads (reference types)")
+    return "i32", (_ptr(skey), n, int(row_base))
+
+
+def _pair_outputs(out_r, out_s, dtype, what):
+    """cap of a probe's two outputs: both, of one length and of `dtype`, or neither (the count form).
+    dtype None: a tuples twin, which checks no dtype and answers either fault with one message."""
+    both = (out_r is None) == (out_s is None)
+    cap = 0 if out_r is None else out_r.numel()
+    level = out_s is None or out_s.numel() == cap
+    if dtype is None:
+        if not both or not level:
+            raise ValueError(f"{what} probe needs two outputs of one length, or neither to count")
+        return cap
+    if not both:
+        raise ValueError(f"{what} probe needs both outputs, or neither to count")
+    if not level:
+        raise ValueError("output columns differ in length")
+    for o in (out_r, out_s):
+        if o is not None and o.dtype != dtype:
+            raise ValueError(f"{what} outputs carry the probe key's dtype")
+    return cap
+
+
+def _sized(cap, alloc, probe, trim, what):
+    """The capacity loop of every call that returns trimmed outputs: alloc(cap) makes the outputs, probe(outs)
+    fills them and returns M as a checked int, trim(outs, M) is the result; a cap below M is grown to M once."""
+    for _ in range(2):
+        cap = max(1, cap)
+        outs = alloc(cap)
+        m = probe(outs)
+        if m <= cap:
+            return trim(outs, m)
+        cap = m
+    raise RuntimeError(f"{what} output did not fit after resizing")
+
+
 class KeyCodec:
     """Composite keys (hj.h "Composite keys"): exact range packing of up to
     four int32 / int64 key columns into one int64 key that every join, probe
@@ -326,23 +397,22 @@ class KeyFilter:
         Synchronises to read M."""
         form = self._form(skey, "skey")
         n = skey.shape[0]
-        cap = max(1, n if capacity is None else int(capacity))
-        for _ in range(2):
-            shape = (cap, 2) if form == "tuples" else (cap,)
-            out_key = torch.empty(shape, dtype=skey.dtype, device=self.device)
-            out_pay = torch.empty(cap, dtype=torch.int64, device=self.device) if spay is not None else None
-            out_row = torch.empty(cap, dtype=skey.dtype, device=self.device) if with_rows else None
-            m = int(self.apply_into(skey, spay, kind, out_key, out_pay, out_row, stream=stream).item())
-            if m <= cap:
-                outs = [o[:m] for o in (out_key, out_pay, out_row) if o is not None]
-                return outs[0] if len(outs) == 1 else tuple(outs)
-            cap = m
-        raise RuntimeError("filter output did not fit after resizing")
+
+        def alloc(cap):
+            return (torch.empty((cap, 2) if form == "tuples" else (cap,), dtype=skey.dtype, device=self.device),
+                    torch.empty(cap, dtype=torch.int64, device=self.device) if spay is not None else None,
+                    torch.empty(cap, dtype=skey.dtype, device=self.device) if with_rows else None)
+
+        def trim(outs, m):
+            outs = [o[:m] for o in outs if o is not None]
+            return outs[0] if len(outs) == 1 else tuple(outs)
+
+        return _sized(n if capacity is None else int(capacity), alloc,
+                      lambda o: int(self.apply_into(skey, spay, kind, *o, stream=stream).item()), trim, "filter")
 
     def count(self, skey, kind="pass", stream=None, sync=True):
         """How many rows of S pass ('pass') / fail ('reject')."""
-        cnt = self.apply_into(skey, kind=kind, stream=stream)
-        return int(cnt.item()) if sync else cnt
+        return _counted(self.apply_into(skey, kind=kind, stream=stream), sync)
 
 
 class StarProbe:
@@ -460,16 +530,10 @@ class StarProbe:
                               "admits (reserve_groups)")
             return g
 
-        cap = groups(into()) if capacity is None else int(capacity)
-        for _ in range(2):
-            cap = max(1, cap)
-            out_key = torch.empty(cap, dtype=torch.int64, device=self.device)
-            cols = {a: torch.empty(cap, dtype=torch.int64, device=self.device) for a in aggs}
-            g = groups(into(out_key, cols.get("count"), cols.get("sum"), cols.get("min"), cols.get("max")))
-            if g <= cap:
-                return {"key": out_key[:g], **{a: c[:g] for a, c in cols.items()}}
-            cap = g
-        raise RuntimeError(f"{what} output did not fit after resizing")
+        return _sized(groups(into()) if capacity is None else int(capacity),
+                      lambda cap: {c: torch.empty(cap, dtype=torch.int64, device=self.device) for c in ("key", *aggs)},
+                      lambda o: groups(into(o["key"], o.get("count"), o.get("sum"), o.get("min"), o.get("max"))),
+                      lambda o, g: {c: t[:g] for c, t in o.items()}, what)
 
     def probe_into(self, dims, out_pay=None, out_row=None, count=None, row_base=0, stream=None):
         """The raw call: writes min(M, cap) qualifying rows, in input order,
@@ -508,20 +572,18 @@ class StarProbe:
         `capacity` with one more call at the exact M.  Synchronises to read M."""
         _, keys, kinds, _ = self._dims(dims)
         n, dt = keys[0].numel(), keys[0].dtype
-        cap = max(1, n if capacity is None else int(capacity))
-        for _ in range(2):
-            rows = torch.empty(cap, dtype=dt, device=self.device)
-            pays = [None if k == HJ_STAR_ANTI else torch.empty(cap, dtype=dt, device=self.device) for k in kinds]
-            m = int(self.probe_into(dims, pays, rows, row_base=row_base, stream=stream).item())
-            if m <= cap:
-                return rows[:m], [None if p is None else p[:m] for p in pays]
-            cap = m
-        raise RuntimeError("star probe output did not fit after resizing")
+
+        def alloc(cap):   # (rows, one payload column per dimension)
+            return (torch.empty(cap, dtype=dt, device=self.device),
+                    [None if k == HJ_STAR_ANTI else torch.empty(cap, dtype=dt, device=self.device) for k in kinds])
+
+        return _sized(n if capacity is None else int(capacity), alloc,
+                      lambda o: int(self.probe_into(dims, o[1], o[0], row_base=row_base, stream=stream).item()),
+                      lambda o, m: (o[0][:m], [None if p is None else p[:m] for p in o[1]]), "star probe")
 
     def count(self, dims, stream=None, sync=True):
         """How many rows qualify under every dimension."""
-        cnt = self.probe_into(dims, stream=stream)
-        return int(cnt.item()) if sync else cnt
+        return _counted(self.probe_into(dims, stream=stream), sync)
 
     # ---- star aggregate (hj.h "Star aggregate"): GROUP BY over the qualifying rows, one fused pass
     def reserve_groups(self, max_groups):
@@ -779,11 +841,28 @@ class HashJoin:
         else:
             raise TypeError("keys must be int32 or int64")
 
+    def _built(self, rkey, rpay, n_probe, stream, default=None):
+        """build_table under the probe hint n_probe, as every build-then-probe method starts.  default "zeros" |
+        "rows" (R's row index) stands in for the payload column an int64 build was given none of."""
+        self.probe_hint(n_probe)
+        try:
+            if default is not None and rkey.dtype == torch.int64 and rpay is None:
+                rpay = (torch.zeros_like(rkey) if default == "zeros"
+                        else torch.arange(rkey.numel(), dtype=torch.int64, device=self.device))
+            self.build_table(rkey, rpay, stream=stream)
+        finally:
+            self.probe_hint(None)
+
+    def _pair_sized(self, dt, cap, probe, what):
+        """_sized for the joins that return (out_r, out_s): probe(out_r, out_s) returns the count tensor."""
+        return _sized(cap, lambda cap: (torch.empty(cap, dtype=dt, device=self.device),
+                                        torch.empty(cap, dtype=dt, device=self.device)),
+                      lambda o: _flagged(int(probe(*o).item())), lambda o, m: (o[0][:m], o[1][:m]), what)
+
     def build_tuples(self, tuples, stream=None):
         """Build from packed (n, 2) int64 {key, payload} rows (exchange format)."""
         _need_cuda(tuples)
-        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
-            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        _tuples(tuples)
         check(lib.hj_dev_build_tuples_i64(self._ctx, _ptr(tuples), tuples.shape[0], _stream(self.device, stream)),
               "hj_dev_build_tuples_i64")
         self.key_bits = 64
@@ -843,27 +922,15 @@ class HashJoin:
         for o in (out_s, out_key):
             if o is not None and o.dtype != skey.dtype:
                 raise ValueError("exists outputs carry the probe key's dtype")
-        if skey.dtype == torch.int64:
-            if spay is None and out_s is not None:
-                raise ValueError("int64 probe needs an int64 payload column")
-            if spay is not None and (spay.dtype != torch.int64 or spay.numel() != skey.numel()):
-                raise ValueError("int64 probe needs an int64 payload column of the same length")
-            check(lib.hj_dev_exists_i64(self._ctx, k, _ptr(skey), _ptr(spay), skey.numel(), _ptr(out_key), _ptr(out_s),
-                                        cap, _ptr(count), st), "hj_dev_exists_i64")
-        elif skey.dtype == torch.int32:
-            if spay is not None:
-                raise ValueError("i32 joins carry row ids, not payloads (reference types)")
-            check(lib.hj_dev_exists_i32(self._ctx, k, _ptr(skey), skey.numel(), int(row_base), _ptr(out_key),
-                                        _ptr(out_s), cap, _ptr(count), st), "hj_dev_exists_i32")
-        else:
-            raise TypeError("keys must be int32 or int64")
+        sfx, rel = _relation(skey, spay, row_base, out_s is not None)
+        name = "hj_dev_exists_" + sfx
+        check(getattr(lib, name)(self._ctx, k, *rel, _ptr(out_key), _ptr(out_s), cap, _ptr(count), st), name)
         return count
 
     def probe_exists_tuples(self, tuples, kind, out_s, out_key=None, count=None, stream=None):
         """probe_exists over packed (n, 2) int64 {key, payload} rows."""
         _need_cuda(tuples, out_s, out_key)
-        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
-            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        _tuples(tuples)
         count = self._count if count is None else count
         cap = 0 if out_s is None else out_s.numel()
         if out_key is not None and (out_s is None or out_key.numel() != cap):
@@ -875,28 +942,15 @@ class HashJoin:
 
     def count_exists(self, skey, kind="semi", stream=None, sync=True):
         """How many S rows have ('semi') / have no ('anti') partner."""
-        cnt = self.probe_exists(skey, kind=kind, stream=stream)
-        return int(cnt.item()) if sync else cnt
+        return _counted(self.probe_exists(skey, kind=kind, stream=stream), sync)
 
     def _exists_join(self, kind, rkey, skey, spay, rpay, with_keys, capacity, stream):
-        self.probe_hint(skey.numel())
-        try:
-            if rkey.dtype == torch.int64 and rpay is None:
-                rpay = torch.zeros_like(rkey)   # (the build ABI wants a column; exists probes never read it)
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
-        cap = max(1, skey.numel() if capacity is None else int(capacity))
-        for _ in range(2):
-            out_s = torch.empty(cap, dtype=skey.dtype, device=self.device)
-            out_key = torch.empty(cap, dtype=skey.dtype, device=self.device) if with_keys else None
-            m = int(self.probe_exists(skey, spay, kind, out_s, out_key, stream=stream).item())
-            if m < 0:   # bit 63 (hj.h)
-                raise RuntimeError("hash join: internal work list overflow (count flagged)")
-            if m <= cap:
-                return (out_key[:m], out_s[:m]) if with_keys else out_s[:m]
-            cap = m
-        raise RuntimeError("exists output did not fit after resizing")
+        self._built(rkey, rpay, skey.numel(), stream, "zeros")   # (the build ABI wants a column; never read here)
+        return _sized(skey.numel() if capacity is None else int(capacity),
+                      lambda cap: (torch.empty(cap, dtype=skey.dtype, device=self.device),
+                                   torch.empty(cap, dtype=skey.dtype, device=self.device) if with_keys else None),
+                      lambda o: _flagged(int(self.probe_exists(skey, spay, kind, *o, stream=stream).item())),
+                      lambda o, m: (o[1][:m], o[0][:m]) if with_keys else o[0][:m], "exists")
 
     def semi_join(self, rkey, skey, spay=None, rpay=None, with_keys=False, capacity=None, stream=None):
         """Build R, then the S payloads (row ids for int32 keys) of the rows
@@ -920,8 +974,7 @@ class HashJoin:
         st = _stream(self.device, stream)
         count = self._count if count is None else count
         n = skey.numel()
-        if skey.dtype not in (torch.int64, torch.int32):
-            raise TypeError("keys must be int32 or int64")
+        _key_dtype(skey)
         if out_r is None and out_cnt is None and n > 0:
             raise ValueError("lookup needs out_r or out_cnt (count_exists counts the rows with a partner)")
         if out_r is not None and (out_r.dtype != skey.dtype or out_r.numel() < n):
@@ -940,18 +993,10 @@ class HashJoin:
         the payload is R's row index (the id -> index mapping); int32 keys
         always carry R's row ids.  Composite keys: pass KeyCodec.pack's
         output of both relations as rkey / skey."""
-        self.probe_hint(skey.numel())
-        try:
-            if rkey.dtype == torch.int64 and rpay is None:
-                rpay = torch.arange(rkey.numel(), dtype=torch.int64, device=self.device)
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
+        self._built(rkey, rpay, skey.numel(), stream, "rows")
         out_r = torch.empty(skey.numel(), dtype=skey.dtype, device=self.device)
         out_cnt = torch.empty(skey.numel(), dtype=torch.int32, device=self.device) if with_counts else None
-        m = int(self.probe_lookup(skey, out_r, out_cnt, null=null, stream=stream).item())
-        if m < 0:   # bit 63 (hj.h)
-            raise RuntimeError("hash join: internal work list overflow (count flagged)")
+        _flagged(int(self.probe_lookup(skey, out_r, out_cnt, null=null, stream=stream).item()))
         return (out_r, out_cnt) if with_counts else out_r
 
     # ---- as-of probe (hj.h "As-of probe"): per probe row, the nearest partner at or before a bound
@@ -969,8 +1014,7 @@ class HashJoin:
         st = _stream(self.device, stream)
         count = self._count if count is None else count
         n = skey.numel()
-        if skey.dtype not in (torch.int64, torch.int32):
-            raise TypeError("keys must be int32 or int64")
+        _key_dtype(skey)
         if sbound is None or sbound.dtype != skey.dtype or sbound.numel() != n:
             raise ValueError("sbound carries the probe key's dtype and length")
         if out_r is None:
@@ -988,18 +1032,10 @@ class HashJoin:
         """Build R, then probe_asof: out_r of length |S|.  int64 keys with rpay
         None: the payload is R's row index ("the last R row with this key at or
         before row b"); int32 keys always carry R's row ids."""
-        self.probe_hint(skey.numel())
-        try:
-            if rkey.dtype == torch.int64 and rpay is None:
-                rpay = torch.arange(rkey.numel(), dtype=torch.int64, device=self.device)
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
+        self._built(rkey, rpay, skey.numel(), stream, "rows")
         out_r = torch.empty(skey.numel(), dtype=skey.dtype, device=self.device)
-        m = int(self.probe_asof(skey, sbound, out_r, direction=direction, strict=strict, null=null,
-                                stream=stream).item())
-        if m < 0:   # bit 63 (hj.h)
-            raise RuntimeError("hash join: internal work list overflow (count flagged)")
+        _flagged(int(self.probe_asof(skey, sbound, out_r, direction=direction, strict=strict, null=null,
+                                     stream=stream).item()))
         return out_r
 
     def asof_join(self, rkey, rtime, skey, stime, direction="backward", allow_exact_matches=True, tolerance=None,
@@ -1034,11 +1070,7 @@ class HashJoin:
         low = (1 << rowbits) - 1
         rpay = ((rtime - t0) << rowbits) | torch.arange(nr, dtype=torch.int64, device=self.device)
         sbase = (stime - t0) << rowbits
-        self.probe_hint(ns)
-        try:
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
+        self._built(rkey, rpay, ns, stream)
 
         def probe(fwd):
             # backward: the low bits all ones admit every row of an equal time and the max takes the last;
@@ -1079,8 +1111,7 @@ class HashJoin:
         st = _stream(self.device, stream)
         count = self._count if count is None else count
         n = skey.numel()
-        if skey.dtype not in (torch.int64, torch.int32):
-            raise TypeError("keys must be int32 or int64")
+        _key_dtype(skey)
         if out_off is None or out_off.dtype != torch.int64 or out_off.numel() < n + 1:
             raise ValueError("out_off is an int64 column of at least len(skey) + 1 elements")
         if out_r is not None and out_r.dtype != skey.dtype:
@@ -1095,23 +1126,14 @@ class HashJoin:
     def count_expand(self, skey, how="inner", stream=None):
         """The count form: (offsets, M) of probe_expand, nothing else written."""
         off = torch.empty(skey.numel() + 1, dtype=torch.int64, device=self.device)
-        m = int(self.probe_expand(skey, off, None, how=how, stream=stream).item())
-        if m < 0:   # bit 63 (hj.h)
-            raise RuntimeError("hash join: internal work list overflow (count flagged)")
-        return off, m
+        return off, _flagged(int(self.probe_expand(skey, off, None, how=how, stream=stream).item()))
 
     def expand(self, rkey, rpay, skey, how="inner", null=-1, stream=None):
         """Build R, then probe_expand sized exactly: (offsets, out_r), a CSR over
         S's rows in input order.  int64 keys with rpay None: the payload is R's
         row index; int32 keys always carry R's row ids.  Composite keys: pass
         KeyCodec.pack's output of both relations as rkey / skey."""
-        self.probe_hint(skey.numel())
-        try:
-            if rkey.dtype == torch.int64 and rpay is None:
-                rpay = torch.arange(rkey.numel(), dtype=torch.int64, device=self.device)
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
+        self._built(rkey, rpay, skey.numel(), stream, "rows")
         off, m = self.count_expand(skey, how=how, stream=stream)
         out_r = torch.empty(m, dtype=skey.dtype, device=self.device)
         if m:
@@ -1159,8 +1181,7 @@ class HashJoin:
         st = _stream(self.device, stream)
         k = GROUP_KINDS[how]
         count = self._count if count is None else count
-        if skey.dtype not in (torch.int64, torch.int32):
-            raise TypeError("keys must be int32 or int64")
+        _key_dtype(skey)
         cap = self._group_outputs(skey.dtype, out_r, out_cnt, out_sum, out_min, out_max)
         outs = (_ptr(out_r), _ptr(out_cnt), _ptr(out_sum), _ptr(out_min), _ptr(out_max))
         if skey.dtype == torch.int64:
@@ -1181,8 +1202,7 @@ class HashJoin:
                            out_max=None, null=0, count=None, stream=None):
         """probe_group over packed (n, 2) int64 {key, value} rows."""
         _need_cuda(tuples, out_r, out_cnt, out_sum, out_min, out_max)
-        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
-            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        _tuples(tuples)
         count = self._count if count is None else count
         cap = self._group_outputs(torch.int64, out_r, out_cnt, out_sum, out_min, out_max)
         check(lib.hj_dev_group_tuples_i64(self._ctx, GROUP_KINDS[how], _ptr(tuples), tuples.shape[0], int(null),
@@ -1192,8 +1212,11 @@ class HashJoin:
 
     def count_group(self, skey, how="matched", stream=None, sync=True):
         """M of the group probe: the R rows with a partner ("matched") or all of them."""
-        cnt = self.probe_group(skey, how=how, stream=stream)
-        return int(cnt.item()) if sync else cnt
+        return _counted(self.probe_group(skey, how=how, stream=stream), sync)
+
+    def _agg_columns(self, cap, dt, names):
+        """One empty output column of cap rows per name: the sum is int64, every other takes dt."""
+        return {a: torch.empty(cap, dtype=torch.int64 if a == "sum" else dt, device=self.device) for a in names}
 
     def group_join(self, rkey, rpay, skey, sval, how="matched", aggs=("count", "sum"), null=0, capacity=None,
                    stream=None):
@@ -1206,24 +1229,16 @@ class HashJoin:
             raise ValueError("how must be 'matched' or 'all'")
         if any(a not in GROUP_AGGS for a in aggs):
             raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
-        self.probe_hint(skey.numel())
-        try:
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
+        self._built(rkey, rpay, skey.numel(), stream)
         dt = torch.int64 if rkey.dtype == torch.int64 else torch.int32
-        cap = max(1, rkey.numel() if capacity is None else int(capacity))
-        for _ in range(2):
-            out_r = torch.empty(cap, dtype=dt, device=self.device)
-            cols = {a: torch.empty(cap, dtype=torch.int64 if a == "sum" else dt, device=self.device) for a in aggs}
-            m = int(self.probe_group(skey, sval, how, out_r, cols.get("count"), cols.get("sum"), cols.get("min"),
-                                     cols.get("max"), null=null, stream=stream).item())
-            if m < 0:   # bit 63 (hj.h)
-                raise RuntimeError("hash join: internal work list overflow (count flagged)")
-            if m <= cap:
-                return out_r[:m], {a: c[:m] for a, c in cols.items()}
-            cap = m
-        raise RuntimeError("group join output did not fit after resizing")
+
+        def probe(o):
+            return _flagged(int(self.probe_group(skey, sval, how, o["r"], o.get("count"), o.get("sum"), o.get("min"),
+                                                 o.get("max"), null=null, stream=stream).item()))
+
+        return _sized(rkey.numel() if capacity is None else int(capacity),
+                      lambda cap: self._agg_columns(cap, dt, ("r", *aggs)), probe,
+                      lambda o, m: (o["r"][:m], {a: c[:m] for a, c in o.items() if a != "r"}), "group join")
 
     # ---- hash aggregate (hj.h "Hash aggregate"): GROUP BY key over one relation, no build
     def aggregate_into(self, key, val=None, out_key=None, out_cnt=None, out_sum=None, out_min=None, out_max=None,
@@ -1239,8 +1254,7 @@ class HashJoin:
         _need_cuda(key, val, out_key, out_cnt, out_sum, out_min, out_max)
         st = _stream(self.device, stream)
         count = self._count if count is None else count
-        if key.dtype not in (torch.int64, torch.int32):
-            raise TypeError("keys must be int32 or int64")
+        _key_dtype(key)
         cap = self._group_outputs(key.dtype, out_key, out_cnt, out_sum, out_min, out_max)
         outs = (_ptr(out_key), _ptr(out_cnt), _ptr(out_sum), _ptr(out_min), _ptr(out_max))
         if key.dtype == torch.int64:
@@ -1259,8 +1273,7 @@ class HashJoin:
                               count=None, stream=None):
         """aggregate_into over packed (n, 2) int64 {key, value} rows."""
         _need_cuda(tuples, out_key, out_cnt, out_sum, out_min, out_max)
-        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
-            raise ValueError("tuples must be an (n, 2) int64 tensor")
+        _tuples(tuples)
         count = self._count if count is None else count
         cap = self._group_outputs(torch.int64, out_key, out_cnt, out_sum, out_min, out_max)
         check(lib.hj_dev_aggregate_tuples_i64(self._ctx, _ptr(tuples), tuples.shape[0], _ptr(out_key), _ptr(out_cnt),
@@ -1270,8 +1283,7 @@ class HashJoin:
 
     def count_distinct(self, key, stream=None, sync=True):
         """The number of distinct keys (the aggregate's count-only form)."""
-        cnt = self.aggregate_into(key, stream=stream)
-        return int(cnt.item()) if sync else cnt
+        return _counted(self.aggregate_into(key, stream=stream), sync)
 
     def aggregate(self, key, val=None, aggs=("count", "sum"), capacity=None, stream=None):
         """GROUP BY key: returns {"key": tensor, agg: tensor, ...} trimmed to M,
@@ -1281,19 +1293,14 @@ class HashJoin:
         if any(a not in GROUP_AGGS for a in aggs):
             raise ValueError("aggs are among 'count', 'sum', 'min', 'max'")
         dt = key.dtype
-        cap = self.count_distinct(key, stream=stream) if capacity is None else int(capacity)
-        for _ in range(2):
-            cap = max(1, cap)
-            out_key = torch.empty(cap, dtype=dt, device=self.device)
-            cols = {a: torch.empty(cap, dtype=torch.int64 if a == "sum" else dt, device=self.device) for a in aggs}
-            m = int(self.aggregate_into(key, val, out_key, cols.get("count"), cols.get("sum"), cols.get("min"),
-                                        cols.get("max"), stream=stream).item())
-            if m < 0:   # bit 63 (hj.h)
-                raise RuntimeError("hash join: internal work list overflow (count flagged)")
-            if m <= cap:
-                return {"key": out_key[:m], **{a: c[:m] for a, c in cols.items()}}
-            cap = m
-        raise RuntimeError("aggregate output did not fit after resizing")
+
+        def probe(o):
+            return _flagged(int(self.aggregate_into(key, val, o["key"], o.get("count"), o.get("sum"), o.get("min"),
+                                                    o.get("max"), stream=stream).item()))
+
+        return _sized(self.count_distinct(key, stream=stream) if capacity is None else int(capacity),
+                      lambda cap: self._agg_columns(cap, dt, ("key", *aggs)), probe,
+                      lambda o, m: {c: t[:m] for c, t in o.items()}, "aggregate")
 
     def distinct(self, key, capacity=None, stream=None):
         """SELECT DISTINCT key: the distinct keys, in no particular order."""
@@ -1310,40 +1317,18 @@ class HashJoin:
         _need_cuda(skey, spay, out_r, out_s)
         st = _stream(self.device, stream)
         count = self._count if count is None else count
-        if (out_r is None) != (out_s is None):
-            raise ValueError("outer probe needs both outputs, or neither to count")
-        cap = 0 if out_r is None else out_r.numel()
-        if out_s is not None and out_s.numel() != cap:
-            raise ValueError("output columns differ in length")
-        for o in (out_r, out_s):
-            if o is not None and o.dtype != skey.dtype:
-                raise ValueError("outer outputs carry the probe key's dtype")
-        if skey.dtype == torch.int64:
-            if spay is None and out_s is not None:
-                raise ValueError("int64 probe needs an int64 payload column")
-            if spay is not None and (spay.dtype != torch.int64 or spay.numel() != skey.numel()):
-                raise ValueError("int64 probe needs an int64 payload column of the same length")
-            check(lib.hj_dev_probe_outer_i64(self._ctx, _ptr(skey), _ptr(spay), skey.numel(), int(null), _ptr(out_r),
-                                             _ptr(out_s), cap, _ptr(count), st), "hj_dev_probe_outer_i64")
-        elif skey.dtype == torch.int32:
-            if spay is not None:
-                raise ValueError("i32 joins carry row ids, not payloads (reference types)")
-            check(lib.hj_dev_probe_outer_i32(self._ctx, _ptr(skey), skey.numel(), int(row_base), int(null),
-                                             _ptr(out_r), _ptr(out_s), cap, _ptr(count), st),
-                  "hj_dev_probe_outer_i32")
-        else:
-            raise TypeError("keys must be int32 or int64")
+        cap = _pair_outputs(out_r, out_s, skey.dtype, "outer")
+        sfx, rel = _relation(skey, spay, row_base, out_s is not None)
+        name = "hj_dev_probe_outer_" + sfx
+        check(getattr(lib, name)(self._ctx, *rel, int(null), _ptr(out_r), _ptr(out_s), cap, _ptr(count), st), name)
         return count
 
     def probe_outer_tuples(self, tuples, out_r, out_s, null=-1, count=None, stream=None):
         """probe_outer over packed (n, 2) int64 {key, payload} rows."""
         _need_cuda(tuples, out_r, out_s)
-        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
-            raise ValueError("tuples must be an (n, 2) int64 tensor")
-        if (out_r is None) != (out_s is None) or (out_r is not None and out_r.numel() != out_s.numel()):
-            raise ValueError("outer probe needs two outputs of one length, or neither to count")
+        _tuples(tuples)
+        cap = _pair_outputs(out_r, out_s, None, "outer")
         count = self._count if count is None else count
-        cap = 0 if out_r is None else out_r.numel()
         check(lib.hj_dev_probe_outer_tuples_i64(self._ctx, _ptr(tuples), tuples.shape[0], int(null), _ptr(out_r),
                                                 _ptr(out_s), cap, _ptr(count), _stream(self.device, stream)),
               "hj_dev_probe_outer_tuples_i64")
@@ -1351,31 +1336,18 @@ class HashJoin:
 
     def count_outer(self, skey, stream=None, sync=True):
         """M of the outer probe: the inner join's pairs plus the S rows without a partner."""
-        cnt = self.probe_outer(skey, stream=stream)
-        return int(cnt.item()) if sync else cnt
+        return _counted(self.probe_outer(skey, stream=stream), sync)
 
     def outer_join(self, rkey, rpay, skey, spay=None, null=-1, capacity=None, stream=None):
         """join() keeping every S row: build R, then the outer probe into an
         output sized |S| rows (exact when no S row has two partners), or
         `capacity`, re-probing once at the exact M if that was too small.
         Returns (R payloads or `null`, S payloads); row ids for int32 keys."""
-        self.probe_hint(skey.numel())
-        try:
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
+        self._built(rkey, rpay, skey.numel(), stream)
         dt = torch.int64 if rkey.dtype == torch.int64 else torch.int32
-        cap = max(1, skey.numel() if capacity is None else int(capacity))
-        for _ in range(2):
-            out_r = torch.empty(cap, dtype=dt, device=self.device)
-            out_s = torch.empty(cap, dtype=dt, device=self.device)
-            m = int(self.probe_outer(skey, spay, out_r, out_s, null=null, stream=stream).item())
-            if m < 0:   # bit 63: an internal work list overflowed (hj.h)
-                raise RuntimeError("hash join: internal work list overflow (count flagged)")
-            if m <= cap:
-                return out_r[:m], out_s[:m]
-            cap = m
-        raise RuntimeError("outer join output did not fit after resizing")
+        return self._pair_sized(dt, skey.numel() if capacity is None else int(capacity),
+                                lambda o_r, o_s: self.probe_outer(skey, spay, o_r, o_s, null=null, stream=stream),
+                                "outer join")
 
     # ---- build-side and full outer join (hj.h "Build-side and full outer join")
     def probe_full(self, skey, spay=None, out_r=None, out_s=None, kind="full", null_r=-1, null_s=-1, count=None,
@@ -1392,41 +1364,19 @@ class HashJoin:
         st = _stream(self.device, stream)
         k = FULL_KINDS[kind]
         count = self._count if count is None else count
-        if (out_r is None) != (out_s is None):
-            raise ValueError("full probe needs both outputs, or neither to count")
-        cap = 0 if out_r is None else out_r.numel()
-        if out_s is not None and out_s.numel() != cap:
-            raise ValueError("output columns differ in length")
-        for o in (out_r, out_s):
-            if o is not None and o.dtype != skey.dtype:
-                raise ValueError("full outputs carry the probe key's dtype")
-        if skey.dtype == torch.int64:
-            if spay is None and out_s is not None:
-                raise ValueError("int64 probe needs an int64 payload column")
-            if spay is not None and (spay.dtype != torch.int64 or spay.numel() != skey.numel()):
-                raise ValueError("int64 probe needs an int64 payload column of the same length")
-            check(lib.hj_dev_probe_full_i64(self._ctx, k, _ptr(skey), _ptr(spay), skey.numel(), int(null_r),
-                                            int(null_s), _ptr(out_r), _ptr(out_s), cap, _ptr(count), st),
-                  "hj_dev_probe_full_i64")
-        elif skey.dtype == torch.int32:
-            if spay is not None:
-                raise ValueError("i32 joins carry row ids, not payloads (reference types)")
-            check(lib.hj_dev_probe_full_i32(self._ctx, k, _ptr(skey), skey.numel(), int(row_base), int(null_r),
-                                            int(null_s), _ptr(out_r), _ptr(out_s), cap, _ptr(count), st),
-                  "hj_dev_probe_full_i32")
-        else:
-            raise TypeError("keys must be int32 or int64")
+        cap = _pair_outputs(out_r, out_s, skey.dtype, "full")
+        sfx, rel = _relation(skey, spay, row_base, out_s is not None)
+        name = "hj_dev_probe_full_" + sfx
+        check(getattr(lib, name)(self._ctx, k, *rel, int(null_r), int(null_s), _ptr(out_r), _ptr(out_s), cap,
+                                 _ptr(count), st), name)
         return count
 
     def probe_full_tuples(self, tuples, out_r, out_s, kind="full", null_r=-1, null_s=-1, count=None, stream=None):
         """probe_full over packed (n, 2) int64 {key, payload} rows."""
         _need_cuda(tuples, out_r, out_s)
-        if tuples.dtype != torch.int64 or tuples.dim() != 2 or tuples.shape[1] != 2:
-            raise ValueError("tuples must be an (n, 2) int64 tensor")
-        if (out_r is None) != (out_s is None) or (out_r is not None and out_r.numel() != out_s.numel()):
-            raise ValueError("full probe needs two outputs of one length, or neither to count")
+        _tuples(tuples)
+        cap = _pair_outputs(out_r, out_s, None, "full")
         count = self._count if count is None else count
-        cap = 0 if out_r is None else out_r.numel()
         check(lib.hj_dev_probe_full_tuples_i64(self._ctx, FULL_KINDS[kind], _ptr(tuples), tuples.shape[0], int(null_r),
                                                int(null_s), _ptr(out_r), _ptr(out_s), cap, _ptr(count),
                                                _stream(self.device, stream)), "hj_dev_probe_full_tuples_i64")
@@ -1434,8 +1384,7 @@ class HashJoin:
 
     def count_full(self, skey, kind="full", stream=None, sync=True):
         """M of the full (or build-side) outer probe."""
-        cnt = self.probe_full(skey, kind=kind, stream=stream)
-        return int(cnt.item()) if sync else cnt
+        return _counted(self.probe_full(skey, kind=kind, stream=stream), sync)
 
     def full_join(self, rkey, rpay, skey, spay=None, how="full", null_r=-1, null_s=-1, capacity=None, stream=None):
         """join() keeping every R row and (how="full") every S row: build R,
@@ -1445,24 +1394,11 @@ class HashJoin:
         payloads or null_s); row ids for int32 keys."""
         if how not in FULL_KINDS:
             raise ValueError("how must be 'full' or 'build'")
-        self.probe_hint(skey.numel())
-        try:
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
+        self._built(rkey, rpay, skey.numel(), stream)
         dt = torch.int64 if rkey.dtype == torch.int64 else torch.int32
-        cap = max(1, skey.numel() + rkey.numel() if capacity is None else int(capacity))
-        for _ in range(2):
-            out_r = torch.empty(cap, dtype=dt, device=self.device)
-            out_s = torch.empty(cap, dtype=dt, device=self.device)
-            m = int(self.probe_full(skey, spay, out_r, out_s, kind=how, null_r=null_r, null_s=null_s,
-                                    stream=stream).item())
-            if m < 0:   # bit 63: an internal work list overflowed (hj.h)
-                raise RuntimeError("hash join: internal work list overflow (count flagged)")
-            if m <= cap:
-                return out_r[:m], out_s[:m]
-            cap = m
-        raise RuntimeError("full join output did not fit after resizing")
+        return self._pair_sized(dt, skey.numel() + rkey.numel() if capacity is None else int(capacity),
+                                lambda o_r, o_s: self.probe_full(skey, spay, o_r, o_s, kind=how, null_r=null_r,
+                                                                 null_s=null_s, stream=stream), "full join")
 
     # ---- folded routing (hj.h "Folded routing"): the owner and the
     # receiver's first radix-pass bin from one hash, so receivers skip a pass
@@ -1597,24 +1533,10 @@ class HashJoin:
         """The @main join (join_v2.mlir:646-696) on device tensors: build, then
         probe into an output sized optimistically (|S| rows, or `capacity`),
         re-probing once at the exact M if that was too small."""
-        self.probe_hint(skey.numel())
-        try:
-            self.build_table(rkey, rpay, stream=stream)
-        finally:
-            self.probe_hint(None)
+        self._built(rkey, rpay, skey.numel(), stream)
         dt = torch.int64 if rkey.dtype == torch.int64 else torch.int32
-        cap = max(1, skey.numel() if capacity is None else int(capacity))
-        for _ in range(2):
-            out_r = torch.empty(cap, dtype=dt, device=self.device)
-            out_s = torch.empty(cap, dtype=dt, device=self.device)
-            cnt = self.probe_relation(skey, spay, out_r, out_s, stream=stream)
-            m = int(cnt.item())
-            if m < 0:   # bit 63: an internal work list overflowed (hj.h)
-                raise RuntimeError("hash join: internal work list overflow (count flagged)")
-            if m <= cap:
-                return out_r[:m], out_s[:m]
-            cap = m
-        raise RuntimeError("join output did not fit after resizing")
+        return self._pair_sized(dt, skey.numel() if capacity is None else int(capacity),
+                                lambda o_r, o_s: self.probe_relation(skey, spay, o_r, o_s, stream=stream), "join")
 
     # ---- key filter (hj.h "Key filter"): opt-in, nothing here turns it on by itself
     FILTERED_JOIN_KINDS = ("inner", "semi", "anti")

@@ -8,14 +8,13 @@ columns, sorted by key, bit for bit.  int64 values span the whole range, so
 sums wrap, and include INT64_MIN / INT64_MAX; i32 values are the row ids.
 Outputs are SENTINEL-filled and EXTRA rows longer than the capacity passed:
 nothing may be written at or past it."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import aggregate_cases as AC
 from hashjoin import HashJoin, HJError, _lib, lib
+from join_gpu import dev, hj, sentinels, strategy  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,27 +27,6 @@ STRATEGIES = ["global", "radix"]
 AGGS = ("count", "sum", "min", "max")
 
 
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-@contextlib.contextmanager
-def strategy(hj, name, bits=0):
-    hj.set_strategy(name, radix_bits=bits if name == "radix" else 0)
-    try:
-        yield hj
-    finally:
-        hj.set_strategy("auto")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def planted(dtype):
     return (I64_MIN, 0, -1) if dtype == np.int64 else (-1, I32_MIN, 0)
 
@@ -59,7 +37,7 @@ def run(hj, key, val, cap, cols=COLS, tuples=False, row_base=0, tensors=None):
     tensors to pass instead of fresh copies."""
     wide = key.dtype == np.int64
     dt = torch.int64 if wide else torch.int32
-    bufs = {c: torch.full((cap + EXTRA,), SENTINEL, dtype=torch.int64 if c == "sum" else dt, device="cuda")
+    bufs = {c: sentinels(cap + EXTRA, SENTINEL, torch.int64 if c == "sum" else dt)
             for c in cols}
     o = {c: (bufs[c][:cap] if c in bufs else None) for c in COLS}
     kw = dict(out_key=o["key"], out_cnt=o["cnt"], out_sum=o["sum"], out_min=o["min"], out_max=o["max"])

@@ -17,6 +17,8 @@ import torch
 import asof_cases as AC
 import outer_cases as OC
 from hashjoin import HashJoin, _lib, lib
+from join_gpu import (assert_radix_kernel, build, dev, glob_hj, graph_replay, hj, host, sentinels,  # noqa: F401
+                      timing_reports)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,35 +26,12 @@ I64_MIN, I64_MAX = AC.I64_MIN, AC.I64_MAX
 NULL, SENTINEL, EXTRA = -9, -12345, 64   # i32 payloads are row ids (>= 0)
 
 
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-@pytest.fixture
-def glob_hj(hj):
-    hj.set_strategy("global")
-    yield hj
-    hj.set_strategy("auto")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def build(hj, rk, rp):
-    hj.build_table(dev(rk), dev(rp) if rk.dtype == np.int64 else None)
-
-
 def probe(hj, sk, sb, kind, null=NULL):
     """One as-of probe of the current build into a sentinel-filled output EXTRA
     rows longer than S: (d_count, out_r as an int64 host array)."""
     n = len(sk)
     dt = torch.int64 if sk.dtype == np.int64 else torch.int32
-    o_r = torch.full((n + EXTRA,), SENTINEL, dtype=dt, device="cuda")
+    o_r = sentinels(n + EXTRA, SENTINEL, dt)
     direction, strict = AC.KIND_ARGS[kind]
     m = int(hj.probe_asof(dev(sk), dev(sb), o_r, direction=direction, strict=strict, null=null).item())
     return m, o_r.cpu().numpy().astype(np.int64)
@@ -80,9 +59,8 @@ def selects(res, sk_has_partner):
 
 
 def assert_radix(hj):
-    assert hj.strategy_used == "radix"
-    assert lib.hj_ctx_join_kernel(hj._ctx) == _lib.HJ_JOIN_KERNEL_ASOF == 11
-    assert hj.join_kernel == "k_join_asof"
+    assert _lib.HJ_JOIN_KERNEL_ASOF == 11
+    assert_radix_kernel(hj, _lib.HJ_JOIN_KERNEL_ASOF, "k_join_asof")
 
 
 # ------------------------------------------------------------------ global
@@ -533,18 +511,7 @@ def test_timing_reports_asof(hj, oracle, strategy):
     rk, _, sk, _ = oracle.gen_pkfk_i64(51, 4000, 20000, 0.5)
     rp = AC.payloads(rk, 51)
     sb = AC.bounds(rk, rp, sk, 51)
-    hj.set_strategy(strategy, radix_bits=6 if strategy == "radix" else 0)
-    hj.set_timing(True)
-    try:
-        build(hj, rk, rp)
-        check(hj, rk, rp, sk, sb, kinds=(0,))
-        t = hj.last_timing()
-        assert t["probe"] > 0
-        if strategy == "radix":
-            assert t["probe_partition"] > 0 and t["probe_join"] > 0
-    finally:
-        hj.set_timing(False)
-        hj.set_strategy("auto")
+    timing_reports(hj, strategy, lambda: build(hj, rk, rp), [lambda: check(hj, rk, rp, sk, sb, kinds=(0,))])
 
 
 @pytest.mark.parametrize("strategy,wide", [("radix", True), ("global", False)], ids=["i64-radix", "i32-global"])
@@ -573,41 +540,31 @@ def test_graph_replay(hj, oracle, strategy, wide):
                 t.copy_(torch.from_numpy(np.ascontiguousarray(x)))
         torch.cuda.synchronize()
 
-    hj.set_strategy(strategy)
-    g = None
-    try:
-        bits = 64 if wide else 32
+    bits = 64 if wide else 32
+    o_r = torch.empty(n, dtype=kt, device="cuda")
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def setup():
         load(*sets[0])
         hj.allocate_hash_table(n, bits)
         hj.build_table(d_rk, d_rp)
         hj.reserve_probe(n, bits)
-        o_r = torch.empty(n, dtype=kt, device="cuda")
-        cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):   # one eager step on the capture stream first
-            hj.build_table(d_rk, d_rp)
-            hj.probe_asof(d_sk, d_sb, o_r, null=NULL, count=cnt)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            hj.build_table(d_rk, d_rp)
-            hj.probe_asof(d_sk, d_sb, o_r, null=NULL, count=cnt)
-        torch.cuda.synchronize()
-        assert hj.strategy_used == strategy
-        for data in sets[1:] + sets[:1]:
-            load(*data)
-            o_r.fill_(SENTINEL)
-            cnt.fill_(SENTINEL)
-            torch.cuda.synchronize()
-            g.replay()
-            torch.cuda.synchronize()
-            er, found = AC.expect(*data, 0, NULL)
-            assert int(cnt.item()) == int(found.sum())
-            assert np.array_equal(o_r.cpu().numpy().astype(np.int64), er)
-    finally:
-        del g
-        torch.cuda.synchronize()
-        hj.set_strategy("auto")
+
+    def step():
+        hj.build_table(d_rk, d_rp)
+        hj.probe_asof(d_sk, d_sb, o_r, null=NULL, count=cnt)
+
+    def reload(data):
+        load(*data)
+        o_r.fill_(SENTINEL)
+        cnt.fill_(SENTINEL)
+
+    def verify(data):
+        er, found = AC.expect(*data, 0, NULL)
+        assert int(cnt.item()) == int(found.sum())
+        assert np.array_equal(host(o_r), er)
+
+    graph_replay(hj, strategy, setup, step, sets[1:] + sets[:1], reload, verify)
 
 
 # ------------------------------------------------------------------ asof_join

@@ -9,23 +9,12 @@ import pytest
 import torch
 
 from hashjoin import HashJoin, lib
+from join_gpu import assert_radix_kernel, dev, glob_hj, graph_replay, hj, host, radix, timing_reports  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 I64_MIN = -(1 << 63)
 KINDS = ("semi", "anti")
-
-
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def build(hj, rk, rp=None):
@@ -72,21 +61,8 @@ def check_both(hj, rk, sk, sp=None, row_base=0):
     return mask
 
 
-@pytest.fixture
-def glob_hj(hj):
-    hj.set_strategy("global")
-    yield hj
-    hj.set_strategy("auto")
-
-
-def radix(hj, bits):
-    hj.set_strategy("radix", radix_bits=bits)
-
-
 def assert_radix(hj):
-    assert hj.strategy_used == "radix"
-    assert lib.hj_ctx_join_kernel(hj._ctx) == 6
-    assert hj.join_kernel == "k_join_exists"
+    assert_radix_kernel(hj, 6, "k_join_exists")
 
 
 def test_errors_kind_and_state():
@@ -429,18 +405,7 @@ def test_auto_dual_build_picks_strategy_by_probe_size(hj):
 @pytest.mark.parametrize("strategy", ["global", "radix"])
 def test_timing_reports_exists_probes(hj, oracle, strategy):
     rk, rp, sk, sp = oracle.gen_pkfk_i64(51, 4000, 20000, 0.5)
-    hj.set_strategy(strategy, radix_bits=6 if strategy == "radix" else 0)
-    hj.set_timing(True)
-    try:
-        build(hj, rk, rp)
-        probe(hj, sk, sp, "anti")
-        t = hj.last_timing()
-        assert t["probe"] > 0
-        if strategy == "radix":
-            assert t["probe_partition"] > 0 and t["probe_join"] > 0
-    finally:
-        hj.set_timing(False)
-        hj.set_strategy("auto")
+    timing_reports(hj, strategy, lambda: build(hj, rk, rp), [lambda: probe(hj, sk, sp, "anti")])
 
 
 @pytest.mark.parametrize("n,strategy,wide", [(1 << 16, "radix", True), (1 << 12, "global", False)],
@@ -462,42 +427,31 @@ def test_graph_replay(hj, oracle, n, strategy, wide):
         sk.copy_(torch.from_numpy(np.ascontiguousarray(data[1])))
         torch.cuda.synchronize()
 
-    hj.set_strategy(strategy)
-    g = None
-    try:
+    bits = 64 if wide else 32
+    out_s = torch.empty(n, dtype=kt, device="cuda")
+    out_k = torch.empty_like(out_s)
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def setup():
         load(sets[0])
-        bits = 64 if wide else 32
         hj.allocate_hash_table(n, bits)
         hj.build_table(rk, rp)
         hj.reserve_probe(n, bits)
-        out_s = torch.empty(n, dtype=kt, device="cuda")
-        out_k = torch.empty_like(out_s)
-        cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):   # one eager step on the capture stream first
-            hj.build_table(rk, rp)
-            hj.probe_exists(sk, sp, "anti", out_s, out_k, count=cnt)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            hj.build_table(rk, rp)
-            hj.probe_exists(sk, sp, "anti", out_s, out_k, count=cnt)
-        torch.cuda.synchronize()
-        assert hj.strategy_used == strategy
-        for data in sets[1:]:
-            load(data)
-            out_s.fill_(-1)
-            cnt.zero_()
-            torch.cuda.synchronize()
-            g.replay()
-            torch.cuda.synchronize()
-            m = int(cnt.item())
-            sel = ~np.isin(data[1], data[0])
-            pay = (np.arange(n, dtype=np.int64) * 2 + 1) if wide else np.arange(n, dtype=np.int64)
-            assert m == int(sel.sum())
-            assert same_pairs(out_k[:m].cpu().numpy().astype(np.int64), out_s[:m].cpu().numpy().astype(np.int64),
-                              data[1][sel].astype(np.int64), pay[sel])
-    finally:
-        del g
-        torch.cuda.synchronize()
-        hj.set_strategy("auto")
+
+    def step():
+        hj.build_table(rk, rp)
+        hj.probe_exists(sk, sp, "anti", out_s, out_k, count=cnt)
+
+    def reload(data):
+        load(data)
+        out_s.fill_(-1)
+        cnt.zero_()
+
+    def verify(data):
+        m = int(cnt.item())
+        sel = ~np.isin(data[1], data[0])
+        pay = (np.arange(n, dtype=np.int64) * 2 + 1) if wide else np.arange(n, dtype=np.int64)
+        assert m == int(sel.sum())
+        assert same_pairs(host(out_k[:m]), host(out_s[:m]), data[1][sel].astype(np.int64), pay[sel])
+
+    graph_replay(hj, strategy, setup, step, sets[1:], reload, verify)

@@ -15,6 +15,7 @@ import torch
 import expand_cases as XC
 import outer_cases as OC
 from hashjoin import HashJoin, _lib, lib
+from join_gpu import assert_radix_kernel, build, dev, glob_hj, hj, sentinels, timing_reports  # noqa: F401
 from test_gpu_lookup import payloads, repeated_keys_case
 
 pytestmark = pytest.mark.gpu
@@ -24,36 +25,13 @@ NULL, SENTINEL, EXTRA = -9, -12345, 64   # i32 payloads are row ids (>= 0)
 TILE, FAN = _lib.EXPAND_SCAN_TILE, _lib.EXPAND_SCAN_FAN   # the scan's tile, and tile sums per step of their scan
 
 
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-@pytest.fixture
-def glob_hj(hj):
-    hj.set_strategy("global")
-    yield hj
-    hj.set_strategy("auto")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def build(hj, rk, rp):
-    hj.build_table(dev(rk), dev(rp) if rk.dtype == np.int64 else None)
-
-
 def probe(hj, sk, how, cap, d_sk=None):
     """One expand of the current build into sentinel-filled outputs: (M,
     offsets, values) as int64 host arrays; cap None is the count form."""
     n = len(sk)
     dt = torch.int64 if sk.dtype == np.int64 else torch.int32
-    off = torch.full((n + 1 + EXTRA,), SENTINEL, dtype=torch.int64, device="cuda")
-    buf = torch.full((cap + EXTRA,), SENTINEL, dtype=dt, device="cuda") if cap is not None else None
+    off = sentinels(n + 1 + EXTRA, SENTINEL, torch.int64)
+    buf = sentinels(cap + EXTRA, SENTINEL, dt) if cap is not None else None
     out = buf[:cap] if cap else None
     m = int(hj.probe_expand(dev(sk) if d_sk is None else d_sk, off, out, how=how, null=NULL).item())
     return m, off.cpu().numpy(), None if buf is None else buf.cpu().numpy().astype(np.int64)
@@ -79,9 +57,8 @@ def both_kinds(hj, rk, rp, sk):
 
 
 def assert_radix(hj):
-    assert hj.strategy_used == "radix"
-    assert lib.hj_ctx_join_kernel(hj._ctx) == _lib.HJ_JOIN_KERNEL_EXPAND == 10
-    assert hj.join_kernel == "k_join_expand"
+    assert _lib.HJ_JOIN_KERNEL_EXPAND == 10
+    assert_radix_kernel(hj, _lib.HJ_JOIN_KERNEL_EXPAND, "k_join_expand")
 
 
 class radix:
@@ -560,14 +537,4 @@ def test_errors_in_order():
 def test_timing_reports_expand(hj, oracle, strategy):
     rk, _, sk, _ = oracle.gen_pkfk_i64(51, 4000, 20000, 0.5)
     rp = payloads(rk, 51)
-    hj.set_timing(True)
-    try:
-        with radix(hj, 6, strategy):
-            build(hj, rk, rp)
-            check(hj, rk, rp, sk, "inner")
-            t = hj.last_timing()
-            assert t["probe"] > 0
-            if strategy == "radix":
-                assert t["probe_partition"] > 0 and t["probe_join"] > 0
-    finally:
-        hj.set_timing(False)
+    timing_reports(hj, strategy, lambda: build(hj, rk, rp), [lambda: check(hj, rk, rp, sk, "inner")])

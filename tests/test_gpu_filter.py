@@ -19,7 +19,8 @@ import pytest
 import torch
 
 import filter_cases as FC
-from hashjoin import HashJoin, KeyFilter, _lib, gen_pkfk, lib
+from hashjoin import KeyFilter, _lib, gen_pkfk, lib
+from join_gpu import dev, hj, sentinels, strategy  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -31,23 +32,6 @@ KINDS = ["pass", "reject"]
 FORMS = ["i64", "tuples", "i32"]
 
 
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-@contextlib.contextmanager
-def strategy(hj, name, bits=0):
-    hj.set_strategy(name, radix_bits=bits if name == "radix" else 0)
-    try:
-        yield hj
-    finally:
-        hj.set_strategy("auto")
-
-
 @contextlib.contextmanager
 def new_filter(nblocks):
     """A filter whose words start as garbage (they are undefined until the first clear)."""
@@ -57,10 +41,6 @@ def new_filter(nblocks):
         yield f
     finally:
         f.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def words_of(f):
@@ -174,7 +154,7 @@ def test_caller_owned_words_with_guards_and_clear():
     nb, guard = 37, 8
     keys = FC.keys(107, 300)
     want = FC.build(keys, nb)
-    buf = torch.full((nb * 4 + guard,), SENTINEL, dtype=torch.int64, device="cuda")
+    buf = sentinels(nb * 4 + guard, SENTINEL, torch.int64)
     f = KeyFilter(words=buf[:nb * 4])
     try:
         assert f.nblocks == nb and f.words.data_ptr() == buf.data_ptr()
@@ -300,7 +280,7 @@ def run_apply(f, form, kind, pd, n, outs, cap, skey_dev=None):
     views = {o: b[:cap] for o, b in bufs.items()}
     if skey_dev is None:
         skey_dev = dev(np.stack([sk, sp], axis=1)) if form == "tuples" else dev(sk)
-    cnt = torch.full((1,), SENTINEL, dtype=torch.int64, device="cuda")
+    cnt = sentinels(1, SENTINEL, torch.int64)
     f.apply_into(skey_dev, dev(sp) if (form == "i64" and "pay" in outs) else None, kind, views.get("key"),
                  views.get("pay"), views.get("row"), count=cnt, row_base=ROW_BASE)
     assert int(cnt.item()) == M, (form, kind, n, int(cnt.item()), M)
@@ -359,7 +339,7 @@ def test_apply_unaligned_relations(filters, probe_data):
 def test_apply_argument_errors(filters, probe_data):
     f = filters["i64"]._f
     k = dev(probe_data["skey"][:100])
-    o = torch.full((100,), SENTINEL, dtype=torch.int64, device="cuda")
+    o = sentinels(100, SENTINEL, torch.int64)
     c = torch.zeros(1, dtype=torch.int64, device="cuda")
     A = lib.hj_dev_filter_apply_i64
     kp, op, cp = k.data_ptr(), o.data_ptr(), c.data_ptr()

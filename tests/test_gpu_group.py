@@ -16,6 +16,7 @@ import group_cases as GC
 import outer_cases as OC
 import routed_layout as RL
 from hashjoin import HashJoin, _lib, lib
+from join_gpu import assert_radix_kernel, build, dev, glob_hj, graph_replay, hj, host, sentinels  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -25,25 +26,6 @@ COLS = GC.COLS
 HOWS = ("matched", "all")
 
 
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-@pytest.fixture
-def glob_hj(hj):
-    hj.set_strategy("global")
-    yield hj
-    hj.set_strategy("auto")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def s_values(sk, seed=5, row_base=0):
     """S's value column: int64 the whole range, i32 the row ids."""
     if sk.dtype == np.int32:
@@ -51,16 +33,12 @@ def s_values(sk, seed=5, row_base=0):
     return GC.values(len(sk), seed)
 
 
-def build(hj, rk, rp):
-    hj.build_table(dev(rk), dev(rp) if rk.dtype == np.int64 else None)
-
-
 def run(hj, sk, sv, how, cap, cols=COLS, tuples=False, row_base=0):
     """One group probe of the current build with out_cap = cap: (M, {col: the
     whole SENTINEL-filled buffer of cap + EXTRA elements as int64})."""
     wide = sk.dtype == np.int64
     dt = torch.int64 if wide else torch.int32
-    bufs = {c: torch.full((cap + EXTRA,), SENTINEL, dtype=torch.int64 if c == "sum" else dt, device="cuda")
+    bufs = {c: sentinels(cap + EXTRA, SENTINEL, torch.int64 if c == "sum" else dt)
             for c in cols}
     o = {c: (bufs[c][:cap] if c in bufs else None) for c in COLS}
     kw = dict(how=how, out_r=o["r"], out_cnt=o["cnt"], out_sum=o["sum"], out_min=o["min"], out_max=o["max"], null=NULL)
@@ -95,9 +73,8 @@ def check(hj, rk, rp, sk, sv, hows=HOWS, cols=COLS, tuples=False, row_base=0):
 
 
 def assert_radix(hj):
-    assert hj.strategy_used == "radix"
-    assert lib.hj_ctx_join_kernel(hj._ctx) == _lib.HJ_JOIN_KERNEL_GROUP == 8
-    assert hj.join_kernel == "k_join_group"
+    assert _lib.HJ_JOIN_KERNEL_GROUP == 8
+    assert_radix_kernel(hj, _lib.HJ_JOIN_KERNEL_GROUP, "k_join_group")
 
 
 def radix_case(hj, bits, rk, sk, seed=3, **kw):
@@ -591,46 +568,33 @@ def test_graph_replay(hj, oracle, n, strategy, wide):
             sv.copy_(torch.from_numpy(vals))
         torch.cuda.synchronize()
 
-    hj.set_strategy(strategy)
-    g = None
-    try:
-        bits = 64 if wide else 32
+    bits = 64 if wide else 32
+    outs = {c: torch.empty(n, dtype=torch.int64 if c == "sum" else kt, device="cuda") for c in COLS}
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def setup():
         hj.allocate_hash_table(n, bits)
         hj.reserve_group(n, bits)
         build(hj, rk, rp)
         hj.reserve_probe(n, bits)
-        outs = {c: torch.empty(n, dtype=torch.int64 if c == "sum" else kt, device="cuda") for c in COLS}
-        cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-
-        def probe():
-            hj.probe_group(sk, sv, "all", outs["r"], outs["cnt"], outs["sum"], outs["min"], outs["max"], null=NULL,
-                           count=cnt)
-
         load(sets[0], s_values(sets[0], 0))
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):   # one eager step on the capture stream first
-            probe()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            probe()
-        torch.cuda.synchronize()
-        assert hj.strategy_used == strategy
-        for j, keys in enumerate(sets[1:] + sets[:1]):
-            vals = s_values(keys, 100 + j)
-            load(keys, vals)
-            for t in outs.values():
-                t.fill_(SENTINEL)
-            cnt.fill_(SENTINEL)
-            torch.cuda.synchronize()
-            g.replay()
-            torch.cuda.synchronize()
-            e = GC.expect(rk, rp, keys, vals, "all", NULL)
-            assert int(cnt.item()) == n
-            o = np.argsort(outs["r"].cpu().numpy(), kind="stable")
-            for c in COLS:
-                assert np.array_equal(outs[c].cpu().numpy().astype(np.int64)[o], e[c]), (j, c)
-    finally:
-        del g
-        torch.cuda.synchronize()
-        hj.set_strategy("auto")
+
+    def probe():
+        hj.probe_group(sk, sv, "all", outs["r"], outs["cnt"], outs["sum"], outs["min"], outs["max"], null=NULL,
+                       count=cnt)
+
+    def reload(entry):
+        load(*entry[1:])
+        for t in (*outs.values(), cnt):
+            t.fill_(SENTINEL)
+
+    def verify(entry):
+        j, keys, vals = entry
+        e = GC.expect(rk, rp, keys, vals, "all", NULL)
+        assert int(cnt.item()) == n
+        o = np.argsort(outs["r"].cpu().numpy(), kind="stable")
+        for c in COLS:
+            assert np.array_equal(host(outs[c])[o], e[c]), (j, c)
+
+    graph_replay(hj, strategy, setup, probe, [(j, keys, s_values(keys, 100 + j))
+                                              for j, keys in enumerate(sets[1:] + sets[:1])], reload, verify)

@@ -13,31 +13,14 @@ import torch
 
 import outer_cases as OC
 from hashjoin import HashJoin, _lib, lib
+from join_gpu import (assert_radix_kernel, build, dev, glob_hj, graph_replay, hj, host, sentinels,  # noqa: F401
+                      timing_reports)
 from positional_cases import EXTRA, NULL, SENTINEL   # -9, -12345, 64: i32 payloads are row ids (>= 0)
 from positional_cases import lookup_expect as expect
 
 pytestmark = pytest.mark.gpu
 
 I64_MIN = OC.I64_MIN
-
-
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-@pytest.fixture
-def glob_hj(hj):
-    hj.set_strategy("global")
-    yield hj
-    hj.set_strategy("auto")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def payloads(rk, seed=1):
@@ -48,17 +31,13 @@ def payloads(rk, seed=1):
     return (np.random.default_rng(seed).permutation(n).astype(np.int64) - n // 2) * 3 + 1
 
 
-def build(hj, rk, rp):
-    hj.build_table(dev(rk), dev(rp) if rk.dtype == np.int64 else None)
-
-
 def probe(hj, sk, want_r=True, want_cnt=True):
     """One lookup of the current build into sentinel-filled outputs EXTRA rows
     longer than S: (d_count, out_r, out_cnt) as int64 host arrays (None if not asked for)."""
     n = len(sk)
     dt = torch.int64 if sk.dtype == np.int64 else torch.int32
-    o_r = torch.full((n + EXTRA,), SENTINEL, dtype=dt, device="cuda") if want_r else None
-    o_c = torch.full((n + EXTRA,), SENTINEL, dtype=torch.int32, device="cuda") if want_cnt else None
+    o_r = sentinels(n + EXTRA, SENTINEL, dt) if want_r else None
+    o_c = sentinels(n + EXTRA, SENTINEL, torch.int32) if want_cnt else None
     m = int(hj.probe_lookup(dev(sk), o_r, o_c, null=NULL).item())
     host = lambda t: None if t is None else t.cpu().numpy().astype(np.int64)   # noqa: E731
     return m, host(o_r), host(o_c)
@@ -79,9 +58,8 @@ def check(hj, rk, rp, sk, want_r=True, want_cnt=True):
 
 
 def assert_radix(hj):
-    assert hj.strategy_used == "radix"
-    assert lib.hj_ctx_join_kernel(hj._ctx) == _lib.HJ_JOIN_KERNEL_LOOKUP == 7
-    assert hj.join_kernel == "k_join_lookup"
+    assert _lib.HJ_JOIN_KERNEL_LOOKUP == 7
+    assert_radix_kernel(hj, _lib.HJ_JOIN_KERNEL_LOOKUP, "k_join_lookup")
 
 
 # ------------------------------------------------------------------ global
@@ -450,18 +428,7 @@ def test_errors_in_order():
 def test_timing_reports_lookup(hj, oracle, strategy):
     rk, _, sk, _ = oracle.gen_pkfk_i64(51, 4000, 20000, 0.5)
     rp = payloads(rk, 51)
-    hj.set_strategy(strategy, radix_bits=6 if strategy == "radix" else 0)
-    hj.set_timing(True)
-    try:
-        build(hj, rk, rp)
-        check(hj, rk, rp, sk)
-        t = hj.last_timing()
-        assert t["probe"] > 0
-        if strategy == "radix":
-            assert t["probe_partition"] > 0 and t["probe_join"] > 0
-    finally:
-        hj.set_timing(False)
-        hj.set_strategy("auto")
+    timing_reports(hj, strategy, lambda: build(hj, rk, rp), [lambda: check(hj, rk, rp, sk)])
 
 
 @pytest.mark.parametrize("n,strategy,wide", [(1 << 16, "radix", True), (1 << 12, "global", False)],
@@ -483,39 +450,27 @@ def test_graph_replay(hj, oracle, n, strategy, wide):
         sk.copy_(torch.from_numpy(np.ascontiguousarray(keys)))
         torch.cuda.synchronize()
 
-    hj.set_strategy(strategy)
-    g = None
-    try:
-        bits = 64 if wide else 32
+    bits = 64 if wide else 32
+    o_r = torch.empty(n, dtype=kt, device="cuda")
+    o_c = torch.empty(n, dtype=torch.int32, device="cuda")
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def setup():
         hj.allocate_hash_table(n, bits)
         build(hj, rk, rp)
         hj.reserve_probe(n, bits)
-        o_r = torch.empty(n, dtype=kt, device="cuda")
-        o_c = torch.empty(n, dtype=torch.int32, device="cuda")
-        cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
         load(sets[0])
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):   # one eager step on the capture stream first
-            hj.probe_lookup(sk, o_r, o_c, null=NULL, count=cnt)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            hj.probe_lookup(sk, o_r, o_c, null=NULL, count=cnt)
-        torch.cuda.synchronize()
-        assert hj.strategy_used == strategy
-        for keys in sets[1:] + sets[:1]:
-            load(keys)
-            o_r.fill_(SENTINEL)
-            o_c.fill_(SENTINEL)
-            cnt.fill_(SENTINEL)
-            torch.cuda.synchronize()
-            g.replay()
-            torch.cuda.synchronize()
-            er, ec = expect(rk, rp, keys)
-            assert int(cnt.item()) == int((ec > 0).sum())
-            assert np.array_equal(o_r.cpu().numpy().astype(np.int64), er)
-            assert np.array_equal(o_c.cpu().numpy().astype(np.int64), ec)
-    finally:
-        del g
-        torch.cuda.synchronize()
-        hj.set_strategy("auto")
+
+    def reload(keys):
+        load(keys)
+        for t in (o_r, o_c, cnt):
+            t.fill_(SENTINEL)
+
+    def verify(keys):
+        er, ec = expect(rk, rp, keys)
+        assert int(cnt.item()) == int((ec > 0).sum())
+        assert np.array_equal(host(o_r), er)
+        assert np.array_equal(host(o_c), ec)
+
+    graph_replay(hj, strategy, setup, lambda: hj.probe_lookup(sk, o_r, o_c, null=NULL, count=cnt),
+                 sets[1:] + sets[:1], reload, verify)

@@ -13,35 +13,12 @@ import torch
 
 import outer_cases as OC
 import routed_layout as RL
-from hashjoin import HashJoin
+from join_gpu import dev, glob_hj, graph_replay, hj, host, radix, timing_reports  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 I64_MIN = -(1 << 63)
 RADIX_KERNELS = ("k_join_b", "k_join_u_stream", "k_join_grp")
-
-
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-@pytest.fixture
-def glob_hj(hj):
-    hj.set_strategy("global")
-    yield hj
-    hj.set_strategy("auto")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def radix(hj, bits):
-    hj.set_strategy("radix", radix_bits=bits)
 
 
 def assert_radix(hj):
@@ -511,18 +488,7 @@ def test_outer_probe_after_routed_build(hj, oracle):
 @pytest.mark.parametrize("strategy", ["global", "radix"])
 def test_timing_reports_outer_probes(hj, oracle, strategy):
     rk, rp, sk, sp = oracle.gen_pkfk_i64(51, 4000, 20000, 0.5)
-    hj.set_strategy(strategy, radix_bits=6 if strategy == "radix" else 0)
-    hj.set_timing(True)
-    try:
-        build(hj, rk, rp)
-        probe(hj, sk, sp, -1, cap=len(sk))
-        t = hj.last_timing()
-        assert t["probe"] > 0
-        if strategy == "radix":
-            assert t["probe_partition"] > 0 and t["probe_join"] > 0
-    finally:
-        hj.set_timing(False)
-        hj.set_strategy("auto")
+    timing_reports(hj, strategy, lambda: build(hj, rk, rp), [lambda: probe(hj, sk, sp, -1, cap=len(sk))])
 
 
 @pytest.mark.parametrize("n,strategy,wide", [(1 << 16, "radix", True), (1 << 12, "global", False)],
@@ -548,51 +514,39 @@ def test_graph_replay(hj, oracle, n, strategy, wide):
         sk.copy_(torch.from_numpy(np.ascontiguousarray(data[1])))
         torch.cuda.synchronize()
 
-    hj.set_strategy(strategy)
-    g = None
-    try:
+    bits, cap = 64 if wide else 32, 8 * n
+    out_r = torch.empty(cap, dtype=kt, device="cuda")
+    out_s = torch.empty_like(out_r)
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+    pay_r = np.arange(n, dtype=np.int64) * 3 + 2 if wide else np.arange(n, dtype=np.int64)
+    pay_s = np.arange(n, dtype=np.int64) * 2 + 1 if wide else np.arange(n, dtype=np.int64)
+
+    def setup():
         load(sets[0])
-        bits = 64 if wide else 32
         hj.allocate_hash_table(n, bits)
         hj.build_table(rk, rp)
         hj.reserve_probe(n, bits)
-        cap = 8 * n
-        out_r = torch.empty(cap, dtype=kt, device="cuda")
-        out_s = torch.empty_like(out_r)
-        cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):   # one eager step on the capture stream first
-            hj.build_table(rk, rp)
-            hj.probe_outer(sk, sp, out_r, out_s, null=-1, count=cnt)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=s):
-            hj.build_table(rk, rp)
-            hj.probe_outer(sk, sp, out_r, out_s, null=-1, count=cnt)
-        torch.cuda.synchronize()
-        assert hj.strategy_used == strategy
-        pay_r = np.arange(n, dtype=np.int64) * 3 + 2 if wide else np.arange(n, dtype=np.int64)
-        pay_s = np.arange(n, dtype=np.int64) * 2 + 1 if wide else np.arange(n, dtype=np.int64)
-        for data in sets[1:]:
-            load(data)
-            out_r.fill_(-9)
-            cnt.zero_()
-            torch.cuda.synchronize()
-            g.replay()
-            torch.cuda.synchronize()
-            m = int(cnt.item())
-            er, es = np_join(data[0], pay_r, data[1], pay_s)
-            un = ~np.isin(data[1], data[0])
-            er, es = np.concatenate([er, np.full(int(un.sum()), -1, np.int64)]), np.concatenate([es, pay_s[un]])
-            assert m == len(er) <= cap
-            assert oracle.same_multiset(out_r[:m].cpu().numpy().astype(np.int64),
-                                        out_s[:m].cpu().numpy().astype(np.int64), er, es)
-            if data is grp:   # the replay chose its kernel from this data, on the device
-                assert m < cap and hj.join_kernel == "k_join_grp"
-    finally:
-        del g
-        torch.cuda.synchronize()
-        hj.set_strategy("auto")
+
+    def step():
+        hj.build_table(rk, rp)
+        hj.probe_outer(sk, sp, out_r, out_s, null=-1, count=cnt)
+
+    def reload(data):
+        load(data)
+        out_r.fill_(-9)
+        cnt.zero_()
+
+    def verify(data):
+        m = int(cnt.item())
+        er, es = np_join(data[0], pay_r, data[1], pay_s)
+        un = ~np.isin(data[1], data[0])
+        er, es = np.concatenate([er, np.full(int(un.sum()), -1, np.int64)]), np.concatenate([es, pay_s[un]])
+        assert m == len(er) <= cap
+        assert oracle.same_multiset(host(out_r[:m]), host(out_s[:m]), er, es)
+        if data is grp:   # the replay chose its kernel from this data, on the device
+            assert m < cap and hj.join_kernel == "k_join_grp"
+
+    graph_replay(hj, strategy, setup, step, sets[1:], reload, verify)
 
 
 def test_outer_join_method(hj, oracle):

@@ -19,23 +19,12 @@ import torch
 
 import outer_cases as OC
 from hashjoin import HashJoin
+from join_gpu import dev, hj, sentinels  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 RADIX_KERNELS = ("k_join_b", "k_join_u_stream", "k_join_grp")
 NULL_R, NULL_S, SENTINEL = -9, -10, -12345   # payloads are >= 0
-
-
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 class Case:
@@ -59,7 +48,7 @@ class Case:
     def probe(self, hj, kind, cap, extra=64):
         """Probe `kind` ("inner" too) into outputs of `cap` rows followed by
         `extra` sentinel rows the probe is not told about: (M, r, s), all cap + extra rows."""
-        back_r = torch.full((cap + extra,), SENTINEL, dtype=self.dt, device="cuda")
+        back_r = sentinels(cap + extra, SENTINEL, self.dt)
         back_s = torch.full_like(back_r, SENTINEL)
         o_r, o_s = back_r[:cap], back_s[:cap]
         if kind == "inner":

@@ -17,20 +17,9 @@ from hashjoin import HashJoin
 from hashjoin import memref as MR
 
 from conftest import golden_cases
+from join_gpu import dev, hj  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def host(t):

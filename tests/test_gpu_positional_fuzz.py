@@ -21,7 +21,8 @@ import expand_cases as XC
 import group_cases as GC
 import outer_cases as OC
 import positional_cases as PC
-from hashjoin import HashJoin, _lib, lib
+from hashjoin import _lib, lib
+from join_gpu import dev, hj, host, sentinels  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -31,22 +32,6 @@ PROBES = ("lookup", "asof-0", "asof-1", "asof-2", "asof-3", "expand-inner", "exp
           "group-matched", "group-all")
 KERNEL = {"lookup": _lib.HJ_JOIN_KERNEL_LOOKUP, "asof": _lib.HJ_JOIN_KERNEL_ASOF,
           "expand": _lib.HJ_JOIN_KERNEL_EXPAND, "group": _lib.HJ_JOIN_KERNEL_GROUP}
-
-
-@pytest.fixture(scope="module")
-def hj():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().astype(np.int64)
 
 
 def expectations(case, d):
@@ -78,8 +63,8 @@ def run_probe(hj, name, d, dv, e):
     dt = torch.int64 if wide else torch.int32
     if name == "lookup":
         er, ec = e[name]
-        o_r = torch.full((n + EXTRA,), SENTINEL, dtype=dt, device="cuda")
-        o_c = torch.full((n + EXTRA,), SENTINEL, dtype=torch.int32, device="cuda")
+        o_r = sentinels(n + EXTRA, SENTINEL, dt)
+        o_c = sentinels(n + EXTRA, SENTINEL, torch.int32)
         m = int(hj.probe_lookup(dv["sk"], o_r, o_c, null=NULL).item())
         g_r, g_c = host(o_r), host(o_c)
         assert np.array_equal(g_r[:n], er), np.flatnonzero(g_r[:n] != er)[:8]
@@ -90,7 +75,7 @@ def run_probe(hj, name, d, dv, e):
     if name.startswith("asof"):
         er, found = e[name]
         direction, strict = AC.KIND_ARGS[int(name[-1])]
-        o_r = torch.full((n + EXTRA,), SENTINEL, dtype=dt, device="cuda")
+        o_r = sentinels(n + EXTRA, SENTINEL, dt)
         m = int(hj.probe_asof(dv["sk"], dv["sb"], o_r, direction=direction, strict=strict, null=NULL).item())
         g = host(o_r)
         assert np.array_equal(g[:n], er), np.flatnonzero(g[:n] != er)[:8]
@@ -101,8 +86,8 @@ def run_probe(hj, name, d, dv, e):
         if e[name] is None:   # a result of fewer than two elements has no cap inside it
             return None
         how, x, cap = e[name] if name == "expand-cut" else (name[7:], e[name], e[name].m)
-        off = torch.full((n + 1 + EXTRA,), SENTINEL, dtype=torch.int64, device="cuda")
-        buf = torch.full((cap + EXTRA,), SENTINEL, dtype=dt, device="cuda")
+        off = sentinels(n + 1 + EXTRA, SENTINEL, torch.int64)
+        buf = sentinels(cap + EXTRA, SENTINEL, dt)
         m = int(hj.probe_expand(dv["sk"], off, buf[:cap] if cap else None, how=how, null=NULL).item())
         off, vals = off.cpu().numpy(), host(buf)
         assert m == x.m, (m, x.m)
@@ -114,7 +99,7 @@ def run_probe(hj, name, d, dv, e):
     how = name[6:]
     x = e[name]
     cap = max(1, len(d["rk"]))
-    bufs = {c: torch.full((cap + EXTRA,), SENTINEL, dtype=torch.int64 if c == "sum" else dt, device="cuda")
+    bufs = {c: sentinels(cap + EXTRA, SENTINEL, torch.int64 if c == "sum" else dt)
             for c in GC.COLS}
     kw = {f"out_{c}": bufs[c][:cap] for c in GC.COLS}
     if wide:

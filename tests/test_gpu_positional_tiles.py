@@ -22,6 +22,7 @@ import asof_cases as AC
 import expand_cases as XC
 import positional_cases as PC
 from hashjoin import HashJoin
+from join_gpu import dev, sentinels
 
 pytestmark = pytest.mark.gpu
 
@@ -38,10 +39,6 @@ def hj():
     h.set_strategy("global")
     yield h
     h.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,8 +93,8 @@ def test_lookup_strided(hj, wide, repeats):
     if wide:   # the INT64_MIN probe rows answer from the side list
         assert (ec[NULL_ROWS] == 1).all() and (er[NULL_ROWS] == c["rp"][PC.SIDE_ROW]).all()
     for want_r, want_cnt in ((True, True), (True, False), (False, True)):
-        o_r = torch.full((n + EXTRA,), SENTINEL, dtype=dt, device="cuda") if want_r else None
-        o_c = torch.full((n + EXTRA,), SENTINEL, dtype=torch.int32, device="cuda") if want_cnt else None
+        o_r = sentinels(n + EXTRA, SENTINEL, dt) if want_r else None
+        o_c = sentinels(n + EXTRA, SENTINEL, torch.int32) if want_cnt else None
         m = int(hj.probe_lookup(c["d_sk"], o_r, o_c, null=NULL).item())
         assert hj.strategy_used == "global"
         g_r, g_c = host(o_r), host(o_c)
@@ -122,7 +119,7 @@ def test_asof_strided(hj, wide, repeats, kind):
         assert 0 < int(found.sum()) < int((c["cnt"] > 0).sum())
         if wide:
             assert 0 < int(found[NULL_ROWS].sum()) < len(NULL_ROWS)
-    o_r = torch.full((n + EXTRA,), SENTINEL, dtype=torch.int64 if wide else torch.int32, device="cuda")
+    o_r = sentinels(n + EXTRA, SENTINEL, torch.int64 if wide else torch.int32)
     direction, strict = AC.KIND_ARGS[kind]
     m = int(hj.probe_asof(c["d_sk"], c["d_sb"], o_r, direction=direction, strict=strict, null=NULL).item())
     assert hj.strategy_used == "global"
@@ -138,8 +135,8 @@ def expand(hj, c, e, how, cap):
     the values below min(M, cap) segment by segment, nothing at or past it."""
     n = len(c["sk"])
     dt = torch.int64 if c["wide"] else torch.int32
-    off = torch.full((n + 1 + EXTRA,), SENTINEL, dtype=torch.int64, device="cuda")
-    buf = torch.full((cap + EXTRA,), SENTINEL, dtype=dt, device="cuda") if cap is not None else None
+    off = sentinels(n + 1 + EXTRA, SENTINEL, torch.int64)
+    buf = sentinels(cap + EXTRA, SENTINEL, dt) if cap is not None else None
     m = int(hj.probe_expand(c["d_sk"], off, None if buf is None else buf[:cap], how=how, null=NULL).item())
     assert hj.strategy_used == "global"
     assert m == e.m, (m, e.m)

@@ -10,19 +10,9 @@ import torch
 
 import hashjoin
 from hashjoin import HashJoin
+from join_gpu import dev, hj  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hj():
-    h = HashJoin(0)
-    yield h
-    h.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def run(hj, rk, rp, sk, sp, bits, capacity=None):

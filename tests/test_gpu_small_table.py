@@ -11,6 +11,7 @@ import torch
 
 import positional_cases as PC
 from hashjoin import HashJoin
+from join_gpu import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +23,6 @@ def hj():
     h.set_strategy("global")
     yield h
     h.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def join(hj, rk, rp, sk, sp):
